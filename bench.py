@@ -23,7 +23,10 @@ RCCL/xGMI once per frame ("strong" scaling: total work fixed).
 --animate adds the reference command line's moving rectangle light (restir_di_main.cpp:7-12) and a slowly orbiting camera to
 config 2 / 4: every frame updates the light's transform (in-place rebuild of the animated BVH subtree) and the camera.
 
-Rank 0 prints ONE JSON line (see DESIGN.md "Measurement").
+Rank 0 prints ONE JSON line (see DESIGN.md "Measurement").  A plain run sets up, warms up, times the --steps frames and prints
+the line; --full adds everything else the line can carry: the per-kernel roofline, the GPU BVH build time, the MSE against the
+64k-spp reference, the CPU baseline, the other configurations and (N > 1) the check of the gathered frame against the ranks' bands.
+--dump-outputs DIR writes the frame the last timed step rendered to DIR (dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -149,9 +152,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--mse-ref-spp", type=int, default=65536, help="frames of plain-NEE reference accumulated in fp64 for the MSE figure; the metric names 64k (0 = skip)")
-    ap.add_argument("--cpu-sample", type=str, default="480x270", help="resolution of the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline, GPU BVH build time, MSE, CPU baseline, other configurations, gathered-frame check (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frame the last timed step rendered to DIR as .npy (dump_outputs)")
+    ap.add_argument("--mse-ref-spp", type=int, default=65536, help="--full: frames of plain-NEE reference accumulated in fp64 for the MSE figure; the metric names 64k (0 = skip)")
+    ap.add_argument("--cpu-sample", type=str, default="480x270", help="--full: resolution of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline")
     ap.add_argument("--balance-bands", type=int, default=2,
                     help="N > 1: rounds of cost-balancing the row bands during the warm-up (each round: 4 frames of every rank's band alone, "
                          "all-gather of the times, gfxh_balance_bands, band renderers re-created); 0 = equal bands")
@@ -165,13 +171,16 @@ def parse():
     ap.add_argument("--config", type=int, default=2, choices=[1, 2, 3, 4], help="BASELINE.json configs[] index (0-based); 2 = the metric's configuration")
     ap.add_argument("--animate", action="store_true", help="configs 2 / 4: moving rectangle light (restir_di_main.cpp:7-12) + slowly orbiting camera")
     ap.add_argument("--other-configs", type=int, default=1,
-                    help="default run only (configs[2], static, textured, one GPU): afterwards measure configs[1], [3], [4] and --animate for --other-steps "
+                    help="--full, default run only (configs[2], static, textured, one GPU): afterwards measure configs[1], [3], [4] and --animate for --other-steps "
                          "steps each (5 warm-up frames) and report them inside the one JSON line as `other_configs` (0 = skip)")
     ap.add_argument("--spawn-timeout", type=float, default=420.0, help="N > 1 without a launcher: seconds the ranks this command starts may take before they are killed")
     ap.add_argument("--rank-timeout", type=float, default=300.0, help="N > 1: seconds a rank may spend between the start of its warm-up and the end of its timed frames before it reports where it is and exits (0 = no limit)")
     ap.add_argument("--other-steps", type=int, default=20)
     ap.add_argument("--other-timeout", type=float, default=240.0, help="seconds each other-configs child process may take before it is killed (the headline stands on its own)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 BUNNY_OBJ = os.path.join(ROOT, "tests", "golden", "assets", "stanford_bunny_309_faces.obj")   # data fixture (a mesh the reference's harness names)
@@ -259,7 +268,7 @@ def _other_configs(args):
     import subprocess
     others = {}
     for name, flags in OTHER_CONFIGS:
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.other_steps), "--warmup", "5", "--mse-ref-spp", "0",
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.other_steps), "--warmup", "5", "--full", "--mse-ref-spp", "0",
                "--cpu-sample", "0", "--other-configs", "0"] + flags
         t0 = time.perf_counter()
         try:
@@ -318,11 +327,11 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
     result = run_config(args, rank, local_rank, world, dist)
     headline_only = args.config == 2 and not (args.animate or args.plain or args.cluttered)
-    if rank == 0 and world == 1 and args.other_configs and headline_only:
+    if rank == 0 and world == 1 and args.full and args.other_configs and headline_only:
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
         result["other_configs"] = _other_configs(args)
-    if world > 1 and args.other_configs and headline_only:
+    if world > 1 and args.full and args.other_configs and headline_only:
         # N > 1: BASELINE's configs[4] IS the split across the GPUs of the node (unbiased estimator + environment map), so the same ranks
         # run a short measurement of it after the headline is complete.  The headline must not depend on it: when the ranks do not finish it
         # in time, every rank's watchdog ends its process with code 0 and rank 0 prints the headline with the reason first.
@@ -612,6 +621,9 @@ def run_config(args, rank, local_rank, world, dist, on_timeout=None):
         watchdog.cancel()
     ms_per_step = 1e3 * elapsed / args.steps
     mpaths = W * H * args.steps / elapsed / 1e6
+    if args.dump_outputs and rank == 0:
+        # after finish_gather rank 0's beauty buffer holds every band: the whole frame on every path
+        dump_outputs(args.dump_outputs, ctx.read_device(renderer.beauty_ptr(), W * H * 16).view(np.float32).reshape(H, W, 4))
 
     result = {
         "metric": metric,
@@ -630,7 +642,7 @@ def run_config(args, rank, local_rank, world, dist, on_timeout=None):
         "setup_s": round(setup_s, 2),
     }
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         result["gpu_bvh_build_ms"] = gpu_bvh_build_ms(ctx, stream)
         if not args.no_roofline:
             ctx.tunable_set("pt_overlap", 0)          # per-kernel durations: kernels that share the GPU with another stream read longer than they are
@@ -661,7 +673,7 @@ def run_config(args, rank, local_rank, world, dist, on_timeout=None):
             else:
                 result["cpu_baseline"] = {"value": None, "unit": "Mpaths/s", "cores": 0, "kind": "port",
                                           "sample": "not timed for this line: see the default line (configs[2], static) for the CPU restatement on this host"}
-    if world > 1:
+    if world > 1 and args.full:
         # what the ranks can say about the frame together: rank 0's gathered frame holds every rank's band bit for bit, and the MSE leg.
         # From here on a failure costs these legs, not the measurement (leave_with_the_measurement).
         import torch
@@ -974,6 +986,23 @@ def mse_vs_reference(ctx, hs, renderer, cam, W, H, ref_spp, band=None, dist=None
            "note": "the metric names a 64k-spp reference (the default); a smaller --mse-ref-spp reads higher by the reference's own noise"}
     out.update(how)
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the float4 HDR beauty buffer, (H, W, 4) float32,
+    top row first -- as out_dir/beauty.npy.  A frame above DUMP_LIMIT_BYTES (above 2048 x 2048) is written as a fixed, seeded sample
+    of half that many bytes of its pixels instead: out_dir/beauty_sample.npy, (n, 4) float32, pixels in row-major order."""
+    os.makedirs(out_dir, exist_ok=True)
+    if frame.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "beauty.npy"), frame)
+        return
+    pixels = frame.reshape(-1, 4)
+    n = DUMP_LIMIT_BYTES // 2 // pixels.itemsize // 4
+    pick = np.sort(np.random.default_rng(0).choice(len(pixels), n, replace=False))
+    np.save(os.path.join(out_dir, "beauty_sample.npy"), pixels[pick])
 
 
 def _device_view(ptr, num_floats):

@@ -241,7 +241,7 @@ def test_counter_files_carry_the_hash_of_the_sources_they_were_measured_on(tmp_p
 
 
 def test_the_committed_bench_line_keeps_the_driver_contract():
-    """profiles/r06_bench_default.json is what `python bench.py` printed on an MI355X at the end of the round: ONE JSON line with the
+    """profiles/r06_bench_default.json is what `python bench.py --full` prints on an MI355X (the round's line): ONE JSON line with the
     fields the driver reads, the roofline and cpu_baseline objects of the measurement section, every other BASELINE configuration inside
     it, and counter figures that belong to the kernel sources of this tree."""
     import json
@@ -274,3 +274,26 @@ def test_the_committed_bench_line_keeps_the_driver_contract():
     for name, o in d["other_configs"].items():
         assert "error" not in o and o["value"] > 0 and o["ms_per_step"] > 0, name
     assert d["mse"]["ref_spp"] == 65536 and d["mse"]["mse"] > 0
+
+
+def test_bench_dump_outputs_writes_the_frame_or_a_fixed_sample_of_it(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: a frame within the budget is written whole as beauty.npy; a larger one as the same seeded sample of its
+    pixels on every run, at most half the budget."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    frame = np.random.default_rng(5).random((6, 10, 4), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), frame)
+    assert os.listdir(tmp_path / "whole") == ["beauty.npy"]
+    got = np.load(tmp_path / "whole" / "beauty.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", frame.nbytes - 1)
+    samples = []
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), frame)
+        assert os.listdir(tmp_path / run) == ["beauty_sample.npy"]
+        samples.append(np.load(tmp_path / run / "beauty_sample.npy"))
+    s = samples[0]
+    assert s.dtype == np.float32 and s.shape == (bench.DUMP_LIMIT_BYTES // 2 // 16, 4) and np.array_equal(s, samples[1])
+    rows = {tuple(p) for p in frame.reshape(-1, 4)}
+    assert all(tuple(p) in rows for p in s) and len({tuple(p) for p in s}) == len(s)

@@ -358,6 +358,30 @@ def test_cpp_rccl_callback_drives_a_band_renderer(built_lib):
 
 
 @pytest.mark.gpu
+def test_plain_bench_run_times_the_steps_alone_and_dumps_the_last_frame(built_lib, tmp_path):
+    """`bench.py --gpus 1` without --full: the headline line alone (none of the legs --full adds), exactly --steps timed frames, and
+    --dump-outputs writes the frame of the last of them as its caller reads it (the float4 HDR beauty buffer)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    W, H = 320, 192
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--width", str(W), "--height", str(H),
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "Mpaths/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - W * H / d["ms_per_step"] / 1e3) < 0.01 * d["value"]
+    for key in ("roofline", "kernels_ms_per_frame", "mse", "cpu_baseline", "other_configs", "gpu_bvh_build_ms"):
+        assert key not in d, key
+    assert os.listdir(tmp_path) == ["beauty.npy"]
+    frame = np.load(tmp_path / "beauty.npy")
+    assert frame.dtype == np.float32 and frame.shape == (H, W, 4) and np.isfinite(frame).all() and frame[..., :3].max() > 0
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("flags", [[], ["--config", "4"], ["--animate"]])
 def test_bench_frame_loop_with_two_ranks_on_one_gpu(built_lib, flags):
     """`bench.py --gpus 2` as the driver launches it (torch.distributed.run, one process per rank), on a one-GPU box: GFX_BENCH_ONE_GPU=1
@@ -372,7 +396,7 @@ def test_bench_frame_loop_with_two_ranks_on_one_gpu(built_lib, flags):
     env = dict(os.environ, GFX_BENCH_ONE_GPU="1", MASTER_ADDR="127.0.0.1")
     port = 29600 + (os.getpid() + len(flags) * 7) % 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--mse-ref-spp", "0", "--cpu-sample", "0"] + flags
+           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--full", "--mse-ref-spp", "0", "--cpu-sample", "0"] + flags
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -408,7 +432,7 @@ def test_bench_starts_its_own_ranks_and_survives_a_transport_that_hangs(built_li
     env = dict(os.environ, GFX_BENCH_ONE_GPU="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    tail = ["--steps", "3", "--warmup", "2", "--cpu-sample", "0"]
+    tail = ["--steps", "3", "--warmup", "2", "--full", "--cpu-sample", "0"]
     base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--mse-ref-spp", "0"] + tail
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--mse-ref-spp", "48"] + tail, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -5,7 +5,7 @@
 # names (listed next to each step).  Replaces the one-off tools/sessions/r0*.sh scripts of rounds 1-2.
 #
 #   tests        python -m pytest tests -m gpu -x -q                                   -> gpurun_out/r03/tests.log
-#   bench        default bench.py line (64k-spp MSE + CPU rows, ~3 min)                -> profiles/r03_bench_default.json
+#   bench        bench.py --full line (64k-spp MSE + CPU rows, ~3 min)                 -> profiles/r03_bench_default.json
 #   benchq       bench.py without the MSE / CPU legs, default + --plain + --cluttered  -> profiles/r03_bench_quick.jsonl
 #   ab           tools/pixel_map_ab.py: scan-line / tiled / XCD-supertile pixel maps   -> profiles/r03_pixel_map_ab.jsonl
 #   absweep      the same over supertile shapes                                        -> profiles/r03_pixel_map_supers.jsonl
@@ -32,7 +32,7 @@ export TMPDIR=/tmp
 ROUND=${ROUND:-r06}
 OUT=gpurun_out/$ROUND
 mkdir -p $OUT
-B="python bench.py --steps 6 --warmup 2 --mse-ref-spp 0 --cpu-sample 0 --other-configs 0"
+B="python bench.py --steps 6 --warmup 2 --full --mse-ref-spp 0 --cpu-sample 0 --other-configs 0"
 
 pmc_passes() {   # $1 = output tag, rest = environment assignments; $BFLAGS = extra bench.py flags (--config N, --animate)
   local tag=$1; shift
@@ -54,9 +54,9 @@ for step in "$@"; do
   echo "==== $step"
   case $step in
     tests)     timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -15 | tee $OUT/tests.log ;;
-    bench)     timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; cat $OUT/bench_default.json | cut -c1-600 ;;
+    bench)     timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; cat $OUT/bench_default.json | cut -c1-600 ;;
     benchq)    : > $OUT/bench_quick.jsonl
-               for f in "" "--plain" "--cluttered"; do timeout 300 python bench.py --steps 30 --warmup 5 --mse-ref-spp 0 --cpu-sample 0 --other-configs 0 $f >> $OUT/bench_quick.jsonl 2>> $OUT/bench_quick.err; done
+               for f in "" "--plain" "--cluttered"; do timeout 300 python bench.py --steps 30 --warmup 5 --full --mse-ref-spp 0 --cpu-sample 0 --other-configs 0 $f >> $OUT/bench_quick.jsonl 2>> $OUT/bench_quick.err; done
                cut -c1-400 $OUT/bench_quick.jsonl ;;
     ab)        timeout 600 python tools/pixel_map_ab.py > $OUT/pixel_map_ab.jsonl 2> $OUT/pixel_map_ab.err
                timeout 600 python tools/pixel_map_ab.py --plain >> $OUT/pixel_map_ab.jsonl 2>> $OUT/pixel_map_ab.err
@@ -113,7 +113,7 @@ for step in "$@"; do
                #   ... occ5 GFX_TRACE_LDS_STACK=6 GFX_TRACE_MIN_WAVES=5 ; ... occ6 GFX_TRACE_LDS_STACK=4 GFX_TRACE_MIN_WAVES=6 ;
                #   ... fastdiv -fno-hip-fp32-correctly-rounded-divide-sqrt   (approximate / and sqrtf: timing only, results differ))
                : > $OUT/whatif.jsonl
-               Q="python bench.py --steps 20 --warmup 5 --mse-ref-spp 0 --cpu-sample 0 --other-configs 0"
+               Q="python bench.py --steps 20 --warmup 5 --full --mse-ref-spp 0 --cpu-sample 0 --other-configs 0"
                run_v() { tag=$1; shift; echo "{\"variant\": \"$tag\"}" >> $OUT/whatif.jsonl; env "$@" timeout 300 $Q >> $OUT/whatif.jsonl 2>> $OUT/whatif.err; }
                V=$PWD/gfxexp_amd/variants
                run_v shipped GFX_NOOP=1
