@@ -206,7 +206,9 @@ def abi_mirrors():
             "gfx_restir_frame_params": GfxRestirFrameParams, "gfx_regir_params": GfxRegirParams, "gfx_nrc_params": GfxNrcParams,
             "gfxh_street_params": GfxhStreetParams, "gfxh_restir_config": GfxhRestirConfig, "gfxh_frame_step": GfxhFrameStep,
             "gfxh_exchange_buffer": GfxhExchangeBuffer, "gfxh_exchange_desc": GfxhExchangeDesc, "gfxh_band_plan": GfxhBandPlan,
-            "gfxh_nrc_config": GfxhNrcConfig, "gfxh_sdr_config": GfxhSdrConfig}
+            "gfxh_nrc_config": GfxhNrcConfig, "gfxh_sdr_config": GfxhSdrConfig,
+            "gfx_denoiser_settings": GfxDenoiserSettings, "gfx_denoiser_inputs": GfxDenoiserInputs,
+            "gfx_denoiser_history_buffers": GfxDenoiserHistoryBuffers}
 
 
 class RcclExchange:
@@ -314,6 +316,8 @@ C_ABI_SYMBOLS = [
     "gfx_accel_build",
     "gfx_accel_set_max_leaf", "gfx_accel_stats", "gfx_accel_tri_ids", "gfx_lights_build_static",
     "gfx_lights_build_instances", "gfx_lights_read", "gfx_lights_table_info", "gfx_trace", "gfx_trace_counted", "gfx_restir_set_params", "gfx_restir_copy_to_linear", "gfx_visualize", "gfx_restir_launch",
+    "gfx_restir_copy_depth_to_linear", "gfx_restir_copy_emissive_to_linear", "gfx_denoiser_default_settings", "gfx_denoiser_create", "gfx_denoiser_destroy", "gfx_denoise",
+    "gfx_denoiser_history",
     "gfx_restir_launch_rows", "gfx_restir_launch_rows_gap", "gfx_pt_launch", "gfx_regir_set_params",
     "gfx_nrc_create", "gfx_nrc_destroy", "gfx_nrc_infer", "gfx_nrc_infer_indirect", "gfx_nrc_query_count_ptr", "gfx_nrc_train", "gfx_nrc_num_params", "gfx_nrc_set_params",
     "gfx_nrc_get_params", "gfx_nrc_inference_image", "gfx_nrc_inference_image_async", "gfx_nrc_params_checksum", "gfx_nrc_set_render_params",
@@ -541,6 +545,20 @@ def band_plan(height, band_begin, band_end, radius_rows, num_spatial_passes, max
     return plan
 
 
+class GfxDenoiserSettings(C.Structure):
+    _fields_ = [("numStages", C.c_uint32), ("kernel", C.c_uint32), ("feedbackStage", C.c_uint32), ("sigmaZ", C.c_float),
+                ("sigmaN", C.c_float), ("sigmaL", C.c_float), ("minAlpha", C.c_float)]
+
+
+class GfxDenoiserInputs(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("beauty", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p),
+                ("flow", C.c_void_p), ("depth", C.c_void_p), ("emissive", C.c_void_p)]
+
+
+class GfxDenoiserHistoryBuffers(C.Structure):
+    _fields_ = [("lighting", C.c_void_p), ("moments", C.c_void_p), ("length", C.c_void_p), ("guide", C.c_void_p)]
+
+
 class GfxhSdrConfig(C.Structure):
     _fields_ = [("alphaForOverride", C.c_float), ("brightnessScale", C.c_float), ("applyToneMap", C.c_uint32),
                 ("apply_sRGB_gammaCorrection", C.c_uint32), ("flipY", C.c_uint32)]
@@ -716,6 +734,14 @@ class Context:
 
     def restir_copy_to_linear(self, d_color, d_albedo, d_normal, d_motion, stream=0):
         self._check(self.L.gfx_restir_copy_to_linear(self.h, C.c_void_p(stream), C.c_void_p(d_color), C.c_void_p(d_albedo), C.c_void_p(d_normal), C.c_void_p(d_motion)))
+
+    def restir_copy_depth_to_linear(self, d_depth, stream=0):
+        """Camera distance of GBuffer2's position per pixel (+inf without a surface) into float[W*H]: the denoiser's depth guide."""
+        self._check(self.L.gfx_restir_copy_depth_to_linear(self.h, C.c_void_p(stream), C.c_void_p(d_depth)))
+
+    def restir_copy_emissive_to_linear(self, d_emissive, stream=0):
+        """1 where the pixel's surface emits, 0 elsewhere, into uint32[W*H]: the denoiser's emissive guide."""
+        self._check(self.L.gfx_restir_copy_emissive_to_linear(self.h, C.c_void_p(stream), C.c_void_p(d_emissive)))
 
     def visualize(self, d_linear, buffer_type, width, height, d_out, mv_offset=0.5, mv_scale=0.02, stream=0):
         self._check(self.L.gfx_visualize(self.h, C.c_void_p(stream), C.c_void_p(d_linear), C.c_int(buffer_type), C.c_float(mv_offset), C.c_float(mv_scale),
@@ -927,6 +953,57 @@ class NrcRenderer:
         t = (C.c_uint32 * 2)()
         self.L.gfxh_nrc_stats(self.h, C.byref(n), t, C.byref(q))
         return dict(numTrainingData=n.value, tileSize=(t[0], t[1]), numInferenceQueries=q.value)
+
+
+DENOISE_BOX3X3, DENOISE_GAUSS3X3, DENOISE_GAUSS5X5 = 0, 1, 2
+
+
+def denoiser_default_settings():
+    st = GfxDenoiserSettings()
+    lib().gfx_denoiser_default_settings(C.byref(st))
+    return st
+
+
+class Denoiser:
+    """gfx_denoiser: the SVGF temporal denoiser (csrc/denoise/denoise.hip) with its own double-buffered history.  Buffers are device
+    pointers (ints): beauty / albedo / normal float4, flow float2, depth float (0 = no depth term), emissive uint32 (0 = none),
+    out float4, all W x H."""
+
+    def __init__(self, ctx, width, height, settings=None):
+        self.L = lib()
+        self.ctx = ctx
+        self.width, self.height = int(width), int(height)
+        h = C.c_void_p()
+        ctx._check(self.L.gfx_denoiser_create(ctx.h, C.c_uint32(width), C.c_uint32(height),
+                                              C.byref(settings) if settings is not None else None, C.byref(h)))
+        self.h = h
+
+    def inputs(self, beauty, albedo, normal, flow, depth=0, width=None, height=None, emissive=0):
+        return GfxDenoiserInputs(self.width if width is None else width, self.height if height is None else height,
+                                 beauty or None, albedo or None, normal or None, flow or None, depth or None, emissive or None)
+
+    def denoise(self, beauty, albedo, normal, flow, out, depth=0, first=False, stream=0, emissive=0):
+        inp = self.inputs(beauty, albedo, normal, flow, depth, emissive=emissive)
+        self.ctx._check(self.L.gfx_denoise(self.ctx.h, C.c_void_p(stream), self.h, C.byref(inp), C.c_int(1 if first else 0),
+                                           C.c_void_p(out or None)))
+
+    def history(self):
+        """Device pointers of the history the next denoise() reprojects: dict lighting / moments / length / guide."""
+        hb = GfxDenoiserHistoryBuffers()
+        if self.L.gfx_denoiser_history(self.h, C.byref(hb)):
+            raise GfxError("gfx_denoiser_history: no denoiser")
+        return {"lighting": hb.lighting, "moments": hb.moments, "length": hb.length, "guide": hb.guide}
+
+    def close(self):
+        if self.h:
+            self.L.gfx_denoiser_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class RestirRenderer:

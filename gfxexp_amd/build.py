@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "libgfxexp.so")
 CLI = os.path.join(HERE, "restir_di_headless")       # host/restir_di_headless.cpp: the reference's command line, windowless
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-SOURCES = ["capi.cpp", "scene.cpp", "lights.hip", "lbvh.hip", "trace.hip", "restir.hip", "pathtrace.hip", "nrc.hip", "textures.hip", "diag.hip",
+SOURCES = ["capi.cpp", "scene.cpp", "lights.hip", "lbvh.hip", "trace.hip", "restir.hip", "pathtrace.hip", "nrc.hip", "textures.hip", "diag.hip", "denoise/denoise.hip",
            "host/scene_builder.cpp", "host/restir_driver.cpp", "host/nrc_driver.cpp", "host/rccl_exchange.cpp", "host/abi_layout.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-fno-slp-vectorize", "-Wall", "-Wno-unused-function",
@@ -71,8 +71,11 @@ def build(force=False):
         subprocess.check_call(cmd)
     cli_src = os.path.join(CSRC, "host", "restir_di_headless.cpp")
     if force or not os.path.exists(CLI) or os.path.getmtime(CLI) < max(os.path.getmtime(cli_src), os.path.getmtime(LIB)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I" + os.path.join(HERE, "..", "include"), cli_src, "-o", CLI,
-                               "-L" + HERE, "-lgfxexp", "-Wl,-rpath,$ORIGIN"])
+        # the HIP runtime for the -denoise buffers and events (host API only; the CLI has no device code)
+        rocm = os.path.dirname(os.path.dirname(os.path.realpath(HIPCC)))
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(HERE, "..", "include"),
+                               "-I" + os.path.join(rocm, "include"), cli_src, "-o", CLI, "-L" + HERE, "-lgfxexp",
+                               "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN"])
     return LIB
 
 

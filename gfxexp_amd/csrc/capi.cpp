@@ -6,10 +6,12 @@
 #include <cstring>
 #include <memory>
 #include "internal.h"
+#include "denoise/denoise.h"
 
 using namespace gfx;
 
 struct gfx_ctx { Context c; };
+struct gfx_denoiser { Denoiser d; };
 
 static thread_local std::string g_createError;
 
@@ -340,6 +342,68 @@ int gfx_visualize(gfx_ctx* ctx, void* stream, const void* dLinearBuffer, int buf
     GFX_TRY(ctx)
     restir_visualize(ctx->c, static_cast<hipStream_t>(stream), dLinearBuffer, bufferTypeToDisplay, motionVectorOffset, motionVectorScale, width, height, dOutputFloat4);
     GFX_CATCH(ctx)
+}
+
+int gfx_restir_copy_depth_to_linear(gfx_ctx* ctx, void* stream, void* dLinearDepth) {
+    GFX_TRY(ctx)
+    restir_copy_depth_to_linear(ctx->c, static_cast<hipStream_t>(stream), dLinearDepth);
+    GFX_CATCH(ctx)
+}
+
+int gfx_restir_copy_emissive_to_linear(gfx_ctx* ctx, void* stream, void* dLinearEmissive) {
+    GFX_TRY(ctx)
+    restir_copy_emissive_to_linear(ctx->c, static_cast<hipStream_t>(stream), dLinearEmissive);
+    GFX_CATCH(ctx)
+}
+
+int gfx_denoiser_default_settings(gfx_denoiser_settings* out) {
+    if (!out) return 1;
+    denoiser_default_settings(out);
+    return 0;
+}
+int gfx_denoiser_create(gfx_ctx* ctx, uint32_t width, uint32_t height, const gfx_denoiser_settings* settings, gfx_denoiser** out) {
+    GFX_TRY(ctx)
+    if (!out) throw HipError("gfx_denoiser_create: null output handle");
+    *out = nullptr;
+    gfx_denoiser_settings st;
+    if (settings) st = *settings;
+    else denoiser_default_settings(&st);
+    std::unique_ptr<gfx_denoiser> d(new gfx_denoiser());
+    d->d.device = ctx->c.device;
+    try { denoiser_init(d->d, width, height, st); }
+    catch (...) { denoiser_release(d->d); throw; }
+    *out = d.release();
+    GFX_CATCH(ctx)
+}
+int gfx_denoiser_destroy(gfx_denoiser* den) {
+    if (!den) return 1;
+    int prev = -1;
+    const bool switched = hipGetDevice(&prev) == hipSuccess && prev != den->d.device && hipSetDevice(den->d.device) == hipSuccess;
+    (void)hipDeviceSynchronize();
+    denoiser_release(den->d);
+    if (switched) (void)hipSetDevice(prev);
+    delete den;
+    return 0;
+}
+int gfx_denoise(gfx_ctx* ctx, void* stream, gfx_denoiser* den, const gfx_denoiser_inputs* in, int isFirstFrame, void* dDenoisedFloat4) {
+    GFX_TRY(ctx)
+    if (!den || !in) throw HipError("gfx_denoise: null denoiser or inputs");
+    if (!in->beauty || !in->albedo || !in->normal || !in->flow || !dDenoisedFloat4)
+        throw HipError("gfx_denoise: beauty, albedo, normal, flow and the output are required");
+    if (in->width != den->d.width || in->height != den->d.height)
+        throw HipError("gfx_denoise: input size differs from gfx_denoiser_create's");
+    if (den->d.device != ctx->c.device) throw HipError("gfx_denoise: the denoiser belongs to another device");
+    denoise(den->d, static_cast<hipStream_t>(stream), *in, isFirstFrame != 0, dDenoisedFloat4);
+    GFX_CATCH(ctx)
+}
+int gfx_denoiser_history(gfx_denoiser* den, gfx_denoiser_history_buffers* out) {
+    if (!den || !out) return 1;
+    const uint32_t k = den->d.cur;
+    out->lighting = den->d.lighting[k].p;
+    out->moments = den->d.moments[k].p;
+    out->length = den->d.length[k].p;
+    out->guide = den->d.guide[k].p;
+    return 0;
 }
 
 int gfx_restir_set_params(gfx_ctx* ctx, void* /*stream*/, const gfx_restir_static_params* s, const gfx_restir_frame_params* f,

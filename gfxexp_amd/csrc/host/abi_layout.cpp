@@ -24,6 +24,12 @@ const Field kFields[] = {
     S(gfx_camera), F(gfx_camera, aspect), F(gfx_camera, fovY), F(gfx_camera, position), F(gfx_camera, orientation),
     S(gfx_hit), F(gfx_hit, dist), F(gfx_hit, bcB), F(gfx_hit, bcC), F(gfx_hit, triIndex),
     S(gfx_tri_ids), F(gfx_tri_ids, instSlot), F(gfx_tri_ids, geomInstSlot), F(gfx_tri_ids, primIndex),
+    S(gfx_denoiser_settings), F(gfx_denoiser_settings, numStages), F(gfx_denoiser_settings, kernel), F(gfx_denoiser_settings, feedbackStage),
+    F(gfx_denoiser_settings, sigmaZ), F(gfx_denoiser_settings, sigmaN), F(gfx_denoiser_settings, sigmaL), F(gfx_denoiser_settings, minAlpha),
+    S(gfx_denoiser_inputs), F(gfx_denoiser_inputs, width), F(gfx_denoiser_inputs, height), F(gfx_denoiser_inputs, beauty), F(gfx_denoiser_inputs, albedo),
+    F(gfx_denoiser_inputs, normal), F(gfx_denoiser_inputs, flow), F(gfx_denoiser_inputs, depth), F(gfx_denoiser_inputs, emissive),
+    S(gfx_denoiser_history_buffers), F(gfx_denoiser_history_buffers, lighting), F(gfx_denoiser_history_buffers, moments),
+    F(gfx_denoiser_history_buffers, length), F(gfx_denoiser_history_buffers, guide),
     S(gfx_restir_static_params), F(gfx_restir_static_params, imageSizeX), F(gfx_restir_static_params, imageSizeY), F(gfx_restir_static_params, rngBuffer),
     F(gfx_restir_static_params, gbuffer0), F(gfx_restir_static_params, gbuffer1), F(gfx_restir_static_params, gbuffer2), F(gfx_restir_static_params, gbuffer3),
     F(gfx_restir_static_params, reservoirBuffer), F(gfx_restir_static_params, reservoirInfoBuffer), F(gfx_restir_static_params, sampleVisibilityBuffer),

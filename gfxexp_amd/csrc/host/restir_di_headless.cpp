@@ -19,6 +19,9 @@
 //   -size W H (1920 1080)   -frames N (1)   -renderer restir-biased|restir-unbiased|rearch-biased|rearch-unbiased|pt|regir|nrc
 //   -animate (advance the instance controllers by 1/60 s per frame, :2249-2257)   -accumulate   -bump   -device k
 //   -out path (.exr / .pfm: HDR; .bmp / .ppm: tone-mapped SDR)   -dry-run (parse, build the scene on the host, print it, no GPU)
+//   -denoise [stages] (5; 0..5): after every frame copy-to-linear, the depth and emissive guides, gfx_denoise and gfxh_restir_outputs_consumed
+//        (the OptiX denoiser call of restir_di_main.cpp:2497-2533 and the order gfxexp_host.h asks for); -out then writes the
+//        denoised beauty (BufferToDisplay::DenoisedBeauty) and the JSON line gains "denoise_ms" (HIP events, all frames)
 // Neural radiance caching (-renderer nrc; neural_radiance_caching/neural_radiance_caching_main.cpp:755-790, defaults :458-460):
 //   -position-encoding tri-wave|hash-grid (hash-grid)   -num-hidden-layers n (2)   -learning-rate lr (1e-2)
 //   and, headless: -max-path-length n (5; 0 = unlimited, :1860-1861)   -no-train   -log10-radiance-scale s (0, :2240)
@@ -33,6 +36,7 @@
 #include <map>
 #include <string>
 #include <vector>
+#include <hip/hip_runtime_api.h>
 #include "../../../include/gfxexp.h"
 #include "../../../include/gfxexp_host.h"
 
@@ -85,6 +89,7 @@ struct Options {
     uint32_t width = 1920, height = 1080, frames = 1;
     int renderer = GFXH_ORIGINAL_RESTIR_BIASED, device = 0;
     bool animate = false, accumulate = false, bump = false, dryRun = false;
+    int denoiseStages = -1;                       // -denoise: a-trous stages; -1 = no denoiser
     std::string out;
     // neural radiance caching (neural_radiance_caching_main.cpp:458-460)
     bool nrc = false, nrcTrain = true;
@@ -240,8 +245,24 @@ Options parse(int argc, const char* argv[]) {
         else if (a == "-accumulate") o.accumulate = true;
         else if (a == "-bump") o.bump = true;
         else if (a == "-dry-run") o.dryRun = true;
+        else if (a == "-denoise") {
+            o.denoiseStages = 5;
+            // an optional stage count: the next argument when it is an integer
+            if (i + 1 < argc) {
+                const std::string v = argv[i + 1];
+                size_t k = (!v.empty() && v[0] == '-') ? 1 : 0;
+                bool integer = k < v.size();
+                for (; k < v.size(); ++k) integer = integer && v[k] >= '0' && v[k] <= '9';
+                if (integer) {
+                    if (v[0] == '-' || v.size() > 1 || v[0] > '5') fail("-denoise takes 0..5 a-trous stages:", argv[i + 1]);
+                    o.denoiseStages = v[0] - '0';
+                    i += 1;
+                }
+            }
+        }
         else fail("unknown option:", argv[i]);                                        // :860-863
     }
+    if (o.denoiseStages >= 0 && o.nrc) fail("-denoise needs a renderer with the ReSTIR output chain (not -renderer nrc)", nullptr);
     if (o.width == 0 || o.height == 0 || o.frames == 0) fail("-size / -frames must be positive", nullptr);
     return o;
 }
@@ -317,6 +338,7 @@ int main(int argc, const char* argv[]) {
     if (o.nrc) std::printf(",\n \"nrc\": {\"position_encoding\": \"%s\", \"num_hidden_layers\": %u, \"learning_rate\": %.9g, \"max_path_length\": %u, \"train\": %s, \"nee\": \"%s\"}",
                            o.positionEncoding == GFX_NRC_HASH_GRID ? "hash-grid" : "tri-wave", o.numHiddenLayers, o.learningRate, o.maxPathLength, o.nrcTrain ? "true" : "false",
                            o.neeSampler == 1 ? "regir" : o.neeSampler == 2 ? "restir" : "lights");
+    if (o.denoiseStages >= 0) std::printf(",\n \"denoise_stages\": %d", o.denoiseStages);
     std::printf(",\n \"instance_transforms\": [");
     for (uint32_t i = 0; i < counts[3]; ++i) {
         uint32_t group; float xfm[12];
@@ -396,14 +418,57 @@ int main(int argc, const char* argv[]) {
         load_env_texture(o.envTexture, env, w, h);
         if (gfxh_restir_set_env(renderer, env.data(), w, h, 1.0f, 0.0f)) fail("gfxh_restir_set_env:", gfxh_restir_last_error());
     }
+    // -denoise: the linear buffers of the output chain, the depth and emissive guides and the denoiser (restir_di_main.cpp:1400-1432)
+    gfx_denoiser* den = nullptr;
+    void* lin[7] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };   // beauty, albedo, normal, flow, depth, emissive, denoised
+    // one event pair per frame, read after the loop: timing the denoiser does not hold the pipelined frame loop at a host wait
+    std::vector<hipEvent_t> ev;
+    if (o.denoiseStages >= 0) {
+        const size_t n = static_cast<size_t>(o.width) * o.height;
+        const size_t bytes[7] = { 16 * n, 16 * n, 16 * n, 8 * n, 4 * n, 4 * n, 16 * n };
+        for (int k = 0; k < 7; ++k) if (hipMalloc(&lin[k], bytes[k]) != hipSuccess) fail("hipMalloc failed", nullptr);
+        ev.resize(2 * static_cast<size_t>(o.frames));
+        for (hipEvent_t& e : ev) if (hipEventCreate(&e) != hipSuccess) fail("hipEventCreate failed", nullptr);
+        gfx_denoiser_settings st;
+        gfx_denoiser_default_settings(&st);
+        st.numStages = static_cast<uint32_t>(o.denoiseStages);
+        if (gfx_denoiser_create(ctx, o.width, o.height, &st, &den)) fail("gfx_denoiser_create:", gfx_last_error(ctx));
+    }
     for (uint32_t frame = 0; frame < o.frames; ++frame) {
         if (o.animate && frame > 0 && !controllers.empty()) {
             animate_instances();
             if (gfxh_restir_rebuild_accel(renderer, nullptr)) fail("gfxh_restir_rebuild_accel:", gfxh_restir_last_error());
         }
         if (gfxh_restir_render_frame(renderer, nullptr)) fail("gfxh_restir_render_frame:", gfxh_restir_last_error());
+        if (den) {
+            // :2497-2533: copyToLinearBuffers, then the denoiser; the renderer's next G-buffer pass waits for outputs_consumed
+            gfx_restir_static_params sp; gfx_restir_frame_params fp; uint32_t res = 0, base = 0;
+            if (gfxh_restir_get_params(renderer, &sp, &fp, &res, &base, nullptr)) fail("gfxh_restir_get_params failed", nullptr);
+            if (gfx_restir_set_params(ctx, nullptr, &sp, &fp, res, base)) fail("gfx_restir_set_params:", gfx_last_error(ctx));
+            if (gfx_restir_copy_to_linear(ctx, nullptr, lin[0], lin[1], lin[2], lin[3])) fail("gfx_restir_copy_to_linear:", gfx_last_error(ctx));
+            if (gfx_restir_copy_depth_to_linear(ctx, nullptr, lin[4])) fail("gfx_restir_copy_depth_to_linear:", gfx_last_error(ctx));
+            if (gfx_restir_copy_emissive_to_linear(ctx, nullptr, lin[5])) fail("gfx_restir_copy_emissive_to_linear:", gfx_last_error(ctx));
+            const gfx_denoiser_inputs in = { o.width, o.height, lin[0], lin[1], lin[2], lin[3], lin[4], lin[5] };
+            if (hipEventRecord(ev[2 * frame], nullptr) != hipSuccess) fail("hipEventRecord failed", nullptr);
+            if (gfx_denoise(ctx, nullptr, den, &in, frame == 0 ? 1 : 0, lin[6])) fail("gfx_denoise:", gfx_last_error(ctx));
+            if (hipEventRecord(ev[2 * frame + 1], nullptr) != hipSuccess) fail("hipEventRecord failed", nullptr);
+            if (gfxh_restir_outputs_consumed(renderer, nullptr)) fail("gfxh_restir_outputs_consumed:", gfxh_restir_last_error());
+        }
     }
-    if (gfx_read_device(ctx, gfxh_restir_beauty_buffer(renderer), rgba.data(), rgba.size() * sizeof(float))) fail("gfx_read_device:", gfx_last_error(ctx));
+    if (gfx_read_device(ctx, den ? lin[6] : gfxh_restir_beauty_buffer(renderer), rgba.data(), rgba.size() * sizeof(float))) fail("gfx_read_device:", gfx_last_error(ctx));
+    if (den) {
+        double denoiseMs = 0.0;
+        for (uint32_t frame = 0; frame < o.frames; ++frame) {
+            float ms = 0.0f;
+            if (hipEventSynchronize(ev[2 * frame + 1]) != hipSuccess || hipEventElapsedTime(&ms, ev[2 * frame], ev[2 * frame + 1]) != hipSuccess)
+                fail("hipEventElapsedTime failed", nullptr);
+            denoiseMs += ms;
+        }
+        std::printf(",\n \"denoise_ms\": %.6g", denoiseMs / o.frames);
+        gfx_denoiser_destroy(den);
+        for (void* p : lin) (void)hipFree(p);
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
     }
     double sum[3] = { 0, 0, 0 };
     for (size_t p = 0; p < static_cast<size_t>(o.width) * o.height; ++p) for (int k = 0; k < 3; ++k) sum[k] += rgba[4 * p + k];

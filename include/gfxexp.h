@@ -364,6 +364,72 @@ enum gfx_buffer_to_display {                       /* BufferToDisplay, restir_di
 int gfx_restir_copy_to_linear(gfx_ctx* ctx, void* stream, void* dLinearColor, void* dLinearAlbedo, void* dLinearNormal, void* dLinearMotionVector);
 int gfx_visualize(gfx_ctx* ctx, void* stream, const void* dLinearBuffer, int bufferTypeToDisplay, float motionVectorOffset, float motionVectorScale,
                   uint32_t width, uint32_t height, void* dOutputFloat4);
+/* Camera distance |GBuffer2.positionInWorld - camera.position| of the current gfx_restir_set_params for pixels with a surface
+ * (GBuffer0.instSlot != ~0u), +inf otherwise, into a caller-owned float[W*H]: the depth guide of gfx_denoise (the reference's
+ * denoiser takes none; svgf/ reads the GL raster depth buffer, svgf_main.cpp). */
+int gfx_restir_copy_depth_to_linear(gfx_ctx* ctx, void* stream, void* dLinearDepth);
+/* 1 for pixels whose surface emits (GBuffer0.instSlot != ~0u and the material of GBuffer3.matSlot has emittance), 0 otherwise, into a
+ * caller-owned uint32[W*H]: the emissive guide of gfx_denoise.  The beauty of such a pixel is emission plus reflected light, and
+ * dividing it by the albedo (the reference's demodulation, svgf/gpu_kernels/optix_pathtracing_kernels.cu:354) yields values that
+ * the a-trous stages would spread to the pixel's neighbours; the denoiser passes these pixels through instead. */
+int gfx_restir_copy_emissive_to_linear(gfx_ctx* ctx, void* stream, void* dLinearEmissive);
+
+/* ---------------------------------------------------------------- SVGF temporal denoiser ------ */
+
+/* Stands in for the OptiX temporal denoiser of restir_di_main.cpp (setup :1400-1432, invoke :2504-2533): the open SVGF of
+ * svgf/gpu_kernels (temporal reprojection with moments optix_pathtracing_kernels.cu:55-130 and :354-364, variance estimate
+ * svgf.cu:30-130, edge-stopped a-trous stages :132-350, albedo re-modulation :378-611) restated over the linear buffers
+ * gfx_restir_copy_to_linear writes plus an optional depth guide.  The order of operations is specified in
+ * gfxexp_amd/csrc/denoise/denoise.hip; the CPU restatement of tests/denoise_ref.cpp follows the same text bit for bit. */
+typedef struct gfx_denoiser gfx_denoiser;   /* opaque; owns its double-buffered history and scratch buffers */
+enum gfx_denoise_kernel {                   /* ATrousKernelType, svgf.cu:138-218 */
+    GFX_DENOISE_BOX3X3 = 0,                 /* the kernel svgf.cu launches (applyATrousFilter_box3x3) */
+    GFX_DENOISE_GAUSS3X3 = 1,
+    GFX_DENOISE_GAUSS5X5 = 2
+};
+typedef struct gfx_denoiser_settings {
+    uint32_t numStages;      /* a-trous stages 0..5 with steps 1 2 4 8 16 (0 = temporal accumulation + re-modulation only); default 5 */
+    uint32_t kernel;         /* gfx_denoise_kernel; default GFX_DENOISE_BOX3X3 */
+    uint32_t feedbackStage;  /* 1 = the history takes stage 0's output (feedback1stFilteredResult, SVGF's default), 0 = the unfiltered
+                                integrated lighting */
+    float sigmaZ;            /* 1 (svgf.cu:8) */
+    float sigmaN;            /* 128 (svgf.cu:15); a power of two 1..1024: pow(x, 2^k) is k squarings */
+    float sigmaL;            /* 4 (svgf.cu:22) */
+    float minAlpha;          /* 0.2: the 1/5 EMA floor of svgf/gpu_kernels/optix_pathtracing_kernels.cu:358-361; 0..1 */
+} gfx_denoiser_settings;
+typedef struct gfx_denoiser_inputs {
+    uint32_t width, height;  /* of every buffer below; must equal gfx_denoiser_create's */
+    const void* beauty;      /* float4[W*H], the layout gfx_restir_copy_to_linear writes; alpha is copied to the output */
+    const void* albedo;      /* float4 */
+    const void* normal;      /* float4, unit or zero (zero = no surface) */
+    const void* flow;        /* float2: the motion vector as the G-buffer pass writes it, pixel centre minus previous position, in pixels */
+    const void* depth;       /* optional float[W*H]: camera distance, +inf = background (gfx_restir_copy_depth_to_linear); NULL = no depth term */
+    const void* emissive;    /* optional uint32[W*H]: nonzero = an emitting surface (gfx_restir_copy_emissive_to_linear), passed through
+                                like background and never a neighbour; NULL = none */
+} gfx_denoiser_inputs;
+/* The history the next gfx_denoise reprojects (device pointers into the denoiser, read-only; for tests and debugging), W*H each:
+ *   lighting  float4  (demodulated lighting r, g, b, 0): stage 0's output with feedbackStage, the integrated lighting otherwise
+ *   moments   float2  (luminance, luminance^2) after the temporal blend
+ *   length    uint32  history length 1..255, 0 = background / no history
+ *   guide     float4  (normal x, y, z, depth): depth is +inf for background and emissive pixels, 0 for a surface when no depth was given */
+typedef struct gfx_denoiser_history_buffers {
+    const void* lighting;
+    const void* moments;
+    const void* length;
+    const void* guide;
+} gfx_denoiser_history_buffers;
+/* defaults of the reference (svgf.cu:5-27, svgf_main.cpp's UI defaults: 5 stages, Box3x3, feedback of the first stage) */
+int gfx_denoiser_default_settings(gfx_denoiser_settings* out);
+/* optixu::Denoiser prepare / setupState / computeNormalizer (restir_di_main.cpp:1400-1432): allocates everything; settings NULL =
+ * defaults.  Invalid settings or a zero size return 1 (gfx_last_error(ctx)). */
+int gfx_denoiser_create(gfx_ctx* ctx, uint32_t width, uint32_t height, const gfx_denoiser_settings* settings, gfx_denoiser** out);
+int gfx_denoiser_destroy(gfx_denoiser* den);
+/* optixu::Denoiser::invoke (restir_di_main.cpp:2504-2533, previousDenoisedBeauty -> the denoiser's own history): enqueues at most
+ * numStages + 2 kernels on `stream`; no allocation, no synchronisation, no host work between the kernels.  isFirstFrame discards the
+ * history (every history length restarts at 1).  dDenoisedFloat4 = float4[W*H].  A null required input or output, or a size other
+ * than create's, returns 1 and launches nothing. */
+int gfx_denoise(gfx_ctx* ctx, void* stream, gfx_denoiser* den, const gfx_denoiser_inputs* in, int isFirstFrame, void* dDenoisedFloat4);
+int gfx_denoiser_history(gfx_denoiser* den, gfx_denoiser_history_buffers* out);
 
 /* ---------------------------------------------------------------- path tracing ---------------- */
 
