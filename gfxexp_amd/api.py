@@ -208,7 +208,7 @@ def abi_mirrors():
             "gfxh_exchange_buffer": GfxhExchangeBuffer, "gfxh_exchange_desc": GfxhExchangeDesc, "gfxh_band_plan": GfxhBandPlan,
             "gfxh_nrc_config": GfxhNrcConfig, "gfxh_sdr_config": GfxhSdrConfig,
             "gfx_denoiser_settings": GfxDenoiserSettings, "gfx_denoiser_inputs": GfxDenoiserInputs,
-            "gfx_denoiser_history_buffers": GfxDenoiserHistoryBuffers}
+            "gfx_denoiser_history_buffers": GfxDenoiserHistoryBuffers, "gfx_taa_inputs": GfxTaaInputs}
 
 
 class RcclExchange:
@@ -317,7 +317,7 @@ C_ABI_SYMBOLS = [
     "gfx_accel_set_max_leaf", "gfx_accel_stats", "gfx_accel_tri_ids", "gfx_lights_build_static",
     "gfx_lights_build_instances", "gfx_lights_read", "gfx_lights_table_info", "gfx_trace", "gfx_trace_counted", "gfx_restir_set_params", "gfx_restir_copy_to_linear", "gfx_visualize", "gfx_restir_launch",
     "gfx_restir_copy_depth_to_linear", "gfx_restir_copy_emissive_to_linear", "gfx_denoiser_default_settings", "gfx_denoiser_create", "gfx_denoiser_destroy", "gfx_denoise",
-    "gfx_denoiser_history",
+    "gfx_denoiser_history", "gfx_restir_copy_taa_flow_to_linear", "gfx_taa_create", "gfx_taa_destroy", "gfx_taa_set_history_length", "gfx_taa_apply", "gfx_taa_history",
     "gfx_restir_launch_rows", "gfx_restir_launch_rows_gap", "gfx_pt_launch", "gfx_regir_set_params",
     "gfx_nrc_create", "gfx_nrc_destroy", "gfx_nrc_infer", "gfx_nrc_infer_indirect", "gfx_nrc_query_count_ptr", "gfx_nrc_train", "gfx_nrc_num_params", "gfx_nrc_set_params",
     "gfx_nrc_get_params", "gfx_nrc_inference_image", "gfx_nrc_inference_image_async", "gfx_nrc_params_checksum", "gfx_nrc_set_render_params",
@@ -559,6 +559,10 @@ class GfxDenoiserHistoryBuffers(C.Structure):
     _fields_ = [("lighting", C.c_void_p), ("moments", C.c_void_p), ("length", C.c_void_p), ("guide", C.c_void_p)]
 
 
+class GfxTaaInputs(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("color", C.c_void_p), ("flow", C.c_void_p)]
+
+
 class GfxhSdrConfig(C.Structure):
     _fields_ = [("alphaForOverride", C.c_float), ("brightnessScale", C.c_float), ("applyToneMap", C.c_uint32),
                 ("apply_sRGB_gammaCorrection", C.c_uint32), ("flipY", C.c_uint32)]
@@ -742,6 +746,11 @@ class Context:
     def restir_copy_emissive_to_linear(self, d_emissive, stream=0):
         """1 where the pixel's surface emits, 0 elsewhere, into uint32[W*H]: the denoiser's emissive guide."""
         self._check(self.L.gfx_restir_copy_emissive_to_linear(self.h, C.c_void_p(stream), C.c_void_p(d_emissive)))
+
+    def restir_copy_taa_flow_to_linear(self, d_flow, stream=0):
+        """Current minus previous raster position of each pixel's point (the motion vector without the jitter offset) into
+        float2[W*H]: the flow TemporalAA.apply wants."""
+        self._check(self.L.gfx_restir_copy_taa_flow_to_linear(self.h, C.c_void_p(stream), C.c_void_p(d_flow)))
 
     def visualize(self, d_linear, buffer_type, width, height, d_out, mv_offset=0.5, mv_scale=0.02, stream=0):
         self._check(self.L.gfx_visualize(self.h, C.c_void_p(stream), C.c_void_p(d_linear), C.c_int(buffer_type), C.c_float(mv_offset), C.c_float(mv_scale),
@@ -997,6 +1006,49 @@ class Denoiser:
     def close(self):
         if self.h:
             self.L.gfx_denoiser_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TemporalAA:
+    """gfx_taa: temporal anti-aliasing (csrc/denoise/taa.hip) with its own double-buffered history.  Buffers are device pointers
+    (ints): color and out float4, flow float2, all W x H.  history_length 1..256 (the reference's default: 16)."""
+
+    def __init__(self, ctx, width, height, history_length=16):
+        self.L = lib()
+        self.ctx = ctx
+        self.width, self.height = int(width), int(height)
+        h = C.c_void_p()
+        ctx._check(self.L.gfx_taa_create(ctx.h, C.c_uint32(width), C.c_uint32(height), C.c_uint32(history_length), C.byref(h)))
+        self.h = h
+
+    def inputs(self, color, flow, width=None, height=None):
+        return GfxTaaInputs(self.width if width is None else width, self.height if height is None else height, color or None, flow or None)
+
+    def apply(self, color, flow, out, first=False, stream=0):
+        inp = self.inputs(color, flow)
+        self.ctx._check(self.L.gfx_taa_apply(self.ctx.h, C.c_void_p(stream), self.h, C.byref(inp), C.c_int(1 if first else 0),
+                                             C.c_void_p(out or None)))
+
+    def set_history_length(self, n):
+        if self.L.gfx_taa_set_history_length(self.h, C.c_uint32(n)):
+            raise GfxError("gfx_taa_set_history_length: historyLength must be 1..256")
+
+    def history(self):
+        """Device pointer of the float4 history the next apply() reprojects (the last output)."""
+        p = C.c_void_p()
+        if self.L.gfx_taa_history(self.h, C.byref(p)):
+            raise GfxError("gfx_taa_history: no TAA object")
+        return p.value
+
+    def close(self):
+        if self.h:
+            self.L.gfx_taa_destroy(self.h)
             self.h = None
 
     def __del__(self):

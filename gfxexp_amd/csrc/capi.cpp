@@ -7,11 +7,13 @@
 #include <memory>
 #include "internal.h"
 #include "denoise/denoise.h"
+#include "denoise/taa.h"
 
 using namespace gfx;
 
 struct gfx_ctx { Context c; };
 struct gfx_denoiser { Denoiser d; };
+struct gfx_taa { TemporalAA t; };
 
 static thread_local std::string g_createError;
 
@@ -403,6 +405,56 @@ int gfx_denoiser_history(gfx_denoiser* den, gfx_denoiser_history_buffers* out) {
     out->moments = den->d.moments[k].p;
     out->length = den->d.length[k].p;
     out->guide = den->d.guide[k].p;
+    return 0;
+}
+
+int gfx_restir_copy_taa_flow_to_linear(gfx_ctx* ctx, void* stream, void* dLinearFlow) {
+    GFX_TRY(ctx)
+    restir_copy_taa_flow_to_linear(ctx->c, static_cast<hipStream_t>(stream), dLinearFlow);
+    GFX_CATCH(ctx)
+}
+
+int gfx_taa_create(gfx_ctx* ctx, uint32_t width, uint32_t height, uint32_t historyLength, gfx_taa** out) {
+    GFX_TRY(ctx)
+    if (!out) throw HipError("gfx_taa_create: null output handle");
+    *out = nullptr;
+    std::unique_ptr<gfx_taa> t(new gfx_taa());
+    t->t.device = ctx->c.device;
+    try { taa_init(t->t, width, height, historyLength); }
+    catch (...) { taa_release(t->t); throw; }
+    *out = t.release();
+    GFX_CATCH(ctx)
+}
+int gfx_taa_destroy(gfx_taa* taa) {
+    if (!taa) return 1;
+    int prev = -1;
+    const bool switched = hipGetDevice(&prev) == hipSuccess && prev != taa->t.device && hipSetDevice(taa->t.device) == hipSuccess;
+    (void)hipDeviceSynchronize();
+    taa_release(taa->t);
+    if (switched) (void)hipSetDevice(prev);
+    delete taa;
+    return 0;
+}
+int gfx_taa_set_history_length(gfx_taa* taa, uint32_t historyLength) {
+    if (!taa || historyLength < 1 || historyLength > kTaaMaxHistoryLength) return 1;
+    taa->t.historyLength = historyLength;
+    return 0;
+}
+int gfx_taa_apply(gfx_ctx* ctx, void* stream, gfx_taa* taa, const gfx_taa_inputs* in, int isFirstFrame, void* dOutFloat4) {
+    GFX_TRY(ctx)
+    if (!taa || !in) throw HipError("gfx_taa_apply: null TAA object or inputs");
+    if (!in->color || !in->flow || !dOutFloat4) throw HipError("gfx_taa_apply: color, flow and the output are required");
+    if (in->width != taa->t.width || in->height != taa->t.height) throw HipError("gfx_taa_apply: input size differs from gfx_taa_create's");
+    if (dOutFloat4 == in->color) throw HipError("gfx_taa_apply: the output must not be the color input (the pass reads neighbours)");
+    if (dOutFloat4 == taa->t.history[0].p || dOutFloat4 == taa->t.history[1].p)
+        throw HipError("gfx_taa_apply: the output must not be the object's own history");
+    if (taa->t.device != ctx->c.device) throw HipError("gfx_taa_apply: the TAA object belongs to another device");
+    taa_apply(taa->t, static_cast<hipStream_t>(stream), in->color, in->flow, isFirstFrame != 0, dOutFloat4);
+    GFX_CATCH(ctx)
+}
+int gfx_taa_history(gfx_taa* taa, const void** dHistory) {
+    if (!taa || !dHistory) return 1;
+    *dHistory = taa->t.history[taa->t.cur].p;
     return 0;
 }
 

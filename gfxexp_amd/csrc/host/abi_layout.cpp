@@ -30,6 +30,7 @@ const Field kFields[] = {
     F(gfx_denoiser_inputs, normal), F(gfx_denoiser_inputs, flow), F(gfx_denoiser_inputs, depth), F(gfx_denoiser_inputs, emissive),
     S(gfx_denoiser_history_buffers), F(gfx_denoiser_history_buffers, lighting), F(gfx_denoiser_history_buffers, moments),
     F(gfx_denoiser_history_buffers, length), F(gfx_denoiser_history_buffers, guide),
+    S(gfx_taa_inputs), F(gfx_taa_inputs, width), F(gfx_taa_inputs, height), F(gfx_taa_inputs, color), F(gfx_taa_inputs, flow),
     S(gfx_restir_static_params), F(gfx_restir_static_params, imageSizeX), F(gfx_restir_static_params, imageSizeY), F(gfx_restir_static_params, rngBuffer),
     F(gfx_restir_static_params, gbuffer0), F(gfx_restir_static_params, gbuffer1), F(gfx_restir_static_params, gbuffer2), F(gfx_restir_static_params, gbuffer3),
     F(gfx_restir_static_params, reservoirBuffer), F(gfx_restir_static_params, reservoirInfoBuffer), F(gfx_restir_static_params, sampleVisibilityBuffer),

@@ -22,6 +22,10 @@
 //   -denoise [stages] (5; 0..5): after every frame copy-to-linear, the depth and emissive guides, gfx_denoise and gfxh_restir_outputs_consumed
 //        (the OptiX denoiser call of restir_di_main.cpp:2497-2533 and the order gfxexp_host.h asks for); -out then writes the
 //        denoised beauty (BufferToDisplay::DenoisedBeauty) and the JSON line gains "denoise_ms" (HIP events, all frames)
+//   -jitter (enableJittering = 1: a per-pixel sub-pixel offset of the primary ray from the pixel RNG)
+//   -taa [N] (16; 1..256): after every frame temporal anti-aliasing with history length N (gfx_restir_copy_taa_flow_to_linear and
+//        gfx_taa_apply; svgf/'s TAA, svgf_main.cpp:2170) on the denoised beauty with -denoise, on the linear beauty otherwise; -out then writes the TAA image
+//        and the JSON line gains "taa_ms" (HIP events, all frames)
 // Neural radiance caching (-renderer nrc; neural_radiance_caching/neural_radiance_caching_main.cpp:755-790, defaults :458-460):
 //   -position-encoding tri-wave|hash-grid (hash-grid)   -num-hidden-layers n (2)   -learning-rate lr (1e-2)
 //   and, headless: -max-path-length n (5; 0 = unlimited, :1860-1861)   -no-train   -log10-radiance-scale s (0, :2240)
@@ -90,6 +94,8 @@ struct Options {
     int renderer = GFXH_ORIGINAL_RESTIR_BIASED, device = 0;
     bool animate = false, accumulate = false, bump = false, dryRun = false;
     int denoiseStages = -1;                       // -denoise: a-trous stages; -1 = no denoiser
+    int taaHistory = 0;                           // -taa: history length; 0 = no TAA
+    bool jitter = false;
     std::string out;
     // neural radiance caching (neural_radiance_caching_main.cpp:458-460)
     bool nrc = false, nrcTrain = true;
@@ -260,9 +266,28 @@ Options parse(int argc, const char* argv[]) {
                 }
             }
         }
+        else if (a == "-jitter") o.jitter = true;
+        else if (a == "-taa") {
+            o.taaHistory = 16;                                                        // svgf_main.cpp:1736
+            // an optional history length: the next argument when it is an integer
+            if (i + 1 < argc) {
+                const std::string v = argv[i + 1];
+                size_t k = (!v.empty() && v[0] == '-') ? 1 : 0;
+                bool integer = k < v.size();
+                for (; k < v.size(); ++k) integer = integer && v[k] >= '0' && v[k] <= '9';
+                if (integer) {
+                    const long n = (v[0] == '-' || v.size() > 3) ? -1 : std::atol(v.c_str());
+                    if (n < 1 || n > 256) fail("-taa takes a history length 1..256:", argv[i + 1]);
+                    o.taaHistory = static_cast<int>(n);
+                    i += 1;
+                }
+            }
+        }
         else fail("unknown option:", argv[i]);                                        // :860-863
     }
     if (o.denoiseStages >= 0 && o.nrc) fail("-denoise needs a renderer with the ReSTIR output chain (not -renderer nrc)", nullptr);
+    if (o.taaHistory > 0 && o.nrc) fail("-taa needs a renderer with the ReSTIR output chain (not -renderer nrc)", nullptr);
+    if (o.jitter && o.nrc) fail("-jitter needs a renderer with the ReSTIR output chain (not -renderer nrc)", nullptr);
     if (o.width == 0 || o.height == 0 || o.frames == 0) fail("-size / -frames must be positive", nullptr);
     return o;
 }
@@ -339,6 +364,8 @@ int main(int argc, const char* argv[]) {
                            o.positionEncoding == GFX_NRC_HASH_GRID ? "hash-grid" : "tri-wave", o.numHiddenLayers, o.learningRate, o.maxPathLength, o.nrcTrain ? "true" : "false",
                            o.neeSampler == 1 ? "regir" : o.neeSampler == 2 ? "restir" : "lights");
     if (o.denoiseStages >= 0) std::printf(",\n \"denoise_stages\": %d", o.denoiseStages);
+    if (o.taaHistory > 0) std::printf(",\n \"taa_history_length\": %d", o.taaHistory);
+    if (o.jitter) std::printf(",\n \"jitter\": true");
     std::printf(",\n \"instance_transforms\": [");
     for (uint32_t i = 0; i < counts[3]; ++i) {
         uint32_t group; float xfm[12];
@@ -411,6 +438,7 @@ int main(int argc, const char* argv[]) {
     for (int k = 0; k < 9; ++k) cfg.camera.orientation[k] = static_cast<float>(camM[k]);
     cfg.enableAccumulation = o.accumulate ? 1u : 0u;
     cfg.enableBumpMapping = o.bump ? 1u : 0u;
+    cfg.enableJittering = o.jitter ? 1u : 0u;
     for (int k = 0; k < 3; ++k) { cfg.regirAabbMin[k] = bounds[k]; cfg.regirAabbMax[k] = bounds[3 + k]; }
     if (gfxh_restir_create(ctx, &cfg, &renderer)) fail("gfxh_restir_create:", gfxh_restir_last_error());
     if (!o.envTexture.empty()) {
@@ -418,15 +446,23 @@ int main(int argc, const char* argv[]) {
         load_env_texture(o.envTexture, env, w, h);
         if (gfxh_restir_set_env(renderer, env.data(), w, h, 1.0f, 0.0f)) fail("gfxh_restir_set_env:", gfxh_restir_last_error());
     }
-    // -denoise: the linear buffers of the output chain, the depth and emissive guides and the denoiser (restir_di_main.cpp:1400-1432)
+    // -denoise / -taa: the linear buffers of the output chain, the depth and emissive guides and the denoiser (restir_di_main.cpp:1400-1432),
+    // the TAA object (svgf_main.cpp:1798-1803)
     gfx_denoiser* den = nullptr;
-    void* lin[7] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };   // beauty, albedo, normal, flow, depth, emissive, denoised
-    // one event pair per frame, read after the loop: timing the denoiser does not hold the pipelined frame loop at a host wait
-    std::vector<hipEvent_t> ev;
-    if (o.denoiseStages >= 0) {
+    gfx_taa* taa = nullptr;
+    const bool chain = o.denoiseStages >= 0 || o.taaHistory > 0;
+    // beauty, albedo, normal, flow, depth, emissive, denoised (-denoise), anti-aliased and its flow (-taa)
+    void* lin[9] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    // one event pair per frame and pass, read after the loop: timing the passes does not hold the pipelined frame loop at a host wait
+    std::vector<hipEvent_t> ev, evTaa;
+    if (chain) {
         const size_t n = static_cast<size_t>(o.width) * o.height;
-        const size_t bytes[7] = { 16 * n, 16 * n, 16 * n, 8 * n, 4 * n, 4 * n, 16 * n };
-        for (int k = 0; k < 7; ++k) if (hipMalloc(&lin[k], bytes[k]) != hipSuccess) fail("hipMalloc failed", nullptr);
+        const size_t bytes[9] = { 16 * n, 16 * n, 16 * n, 8 * n, 4 * n, 4 * n, 16 * n, 16 * n, 8 * n };
+        const bool dn = o.denoiseStages >= 0, aa = o.taaHistory > 0;
+        const bool need[9] = { true, true, true, true, dn, dn, dn, aa, aa };
+        for (int k = 0; k < 9; ++k) if (need[k] && hipMalloc(&lin[k], bytes[k]) != hipSuccess) fail("hipMalloc failed", nullptr);
+    }
+    if (o.denoiseStages >= 0) {
         ev.resize(2 * static_cast<size_t>(o.frames));
         for (hipEvent_t& e : ev) if (hipEventCreate(&e) != hipSuccess) fail("hipEventCreate failed", nullptr);
         gfx_denoiser_settings st;
@@ -434,41 +470,67 @@ int main(int argc, const char* argv[]) {
         st.numStages = static_cast<uint32_t>(o.denoiseStages);
         if (gfx_denoiser_create(ctx, o.width, o.height, &st, &den)) fail("gfx_denoiser_create:", gfx_last_error(ctx));
     }
+    if (o.taaHistory > 0) {
+        evTaa.resize(2 * static_cast<size_t>(o.frames));
+        for (hipEvent_t& e : evTaa) if (hipEventCreate(&e) != hipSuccess) fail("hipEventCreate failed", nullptr);
+        if (gfx_taa_create(ctx, o.width, o.height, static_cast<uint32_t>(o.taaHistory), &taa)) fail("gfx_taa_create:", gfx_last_error(ctx));
+    }
     for (uint32_t frame = 0; frame < o.frames; ++frame) {
         if (o.animate && frame > 0 && !controllers.empty()) {
             animate_instances();
             if (gfxh_restir_rebuild_accel(renderer, nullptr)) fail("gfxh_restir_rebuild_accel:", gfxh_restir_last_error());
         }
         if (gfxh_restir_render_frame(renderer, nullptr)) fail("gfxh_restir_render_frame:", gfxh_restir_last_error());
-        if (den) {
-            // :2497-2533: copyToLinearBuffers, then the denoiser; the renderer's next G-buffer pass waits for outputs_consumed
+        if (chain) {
+            // :2497-2533: copyToLinearBuffers, then the denoiser and TAA; the renderer's next G-buffer pass waits for outputs_consumed
             gfx_restir_static_params sp; gfx_restir_frame_params fp; uint32_t res = 0, base = 0;
             if (gfxh_restir_get_params(renderer, &sp, &fp, &res, &base, nullptr)) fail("gfxh_restir_get_params failed", nullptr);
             if (gfx_restir_set_params(ctx, nullptr, &sp, &fp, res, base)) fail("gfx_restir_set_params:", gfx_last_error(ctx));
             if (gfx_restir_copy_to_linear(ctx, nullptr, lin[0], lin[1], lin[2], lin[3])) fail("gfx_restir_copy_to_linear:", gfx_last_error(ctx));
-            if (gfx_restir_copy_depth_to_linear(ctx, nullptr, lin[4])) fail("gfx_restir_copy_depth_to_linear:", gfx_last_error(ctx));
-            if (gfx_restir_copy_emissive_to_linear(ctx, nullptr, lin[5])) fail("gfx_restir_copy_emissive_to_linear:", gfx_last_error(ctx));
-            const gfx_denoiser_inputs in = { o.width, o.height, lin[0], lin[1], lin[2], lin[3], lin[4], lin[5] };
-            if (hipEventRecord(ev[2 * frame], nullptr) != hipSuccess) fail("hipEventRecord failed", nullptr);
-            if (gfx_denoise(ctx, nullptr, den, &in, frame == 0 ? 1 : 0, lin[6])) fail("gfx_denoise:", gfx_last_error(ctx));
-            if (hipEventRecord(ev[2 * frame + 1], nullptr) != hipSuccess) fail("hipEventRecord failed", nullptr);
+            if (den) {
+                if (gfx_restir_copy_depth_to_linear(ctx, nullptr, lin[4])) fail("gfx_restir_copy_depth_to_linear:", gfx_last_error(ctx));
+                if (gfx_restir_copy_emissive_to_linear(ctx, nullptr, lin[5])) fail("gfx_restir_copy_emissive_to_linear:", gfx_last_error(ctx));
+                const gfx_denoiser_inputs in = { o.width, o.height, lin[0], lin[1], lin[2], lin[3], lin[4], lin[5] };
+                if (hipEventRecord(ev[2 * frame], nullptr) != hipSuccess) fail("hipEventRecord failed", nullptr);
+                if (gfx_denoise(ctx, nullptr, den, &in, frame == 0 ? 1 : 0, lin[6])) fail("gfx_denoise:", gfx_last_error(ctx));
+                if (hipEventRecord(ev[2 * frame + 1], nullptr) != hipSuccess) fail("hipEventRecord failed", nullptr);
+            }
+            if (taa) {
+                // svgf_main.cpp:2170: after the a-trous stages when the denoiser runs, on the beauty otherwise; through the flow without
+                // the jitter offset
+                if (gfx_restir_copy_taa_flow_to_linear(ctx, nullptr, lin[8])) fail("gfx_restir_copy_taa_flow_to_linear:", gfx_last_error(ctx));
+                const gfx_taa_inputs tin = { o.width, o.height, den ? lin[6] : lin[0], lin[8] };
+                if (hipEventRecord(evTaa[2 * frame], nullptr) != hipSuccess) fail("hipEventRecord failed", nullptr);
+                if (gfx_taa_apply(ctx, nullptr, taa, &tin, frame == 0 ? 1 : 0, lin[7])) fail("gfx_taa_apply:", gfx_last_error(ctx));
+                if (hipEventRecord(evTaa[2 * frame + 1], nullptr) != hipSuccess) fail("hipEventRecord failed", nullptr);
+            }
             if (gfxh_restir_outputs_consumed(renderer, nullptr)) fail("gfxh_restir_outputs_consumed:", gfxh_restir_last_error());
         }
     }
-    if (gfx_read_device(ctx, den ? lin[6] : gfxh_restir_beauty_buffer(renderer), rgba.data(), rgba.size() * sizeof(float))) fail("gfx_read_device:", gfx_last_error(ctx));
-    if (den) {
-        double denoiseMs = 0.0;
+    const void* shown = taa ? lin[7] : den ? lin[6] : gfxh_restir_beauty_buffer(renderer);
+    if (gfx_read_device(ctx, shown, rgba.data(), rgba.size() * sizeof(float))) fail("gfx_read_device:", gfx_last_error(ctx));
+    // mean ms per frame between each event pair
+    auto eventMs = [&](const std::vector<hipEvent_t>& e) {
+        double sum = 0.0;
         for (uint32_t frame = 0; frame < o.frames; ++frame) {
             float ms = 0.0f;
-            if (hipEventSynchronize(ev[2 * frame + 1]) != hipSuccess || hipEventElapsedTime(&ms, ev[2 * frame], ev[2 * frame + 1]) != hipSuccess)
+            if (hipEventSynchronize(e[2 * frame + 1]) != hipSuccess || hipEventElapsedTime(&ms, e[2 * frame], e[2 * frame + 1]) != hipSuccess)
                 fail("hipEventElapsedTime failed", nullptr);
-            denoiseMs += ms;
+            sum += ms;
         }
-        std::printf(",\n \"denoise_ms\": %.6g", denoiseMs / o.frames);
+        return sum / o.frames;
+    };
+    if (den) {
+        std::printf(",\n \"denoise_ms\": %.6g", eventMs(ev));
         gfx_denoiser_destroy(den);
-        for (void* p : lin) (void)hipFree(p);
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     }
+    if (taa) {
+        std::printf(",\n \"taa_ms\": %.6g", eventMs(evTaa));
+        gfx_taa_destroy(taa);
+        for (hipEvent_t e : evTaa) (void)hipEventDestroy(e);
+    }
+    for (void* p : lin) if (p) (void)hipFree(p);
     }
     double sum[3] = { 0, 0, 0 };
     for (size_t p = 0; p < static_cast<size_t>(o.width) * o.height; ++p) for (int k = 0; k < 3; ++k) sum[k] += rgba[4 * p + k];

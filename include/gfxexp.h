@@ -431,6 +431,42 @@ int gfx_denoiser_destroy(gfx_denoiser* den);
 int gfx_denoise(gfx_ctx* ctx, void* stream, gfx_denoiser* den, const gfx_denoiser_inputs* in, int isFirstFrame, void* dDenoisedFloat4);
 int gfx_denoiser_history(gfx_denoiser* den, gfx_denoiser_history_buffers* out);
 
+/* ---------------------------------------------------------------- temporal anti-aliasing ------ */
+
+/* The TAA half of svgf/'s output pass, applyAlbedoModulationAndTemporalAntiAliasing (svgf/gpu_kernels/svgf.cu:533-611, launch
+ * svgf_main.cpp:2170) with reprojectPreviousAccumulation (svgf.cu:465-531): reproject the previous final image through the flow,
+ * clamp it to the current frame's 3x3 neighbourhood (the mean of the box and cross extrema), blend with an exponential moving
+ * average of weight 1/historyLength (the taaHistoryLength slider 2^0..2^8, default 16: svgf_main.cpp:1736, :1798-1803, :1986).
+ * Independent of the denoiser, as the reference's enableSVGF and enableTemporalAA are: run it on gfx_denoise's output or on the
+ * linear beauty.  One deviation: a pixel whose previous position is off screen outputs the current colour (the reference drops its
+ * off-screen flag and blends black clamped to the neighbourhood).  The order of operations is specified in
+ * gfxexp_amd/csrc/denoise/taa.hip; the CPU restatement of tests/taa_ref.cpp follows the same text bit for bit. */
+typedef struct gfx_taa gfx_taa;              /* opaque; owns its double-buffered history */
+/* The flow gfx_taa_apply should reproject through, into a caller-owned float2[W*H], from the G-buffers of the current
+ * gfx_restir_set_params: per pixel the current minus the previous raster position of the point the pixel sees.  For a surface
+ * that is GBuffer1.motionVector less the pixel's jitter offset ((x + 0.5) minus the hit point's current raster position); for a
+ * pixel without a surface, the motion of its view direction under the camera rotation (svgf.cu:443-449; restir_di's miss program
+ * projects the direction as a point, optix_gbuffer_kernels.cu:205-221); 0 under resetFlowBuffer.  The motion vector itself, fed
+ * to TAA under enableJittering, resamples the history at a random sub-pixel offset every frame. */
+int gfx_restir_copy_taa_flow_to_linear(gfx_ctx* ctx, void* stream, void* dLinearFlow);
+typedef struct gfx_taa_inputs {
+    uint32_t width, height;                  /* of both buffers; must equal gfx_taa_create's */
+    const void* color;                       /* float4[W*H]: the current colour; alpha is copied to the output */
+    const void* flow;                        /* float2[W*H]: pixel centre minus previous position, in pixels (as gfx_denoise reads it) */
+} gfx_taa_inputs;
+/* Allocates the history (zeroed).  historyLength 1..256; a zero size, a side above 16384 or a historyLength out of range returns 1. */
+int gfx_taa_create(gfx_ctx* ctx, uint32_t width, uint32_t height, uint32_t historyLength, gfx_taa** out);
+int gfx_taa_destroy(gfx_taa* taa);
+/* The reference's live slider: takes effect from the next gfx_taa_apply.  0 or above 256 returns 1 and changes nothing. */
+int gfx_taa_set_history_length(gfx_taa* taa, uint32_t historyLength);
+/* Enqueues exactly one kernel on `stream`; no allocation, no synchronisation.  isFirstFrame ignores the history (out = color).
+ * dOutFloat4 = float4[W*H]; its image also becomes the history of the next call.  A null input or output, a size other than
+ * create's, dOutFloat4 == color (the pass reads neighbours: no in-place use) or dOutFloat4 == one of the object's own history
+ * buffers returns 1, launches nothing and leaves the history as it was. */
+int gfx_taa_apply(gfx_ctx* ctx, void* stream, gfx_taa* taa, const gfx_taa_inputs* in, int isFirstFrame, void* dOutFloat4);
+/* Device pointer of the float4[W*H] history the next gfx_taa_apply reprojects (the last output; read-only; for tests). */
+int gfx_taa_history(gfx_taa* taa, const void** dHistory);
+
 /* ---------------------------------------------------------------- path tracing ---------------- */
 
 /* The baseline path tracer (path_tracing/path_tracing_main.cpp:2068-2093: G-buffer pipeline, then
