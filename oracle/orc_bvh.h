@@ -53,10 +53,20 @@ struct AABB { // common/basic_types.h AABB_T
             const V3 e(k * std::fabs(invRayDir.x) * (std::fabs(org.x) + std::fmax(std::fabs(minP.x), std::fabs(maxP.x))),
                        k * std::fabs(invRayDir.y) * (std::fabs(org.y) + std::fmax(std::fabs(minP.y), std::fabs(maxP.y))),
                        k * std::fabs(invRayDir.z) * (std::fabs(org.z) + std::fmax(std::fabs(minP.z), std::fabs(maxP.z))));
-            // an axis the ray runs parallel to has e = inf and near / far = -+inf already (or NaN, which fmin / fmax drop)
-            if (std::isfinite(e.x)) { near_.x -= e.x; far_.x += e.x; }
-            if (std::isfinite(e.y)) { near_.y -= e.y; far_.y += e.y; }
-            if (std::isfinite(e.z)) { near_.z -= e.z; far_.z += e.z; }
+            // An axis the ray runs parallel to (1 / dir_k = +-inf, so e_k = inf) is widened in space instead, by the limit of the above
+            // as dir_k goes to 0: the slab holds the whole ray when org_k lies within 2^-20 (|org_k| + |plane_k|) of [min_k, max_k], else
+            // nothing.  Left to the slab distances, such an axis was not widened at all, and a ray that starts exactly in one of the
+            // box's planes got (plane - org) * inf = 0 * inf = NaN there, which fmin / fmax drop -- the other plane's +-inf became BOTH
+            // bounds and a box the ray runs along the face of was culled (rays grazing an axis-aligned wall, test_oracle_trace_edges.py).
+            auto parallel = [k](float o, float lo, float hi, float* n, float* f) {
+                const float d = k * (std::fabs(o) + std::fmax(std::fabs(lo), std::fabs(hi)));
+                const bool inside = o >= lo - d && o <= hi + d;
+                *n = inside ? -INFINITY : INFINITY;
+                *f = inside ? INFINITY : -INFINITY;
+            };
+            if (std::isfinite(e.x)) { near_.x -= e.x; far_.x += e.x; } else parallel(org.x, minP.x, maxP.x, &near_.x, &far_.x);
+            if (std::isfinite(e.y)) { near_.y -= e.y; far_.y += e.y; } else parallel(org.y, minP.y, maxP.y, &near_.y, &far_.y);
+            if (std::isfinite(e.z)) { near_.z -= e.z; far_.z += e.z; } else parallel(org.z, minP.z, maxP.z, &near_.z, &far_.z);
         }
         *hitDistMin = std::fmax(std::fmax(near_.x, near_.y), near_.z);
         *hitDistMax = std::fmin(std::fmin(far_.x, far_.y), far_.z);

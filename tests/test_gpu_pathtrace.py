@@ -9,7 +9,10 @@ from oracle import oracle as O
 from tests import util
 
 
-def run_pt_both(hs, width, height, frames=2, max_len=5, camera=None, env=None, jitter=0, env_rotation=0.0, rows=None, fuse=None, regen=None):
+def run_pt_both(hs, width, height, frames=2, max_len=5, camera=None, env=None, jitter=0, env_rotation=0.0, rows=None, fuse=None, regen=None,
+                build=None):
+    """build: callable(ctx, osc) -> accel handle, in place of a plain accel_build (a transform update between the build and the
+    frames, applied to the oracle's scene too: tests/test_gpu_trace_edges.py)."""
     import torch
     ctx = api.Context(0)
     if fuse is not None:
@@ -17,9 +20,9 @@ def run_pt_both(hs, width, height, frames=2, max_len=5, camera=None, env=None, j
     if regen is not None:
         ctx.tunable_set("pt_regen", regen)
     hs.upload(ctx)
-    accel = ctx.accel_build()
-    ctx.lights_build_static()
     osc = util.feed_oracle(hs)
+    accel = build(ctx, osc) if build else ctx.accel_build()
+    ctx.lights_build_static()
     cam = camera if camera is not None else api.make_camera(width, height, pos=(1.5, 5.0, 14.0), pitch=12.0, yaw=186.0)
     ocam = util.copy_struct(O.GfxCamera, cam)
     pb_gpu_init = util.PixelBuffers(width, height)

@@ -12,43 +12,9 @@ from tests import util
 pytestmark = pytest.mark.gpu
 
 
-def _gpu_trace(ctx, accel, mode, org, dirs, counters=False):
-    import torch
-    n = len(org)
-    d_org = torch.from_numpy(org).cuda()
-    d_dir = torch.from_numpy(dirs).cuda()
-    if mode == api.TRACE_ANY:
-        d_out = torch.zeros(n, dtype=torch.int32, device="cuda")
-    else:
-        d_out = torch.zeros(n * 4, dtype=torch.int32, device="cuda")
-    d_cnt = torch.zeros(4, dtype=torch.int64, device="cuda") if counters else None
-    ctx.trace(accel, mode, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), d_cnt.data_ptr() if counters else 0,
-              stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    out = d_out.cpu().numpy()
-    res = out.view(np.uint32) if mode == api.TRACE_ANY else out.view(api.HIT_DTYPE).reshape(n)
-    if counters:
-        return res, d_cnt.cpu().numpy()
-    return res
-
-
-def _tri_ids(ctx, accel):
-    ptr, n = ctx.accel_tri_ids_ptr(accel)
-    return ctx.read_device(ptr, n * 12).view(api.TRI_IDS_DTYPE).reshape(n)
-
-
-def _compare_closest(gpu_hits, gpu_ids, orc_hits, orc_ids, what):
-    g_hit = gpu_hits["triIndex"] != api.GFX_INVALID_SLOT
-    o_hit = orc_hits["triIndex"] != api.GFX_INVALID_SLOT
-    assert np.array_equal(g_hit, o_hit), f"{what}: hit/miss differs on {np.count_nonzero(g_hit != o_hit)} rays"
-    gi = gpu_ids[gpu_hits["triIndex"][g_hit]]
-    oi = orc_ids[orc_hits["triIndex"][o_hit]]
-    for f in ("instSlot", "geomInstSlot", "primIndex"):
-        assert np.array_equal(gi[f], oi[f]), f"{what}: {f} differs on {np.count_nonzero(gi[f] != oi[f])} rays"
-    for f in ("dist", "bcB", "bcC"):
-        util.assert_same_bits(f"{what}.{f}", gpu_hits[f][g_hit], orc_hits[f][o_hit])
-    # misses report tmax
-    util.assert_same_bits(f"{what}.miss dist", gpu_hits["dist"][~g_hit], orc_hits["dist"][~o_hit])
+_gpu_trace = util.gpu_trace
+_tri_ids = util.accel_tri_ids
+_compare_closest = util.compare_closest
 
 
 @pytest.mark.parametrize("scene_name,res", [("bunny", 512), ("teapot", 384)])

@@ -348,6 +348,47 @@ def assert_same_bits(name, a, b):
                              f"{np.ascontiguousarray(b).reshape(-1)[first] if item > 1 else b8[bad[0]]}")
 
 
+def gpu_trace(ctx, accel, mode, org, dirs, counters=False):
+    """gfx_trace of (org.xyz | tmin, dir.xyz | tmax) rays on cuda:0 -> gfx_hit records (closest) or uint32 flags (any);
+    counters=True: also the launch's u64[4] {node fetches, triangle fetches, rays, stack spills}."""
+    import torch
+    n = len(org)
+    d_org = torch.from_numpy(np.ascontiguousarray(org)).cuda()
+    d_dir = torch.from_numpy(np.ascontiguousarray(dirs)).cuda()
+    d_out = torch.zeros(n if mode == api.TRACE_ANY else n * 4, dtype=torch.int32, device="cuda")
+    d_cnt = torch.zeros(4, dtype=torch.int64, device="cuda") if counters else None
+    ctx.trace(accel, mode, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), d_cnt.data_ptr() if counters else 0,
+              stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    out = d_out.cpu().numpy()
+    res = out.view(np.uint32) if mode == api.TRACE_ANY else out.view(api.HIT_DTYPE).reshape(n)
+    if counters:
+        return res, d_cnt.cpu().numpy()
+    return res
+
+
+def accel_tri_ids(ctx, accel):
+    """(instSlot, geomInstSlot, primIndex) of every triangle record of a GPU acceleration structure."""
+    ptr, n = ctx.accel_tri_ids_ptr(accel)
+    return ctx.read_device(ptr, n * 12).view(api.TRI_IDS_DTYPE).reshape(n)
+
+
+def compare_closest(gpu_hits, gpu_ids, orc_hits, orc_ids, what):
+    """Closest hits of the GPU (triIndex = record index, gpu_ids) and of the oracle (flattened index, orc_ids) are the same, bit for bit:
+    hit or miss, (instSlot, geomInstSlot, primIndex), dist, bcB, bcC, and tmax on a miss."""
+    g_hit = gpu_hits["triIndex"] != api.GFX_INVALID_SLOT
+    o_hit = orc_hits["triIndex"] != api.GFX_INVALID_SLOT
+    assert np.array_equal(g_hit, o_hit), f"{what}: hit/miss differs on {np.count_nonzero(g_hit != o_hit)} rays"
+    gi = gpu_ids[gpu_hits["triIndex"][g_hit]]
+    oi = orc_ids[orc_hits["triIndex"][o_hit]]
+    for f in ("instSlot", "geomInstSlot", "primIndex"):
+        assert np.array_equal(gi[f], oi[f]), f"{what}: {f} differs on {np.count_nonzero(gi[f] != oi[f])} rays"
+    for f in ("dist", "bcB", "bcC"):
+        assert_same_bits(f"{what}.{f}", gpu_hits[f][g_hit], orc_hits[f][o_hit])
+    # misses report tmax
+    assert_same_bits(f"{what}.miss dist", gpu_hits["dist"][~g_hit], orc_hits["dist"][~o_hit])
+
+
 class RegirBuffers:
     """Host (numpy) ReGIR grid state in the ABI layout; device mirrors via to_device()."""
 
