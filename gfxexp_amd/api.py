@@ -107,6 +107,9 @@ class GfxNrcParams(C.Structure):
 
 
 TEX_RGBA8_SRGB, TEX_RGBA8_UNORM, TEX_R8_UNORM, TEX_RG8_UNORM, TEX_RGBA32F = 0, 1, 2, 3, 4
+BC1, BC2, BC3, BC4_UNORM, BC4_SNORM, BC5_UNORM, BC5_SNORM, BC7 = range(8)      # enum gfx_bc_format
+BC_BLOCK_BYTES = {BC1: 8, BC2: 16, BC3: 16, BC4_UNORM: 8, BC4_SNORM: 8, BC5_UNORM: 16, BC5_SNORM: 16, BC7: 16}
+TEX_BYTES_PER_TEXEL = {TEX_RGBA8_SRGB: 4, TEX_RGBA8_UNORM: 4, TEX_R8_UNORM: 1, TEX_RG8_UNORM: 2, TEX_RGBA32F: 16}
 BUMP_NORMAL_MAP, BUMP_NORMAL_MAP_2CH, BUMP_HEIGHT_MAP, BUMP_LEFT_HANDED = 0, 1, 2, 0x100
 
 
@@ -208,7 +211,7 @@ def abi_mirrors():
             "gfxh_exchange_buffer": GfxhExchangeBuffer, "gfxh_exchange_desc": GfxhExchangeDesc, "gfxh_band_plan": GfxhBandPlan,
             "gfxh_nrc_config": GfxhNrcConfig, "gfxh_sdr_config": GfxhSdrConfig,
             "gfx_denoiser_settings": GfxDenoiserSettings, "gfx_denoiser_inputs": GfxDenoiserInputs,
-            "gfx_denoiser_history_buffers": GfxDenoiserHistoryBuffers, "gfx_taa_inputs": GfxTaaInputs}
+            "gfx_denoiser_history_buffers": GfxDenoiserHistoryBuffers, "gfx_taa_inputs": GfxTaaInputs, "gfxh_dds_info": GfxhDdsInfo}
 
 
 class RcclExchange:
@@ -311,7 +314,7 @@ GBUFFER3_DTYPE = np.dtype([("qShadingNormal", "<u4"), ("qShadingTangent", "<u4")
 
 # every symbol include/gfxexp.h and include/gfxexp_host.h declare
 C_ABI_SYMBOLS = [
-    "gfx_ctx_create", "gfx_ctx_destroy", "gfx_last_error", "gfx_version", "gfx_material_set", "gfx_texture_set", "gfx_texture_sample", "gfx_geom_create",
+    "gfx_ctx_create", "gfx_ctx_destroy", "gfx_last_error", "gfx_version", "gfx_material_set", "gfx_texture_set", "gfx_texture_sample", "gfx_texture_set_bc", "gfx_texture_read", "gfx_geom_create",
     "gfx_group_create", "gfx_instance_create", "gfx_instance_set_transform", "gfx_instance_set_transform_and_normal_matrix", "gfx_instance_set_dynamic",
     "gfx_accel_build",
     "gfx_accel_set_max_leaf", "gfx_accel_stats", "gfx_accel_tri_ids", "gfx_lights_build_static",
@@ -322,11 +325,11 @@ C_ABI_SYMBOLS = [
     "gfx_nrc_create", "gfx_nrc_destroy", "gfx_nrc_infer", "gfx_nrc_infer_indirect", "gfx_nrc_query_count_ptr", "gfx_nrc_train", "gfx_nrc_num_params", "gfx_nrc_set_params",
     "gfx_nrc_get_params", "gfx_nrc_inference_image", "gfx_nrc_inference_image_async", "gfx_nrc_params_checksum", "gfx_nrc_set_render_params",
     "gfx_read_device", "gfx_timing_enable", "gfx_timing_collect", "gfx_counters_enable", "gfx_counters_read", "gfx_trace_diag_read", "gfx_pt_diag_read",
-    "gfx_tunable_set", "gfx_stream_copy",
+    "gfx_tunable_set", "gfx_stream_copy", "gfx_bc_expand",
 ]
 HOST_ABI_SYMBOLS = [
     "gfxh_scene_create", "gfxh_scene_destroy", "gfxh_last_error", "gfxh_scene_add_material_traditional",
-    "gfxh_scene_add_material", "gfxh_scene_add_texture", "gfxh_scene_load_texture", "gfxh_scene_num_textures", "gfxh_scene_get_texture", "gfxh_scene_add_geom", "gfxh_scene_add_group", "gfxh_scene_add_instance",
+    "gfxh_scene_add_material", "gfxh_scene_add_texture", "gfxh_scene_load_texture", "gfxh_scene_num_textures", "gfxh_scene_get_texture", "gfxh_scene_add_texture_bc", "gfxh_scene_get_texture_bc", "gfxh_dds_parse", "gfxh_scene_add_geom", "gfxh_scene_add_group", "gfxh_scene_add_instance",
     "gfxh_scene_load_obj", "gfxh_scene_load_obj_conv", "gfxh_scene_add_rectangle_textured", "gfxh_scene_add_rectangle", "gfxh_scene_make_street", "gfxh_scene_counts",
     "gfxh_scene_get_material", "gfxh_scene_get_geom", "gfxh_scene_get_group", "gfxh_scene_get_instance",
     "gfxh_scene_bounds", "gfxh_scene_upload", "gfxh_make_transform", "gfxh_make_orientation",
@@ -368,7 +371,8 @@ def lib():
         L.gfxh_restir_accel.restype = C.c_uint64
         for name in ("gfxh_scene_add_material_traditional", "gfxh_scene_add_material", "gfxh_scene_add_geom",
                      "gfxh_scene_add_group", "gfxh_scene_add_instance", "gfxh_scene_load_obj", "gfxh_scene_load_obj_conv",
-                     "gfxh_scene_add_rectangle", "gfxh_scene_add_rectangle_textured"):
+                     "gfxh_scene_add_rectangle", "gfxh_scene_add_rectangle_textured", "gfxh_scene_add_texture", "gfxh_scene_add_texture_bc",
+                     "gfxh_scene_load_texture"):
             getattr(L, name).restype = C.c_uint32
         _lib = L
     return _lib
@@ -376,6 +380,39 @@ def lib():
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+class GfxhDdsInfo(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("mipCount", C.c_uint32), ("isBlockCompressed", C.c_uint32), ("bcFormat", C.c_uint32),
+                ("isBGRA", C.c_uint32), ("isSRGB", C.c_uint32), ("reserved", C.c_uint32), ("dataOffset", C.c_uint64), ("dataBytes", C.c_uint64)]
+
+
+def dds_parse(data):
+    """gfxh_dds_parse of the bytes of a .dds file: a GfxhDdsInfo, or GfxError with the cause.  The parser is handed a heap block of
+    exactly len(data) bytes, so that a sanitizer build (tools/asan_cpu_suite.sh) sees any read past the end."""
+    L = lib()
+    libc = C.CDLL(None)
+    libc.malloc.restype = C.c_void_p
+    buf = bytes(data)
+    p = libc.malloc(C.c_size_t(max(len(buf), 1)))
+    if not p:
+        raise MemoryError("dds_parse: malloc")
+    try:
+        C.memmove(p, buf, len(buf))
+        info = GfxhDdsInfo()
+        if L.gfxh_dds_parse(C.c_void_p(p), C.c_size_t(len(buf)), C.byref(info)):
+            raise GfxError(L.gfxh_last_error().decode(errors="replace"))
+        return info
+    finally:
+        libc.free(C.c_void_p(p))
+
+
+def _bc_blocks(blocks, w, h, bc_format):
+    b = np.ascontiguousarray(blocks, np.uint8).reshape(-1)
+    if bc_format in BC_BLOCK_BYTES and b.size != ((w + 3) // 4) * ((h + 3) // 4) * BC_BLOCK_BYTES[bc_format]:
+        raise GfxError("a %d x %d texture of block format %d takes %d bytes of blocks, got %d"
+                       % (w, h, bc_format, ((w + 3) // 4) * ((h + 3) // 4) * BC_BLOCK_BYTES[bc_format], b.size))
+    return b
 
 
 def _f3(v):
@@ -418,19 +455,36 @@ class HostScene:
             raise GfxError(self.L.gfxh_last_error().decode(errors="replace"))
         return slot
 
+    def add_texture_bc(self, blocks, width, height, bc_format, fmt):
+        """blocks: ceil(width / 4) * ceil(height / 4) blocks of `bc_format` (BC1 .. BC7) as bytes, row-major; sampled as the 8-bit
+        format `fmt`.  Returns the 1-based texture slot."""
+        b = _bc_blocks(blocks, width, height, bc_format)
+        slot = self.L.gfxh_scene_add_texture_bc(self.h, C.c_uint32(width), C.c_uint32(height), C.c_uint32(bc_format), _p(b), C.c_uint32(fmt))
+        if slot == 0:
+            raise GfxError(self.L.gfxh_last_error().decode(errors="replace"))
+        return slot
+
     def load_texture(self, path, fmt8=0):
+        """An image file (PPM / PGM / PFM / BMP / TGA / EXR) or a .dds, whose block-compressed level 0 stays blocks."""
         slot = self.L.gfxh_scene_load_texture(self.h, path.encode(), C.c_uint32(fmt8))
         if slot == 0:
             raise GfxError(self.L.gfxh_last_error().decode(errors="replace"))
         return slot
 
     def textures(self):
-        """[(slot, width, height, format, texel bytes)] of every texture."""
+        """[(slot, width, height, format, texel bytes)] of every texture; a block-compressed one yields
+        (slot, width, height, format, None, bc format, block bytes)."""
         out = []
         for slot in range(1, self.L.gfxh_scene_num_textures(self.h) + 1):
             w, h, f, ptr = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_void_p()
             self.L.gfxh_scene_get_texture(self.h, C.c_uint32(slot), C.byref(w), C.byref(h), C.byref(f), C.byref(ptr))
-            bpp = {TEX_RGBA8_SRGB: 4, TEX_RGBA8_UNORM: 4, TEX_R8_UNORM: 1, TEX_RG8_UNORM: 2, TEX_RGBA32F: 16}[f.value]
+            if not ptr.value:
+                bc, n = C.c_uint32(), C.c_size_t()
+                self.L.gfxh_scene_get_texture_bc(self.h, C.c_uint32(slot), C.byref(bc), C.byref(ptr), C.byref(n))
+                blocks = np.frombuffer((C.c_char * n.value).from_address(ptr.value), dtype=np.uint8).copy()
+                out.append((slot, w.value, h.value, f.value, None, bc.value, blocks))
+                continue
+            bpp = TEX_BYTES_PER_TEXEL[f.value]
             data = np.frombuffer((C.c_char * (bpp * w.value * h.value)).from_address(ptr.value), dtype=np.uint8).copy()
             out.append((slot, w.value, h.value, f.value, data))
         return out
@@ -694,6 +748,17 @@ class Context:
         t = np.ascontiguousarray(texels)
         self._check(self.L.gfx_texture_set(self.h, C.c_uint32(slot), C.c_uint32(t.shape[1]), C.c_uint32(t.shape[0]), C.c_uint32(fmt), _p(t)))
 
+    def texture_set_bc(self, slot, blocks, width, height, bc_format, fmt):
+        """Block-compressed upload: `blocks` as bytes (see HostScene.add_texture_bc), expanded on the device into the 8-bit format `fmt`."""
+        b = _bc_blocks(blocks, width, height, bc_format)
+        self._check(self.L.gfx_texture_set_bc(self.h, C.c_uint32(slot), C.c_uint32(width), C.c_uint32(height), C.c_uint32(bc_format), _p(b), C.c_uint32(fmt)))
+
+    def texture_read(self, slot, width, height, fmt, stream=0):
+        """The slot's texels as they lie in the device pool: uint8 [height, width, channels] ([height, width, 16] bytes for RGBA32F)."""
+        out = np.zeros((height, width, TEX_BYTES_PER_TEXEL[fmt]), np.uint8)
+        self._check(self.L.gfx_texture_read(self.h, C.c_void_p(stream), C.c_uint32(slot), _p(out), C.c_size_t(out.nbytes)))
+        return out
+
     def texture_sample(self, slot, d_uv, n, d_out, gather=False, stream=0):
         self._check(self.L.gfx_texture_sample(self.h, C.c_void_p(stream), C.c_uint32(slot), C.c_void_p(d_uv), C.c_uint32(n), C.c_void_p(d_out),
                                               C.c_int(1 if gather else 0)))
@@ -808,6 +873,11 @@ class Context:
     def stream_copy(self, d_dst, d_src, nbytes, stream=0):
         """Measurement utility: device-to-device copy with 16-byte accesses per lane (bench.py times it for roofline.peak_measured)."""
         self._check(self.L.gfx_stream_copy(self.h, C.c_void_p(d_dst), C.c_void_p(d_src), C.c_size_t(nbytes), C.c_void_p(stream)))
+
+    def bc_expand(self, bc_format, d_blocks, width, height, fmt, d_texels, stream=0):
+        """Measurement utility: the upload-time expansion on caller-owned device memory (tools/bench_bc_expand.py times it)."""
+        self._check(self.L.gfx_bc_expand(self.h, C.c_void_p(stream), C.c_uint32(bc_format), C.c_void_p(d_blocks), C.c_uint32(width), C.c_uint32(height),
+                                         C.c_uint32(fmt), C.c_void_p(d_texels)))
 
     def counters_enable(self, on=True):
         self._check(self.L.gfx_counters_enable(self.h, C.c_int(1 if on else 0)))

@@ -8,6 +8,7 @@
 #include "internal.h"
 #include "denoise/denoise.h"
 #include "denoise/taa.h"
+#include "bc/bc_textures.h"
 
 using namespace gfx;
 
@@ -84,6 +85,7 @@ int gfx_ctx_create(int device, gfx_ctx** out) {
 void gfx_ctx_destroy(gfx_ctx* ctx) {
     if (!ctx) return;
     (void)hipDeviceSynchronize();
+    bc_textures_drop(ctx->c);
     delete ctx;
 }
 
@@ -119,7 +121,49 @@ int gfx_texture_set(gfx_ctx* ctx, uint32_t texSlot, uint32_t width, uint32_t hei
     HostTexture& t = ctx->c.textures[texSlot];
     t.width = width; t.height = height; t.format = format;
     t.texels.assign(static_cast<const uint8_t*>(texels), static_cast<const uint8_t*>(texels) + bpp * width * height);
+    bc_texture_forget(ctx->c, texSlot);
     ctx->c.sceneDirty = true;
+    GFX_CATCH(ctx)
+}
+
+static size_t texel_bytes(uint32_t format) {
+    return format == GFX_TEX_RGBA32F ? 16 : (format == GFX_TEX_RG8_UNORM ? 2 : (format == GFX_TEX_R8_UNORM ? 1 : 4));
+}
+
+int gfx_texture_set_bc(gfx_ctx* ctx, uint32_t texSlot, uint32_t width, uint32_t height, uint32_t bcFormat, const void* blocks, uint32_t format) {
+    GFX_TRY(ctx)
+    if (texSlot == 0 || texSlot > (1u << 20)) throw HipError("gfx_texture_set_bc: texture slots are 1-based");
+    if (width == 0 || height == 0 || width > 16384 || height > 16384) throw HipError("gfx_texture_set_bc: bad size");
+    const uint32_t blockBytes = bc_block_bytes(bcFormat);
+    if (blockBytes == 0) throw HipError("gfx_texture_set_bc: unknown block-compressed format");
+    if (format == GFX_TEX_RGBA32F) throw HipError("gfx_texture_set_bc: blocks expand into an 8-bit format, not GFX_TEX_RGBA32F");
+    if (format != GFX_TEX_RGBA8_SRGB && format != GFX_TEX_RGBA8_UNORM && format != GFX_TEX_R8_UNORM && format != GFX_TEX_RG8_UNORM)
+        throw HipError("gfx_texture_set_bc: unknown format");
+    if (!blocks) throw HipError("gfx_texture_set_bc: null blocks");
+    // the blocks reach the device before the slot changes: a failure here leaves the slot as it was
+    bc_texture_store(ctx->c, texSlot, bcFormat, blocks, static_cast<size_t>((width + 3) / 4) * ((height + 3) / 4) * blockBytes);
+    if (ctx->c.textures.size() <= texSlot) ctx->c.textures.resize(texSlot + 1);
+    HostTexture& t = ctx->c.textures[texSlot];
+    t.width = width; t.height = height; t.format = format;
+    std::vector<uint8_t>().swap(t.texels);      // no texels on the host: scene_upload reserves the region and expands into it
+    ctx->c.sceneDirty = true;
+    GFX_CATCH(ctx)
+}
+
+int gfx_texture_read(gfx_ctx* ctx, void* stream, uint32_t texSlot, void* hostOut, size_t bytes) {
+    GFX_TRY(ctx)
+    Context& c = ctx->c;
+    if (texSlot == 0 || texSlot >= c.textures.size() || c.textures[texSlot].width == 0) throw HipError("gfx_texture_read: texture slot was never set");
+    const HostTexture& t = c.textures[texSlot];
+    if (!hostOut || bytes != texel_bytes(t.format) * t.width * t.height) throw HipError("gfx_texture_read: the buffer must hold the slot's texels exactly");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    scene_upload(c, s);
+    DevTexture d;
+    GFX_HIP(hipMemcpyAsync(&d, c.dTextures.as<DevTexture>() + texSlot, sizeof(d), hipMemcpyDeviceToHost, s));
+    GFX_HIP(hipStreamSynchronize(s));
+    if (d.width != t.width || d.height != t.height || d.format != t.format) throw HipError("gfx_texture_read: the device descriptor does not match the slot");
+    GFX_HIP(hipMemcpyAsync(hostOut, c.dTexelPool.as<uint32_t>() + d.offset, bytes, hipMemcpyDeviceToHost, s));
+    GFX_HIP(hipStreamSynchronize(s));
     GFX_CATCH(ctx)
 }
 
@@ -662,6 +706,13 @@ int gfx_tunable_set(gfx_ctx* ctx, const char* name, int value) {
 int gfx_stream_copy(gfx_ctx* ctx, void* dDst, const void* dSrc, size_t bytes, void* stream) {
     GFX_TRY(ctx)
     stream_copy(ctx->c, static_cast<hipStream_t>(stream), dDst, dSrc, bytes);
+    GFX_CATCH(ctx)
+}
+
+int gfx_bc_expand(gfx_ctx* ctx, void* stream, uint32_t bcFormat, const void* dBlocks, uint32_t width, uint32_t height, uint32_t format, void* dTexels) {
+    GFX_TRY(ctx)
+    if (!dBlocks || !dTexels) throw HipError("gfx_bc_expand: null pointer");
+    bc_expand_launch(static_cast<hipStream_t>(stream), bcFormat, dBlocks, width, height, format, dTexels);
     GFX_CATCH(ctx)
 }
 

@@ -84,6 +84,8 @@ const Field kFields[] = {
     F(gfxh_nrc_config, regirEnableTemporalReuse), F(gfxh_nrc_config, regirEnableCellRandomization), F(gfxh_nrc_config, enableBumpMapping),
     S(gfxh_sdr_config), F(gfxh_sdr_config, alphaForOverride), F(gfxh_sdr_config, brightnessScale), F(gfxh_sdr_config, applyToneMap),
     F(gfxh_sdr_config, apply_sRGB_gammaCorrection), F(gfxh_sdr_config, flipY),
+    S(gfxh_dds_info), F(gfxh_dds_info, width), F(gfxh_dds_info, height), F(gfxh_dds_info, mipCount), F(gfxh_dds_info, isBlockCompressed), F(gfxh_dds_info, bcFormat),
+    F(gfxh_dds_info, isBGRA), F(gfxh_dds_info, isSRGB), F(gfxh_dds_info, reserved), F(gfxh_dds_info, dataOffset), F(gfxh_dds_info, dataBytes),
 };
 #undef S
 #undef F

@@ -28,7 +28,8 @@ thread_local std::string g_hostError;
 
 struct Geom { std::vector<gfx_vertex> v; std::vector<uint32_t> t; uint32_t mat; };
 struct Inst { uint32_t group; float xfm[12]; };
-struct Tex { uint32_t width = 0, height = 0, format = 0; std::vector<uint8_t> texels; };
+// an uncompressed texture holds texels; a block-compressed one holds blocks (isBc) and is sampled as the 8-bit `format`
+struct Tex { uint32_t width = 0, height = 0, format = 0; std::vector<uint8_t> texels; bool isBc = false; uint32_t bcFormat = 0; std::vector<uint8_t> blocks; };
 
 } // namespace
 
@@ -241,7 +242,102 @@ uint32_t gfxh_scene_num_textures(gfxh_scene* s) { return static_cast<uint32_t>(s
 int gfxh_scene_get_texture(gfxh_scene* s, uint32_t slot, uint32_t* width, uint32_t* height, uint32_t* format, const void** texels) {
     if (slot == 0 || slot > s->textures.size()) { g_hostError = "gfxh_scene_get_texture: bad slot"; return 1; }
     const Tex& t = s->textures[slot - 1];
-    *width = t.width; *height = t.height; *format = t.format; *texels = t.texels.data();
+    *width = t.width; *height = t.height; *format = t.format; *texels = t.isBc ? nullptr : t.texels.data();
+    return 0;
+}
+
+static uint32_t bc_bytes_per_block(uint32_t bcFormat) {
+    switch (bcFormat) {
+    case GFX_BC1: case GFX_BC4_UNORM: case GFX_BC4_SNORM: return 8;
+    case GFX_BC2: case GFX_BC3: case GFX_BC5_UNORM: case GFX_BC5_SNORM: case GFX_BC7: return 16;
+    default: return 0;
+    }
+}
+uint32_t gfxh_scene_add_texture_bc(gfxh_scene* s, uint32_t width, uint32_t height, uint32_t bcFormat, const void* blocks, uint32_t format) {
+    const size_t blockBytes = bc_bytes_per_block(bcFormat), bpp = tex_bytes_per_texel(format);
+    if (!blockBytes || !bpp || format == GFX_TEX_RGBA32F || !width || !height || !blocks) { g_hostError = "gfxh_scene_add_texture_bc: bad arguments"; return 0; }
+    if (width > kMaxTextureDim || height > kMaxTextureDim) { g_hostError = "gfxh_scene_add_texture_bc: texture larger than 16384 x 16384"; return 0; }
+    try {
+        Tex t;
+        t.width = width; t.height = height; t.format = format; t.isBc = true; t.bcFormat = bcFormat;
+        const size_t bytes = static_cast<size_t>((width + 3) / 4) * ((height + 3) / 4) * blockBytes;
+        t.blocks.assign(static_cast<const uint8_t*>(blocks), static_cast<const uint8_t*>(blocks) + bytes);
+        s->textures.push_back(std::move(t));
+    }
+    catch (const std::exception& e) { g_hostError = std::string("gfxh_scene_add_texture_bc: ") + e.what(); return 0; }
+    return static_cast<uint32_t>(s->textures.size());
+}
+int gfxh_scene_get_texture_bc(gfxh_scene* s, uint32_t slot, uint32_t* bcFormat, const void** blocks, size_t* bytes) {
+    if (slot == 0 || slot > s->textures.size()) { g_hostError = "gfxh_scene_get_texture_bc: bad slot"; return 1; }
+    const Tex& t = s->textures[slot - 1];
+    if (!t.isBc) { *blocks = nullptr; *bytes = 0; return 0; }
+    *bcFormat = t.bcFormat; *blocks = t.blocks.data(); *bytes = t.blocks.size();
+    return 0;
+}
+
+// dds::load (common/dds_loader.cpp:207-346) as far as the header goes; every read is checked against `bytes` first.
+int gfxh_dds_parse(const void* data, size_t bytes, gfxh_dds_info* info) {
+    auto fail = [](const std::string& why) { g_hostError = "gfxh_dds_parse: " + why; return 1; };
+    if (!data || !info) return fail("null argument");
+    std::memset(info, 0, sizeof(*info));
+    const uint8_t* d = static_cast<const uint8_t*>(data);
+    if (bytes < 128 || std::memcmp(d, "DDS ", 4) != 0) return fail("not a DDS file");
+    auto u32 = [&](size_t at) { uint32_t v; std::memcpy(&v, d + at, 4); return v; };   // at + 4 <= 128 <= bytes, or checked below
+    const uint32_t flags = u32(8), height = u32(12), width = u32(16), depth = u32(24), mips = u32(28);
+    const uint32_t pfFlags = u32(80), bitCount = u32(88), rMask = u32(92), gMask = u32(96), bMask = u32(100), aMask = u32(104), caps2 = u32(112);
+    if (caps2 & 0xFE00u) return fail("cube maps are not handled");
+    if ((caps2 & 0x200000u) || ((flags & 0x800000u) && depth > 1)) return fail("volume textures are not handled");
+    size_t offset = 128;
+    enum { kNone = 0xFFu, kRGBA = 0x100u, kBGRA = 0x101u };
+    uint32_t fmt = kNone;
+    bool srgb = false;
+    if ((pfFlags & 0x4u) && std::memcmp(d + 84, "DX10", 4) == 0) {
+        if (bytes < 148) return fail("truncated DX10 header");
+        const uint32_t dxgi = u32(128), dimension = u32(132), misc = u32(136), arraySize = u32(140);
+        offset = 148;
+        if (misc & 0x4u) return fail("cube maps are not handled");
+        if (dimension != 3) return fail("only two-dimensional textures are handled");
+        if (arraySize > 1) return fail("texture arrays are not handled");
+        switch (dxgi) {
+        case 71: case 72: fmt = GFX_BC1; break;
+        case 74: case 75: fmt = GFX_BC2; break;
+        case 77: case 78: fmt = GFX_BC3; break;
+        case 80: fmt = GFX_BC4_UNORM; break;
+        case 81: fmt = GFX_BC4_SNORM; break;
+        case 83: fmt = GFX_BC5_UNORM; break;
+        case 84: fmt = GFX_BC5_SNORM; break;
+        case 98: case 99: fmt = GFX_BC7; break;
+        case 28: case 29: fmt = kRGBA; break;
+        case 87: case 91: fmt = kBGRA; break;
+        case 95: case 96: return fail("BC6H (HDR) blocks are not decoded; convert with the asset's authoring tool to .pfm");
+        default: return fail("DXGI format " + std::to_string(dxgi) + " is not handled");
+        }
+        srgb = dxgi == 72 || dxgi == 75 || dxgi == 78 || dxgi == 99 || dxgi == 29 || dxgi == 91;   // translate: the _SRGB formats only
+    }
+    else if (pfFlags & 0x4u) {
+        static const struct { const char* code; uint32_t fmt; } kFourCC[] = {
+            { "DXT1", GFX_BC1 }, { "DXT3", GFX_BC2 }, { "DXT5", GFX_BC3 }, { "BC4U", GFX_BC4_UNORM }, { "ATI1", GFX_BC4_UNORM }, { "BC4S", GFX_BC4_SNORM },
+            { "ATI2", GFX_BC5_UNORM }, { "BC5U", GFX_BC5_UNORM }, { "BC5S", GFX_BC5_SNORM } };
+        for (const auto& f : kFourCC) if (std::memcmp(d + 84, f.code, 4) == 0) fmt = f.fmt;
+        if (fmt == kNone) {
+            std::string code;
+            for (int k = 0; k < 4; ++k) code.push_back(std::isprint(d[84 + k]) ? static_cast<char>(d[84 + k]) : '?');
+            return fail("FourCC '" + code + "' is not handled");
+        }
+    }
+    else if (bitCount == 32 && rMask == 0xFFu && gMask == 0xFF00u && bMask == 0xFF0000u) fmt = kRGBA;
+    else if (bitCount == 32 && rMask == 0xFF0000u && gMask == 0xFF00u && bMask == 0xFFu) fmt = kBGRA;
+    else { (void)aMask; return fail("uncompressed layout with " + std::to_string(bitCount) + " bits is not handled (32-bit RGBA / BGRA only)"); }
+    if (width == 0 || height == 0) return fail("empty image");
+    if (width > kMaxTextureDim || height > kMaxTextureDim) return fail("image larger than 16384 x 16384");
+    info->width = width; info->height = height; info->mipCount = mips ? mips : 1;
+    info->isBlockCompressed = fmt < kRGBA ? 1u : 0u;
+    info->bcFormat = fmt < kRGBA ? fmt : 0u;
+    info->isBGRA = fmt == kBGRA ? 1u : 0u;
+    info->isSRGB = srgb ? 1u : 0u;
+    info->dataOffset = offset;
+    info->dataBytes = fmt < kRGBA ? static_cast<uint64_t>((width + 3) / 4) * ((height + 3) / 4) * bc_bytes_per_block(fmt) : 4ull * width * height;
+    if (info->dataBytes > bytes - offset) return fail("the file ends before level 0 does");
     return 0;
 }
 
@@ -617,6 +713,19 @@ bool decode_image(const std::string& path, Image& img, std::string& err) {
 }
 } // namespace
 
+static bool is_dds_path(const std::string& path) {   // filePath.extension() == ".dds" || ".DDS" (common_host.cpp:1185-1186)
+    return path.size() >= 4 && (path.compare(path.size() - 4, 4, ".dds") == 0 || path.compare(path.size() - 4, 4, ".DDS") == 0);
+}
+// Header of a .dds map named by a material; false when the path is no .dds or the file cannot be parsed (the load then fails the
+// usual way and leaves the immediate value in place).
+static bool dds_map_info(const std::string& path, gfxh_dds_info& info) {
+    if (!is_dds_path(path)) return false;
+    std::vector<uint8_t> file;
+    try { if (!read_file(path, file)) return false; }
+    catch (const std::exception&) { return false; }
+    return gfxh_dds_parse(file.data(), file.size(), &info) == 0;
+}
+
 // loadTexture (common_host.cpp:1163-1244): cached per path; 8-bit images become RGBA8 read through `format8`
 // (GFX_TEX_RGBA8_SRGB for colour maps = needsDegamma, GFX_TEX_RGBA8_UNORM for normal maps, GFX_TEX_R8_UNORM takes
 // the red channel); float images become GFX_TEX_RGBA32F (isHDR).  Returns the texture slot, 0 on failure.
@@ -626,7 +735,23 @@ uint32_t gfxh_scene_load_texture(gfxh_scene* s, const char* path, uint32_t forma
     if (it != s->textureCache.end()) return it->second;
     Image img; std::string err;
     try {
-        if (!decode_image(path, img, err)) { g_hostError = err; return 0; }
+        if (is_dds_path(path)) {
+            // the .dds branch of loadTexture (common_host.cpp:1185-1209): level 0 as it lies in the file; blocks stay blocks
+            std::vector<uint8_t> file;
+            gfxh_dds_info info;
+            if (!read_file(path, file)) { g_hostError = std::string("cannot open ") + path; return 0; }
+            if (gfxh_dds_parse(file.data(), file.size(), &info)) { g_hostError += std::string(": ") + path; return 0; }
+            if (info.isBlockCompressed) {
+                const uint32_t fmt = (format8 == GFX_TEX_RGBA8_UNORM || format8 == GFX_TEX_R8_UNORM || format8 == GFX_TEX_RG8_UNORM) ? format8 : GFX_TEX_RGBA8_SRGB;
+                const uint32_t slot = gfxh_scene_add_texture_bc(s, info.width, info.height, info.bcFormat, file.data() + info.dataOffset, fmt);
+                if (slot) s->textureCache[key] = slot;
+                return slot;
+            }
+            img.w = info.width; img.h = info.height;
+            img.rgba8.assign(file.begin() + static_cast<std::ptrdiff_t>(info.dataOffset), file.begin() + static_cast<std::ptrdiff_t>(info.dataOffset + info.dataBytes));
+            if (info.isBGRA) for (size_t i = 0; i < img.rgba8.size(); i += 4) std::swap(img.rgba8[i], img.rgba8[i + 2]);
+        }
+        else if (!decode_image(path, img, err)) { g_hostError = err; return 0; }
     }
     catch (const std::exception& e) { g_hostError = std::string("gfxh_scene_load_texture: ") + e.what(); return 0; }   // a bad_alloc from the decode buffers
     uint32_t slot = 0;
@@ -763,8 +888,14 @@ static uint32_t load_obj_impl(gfxh_scene* s, const char* path, int simplePbr) {
         {   // texture maps (createDiffuseAndSpecularMaterial, common_host.cpp:1560-1700): a map that cannot be read
             // leaves the immediate value in place
             gfx_material& m = s->materials[matSlot];
-            if (!d.mapKd.empty()) m.texA = gfxh_scene_load_texture(s, (dir + d.mapKd).c_str(), GFX_TEX_RGBA8_SRGB);
-            if (!d.mapKs.empty()) m.texB = gfxh_scene_load_texture(s, (dir + d.mapKs).c_str(), simplePbr ? GFX_TEX_RGBA8_UNORM : GFX_TEX_RGBA8_SRGB);
+            // needsDegamma of a colour map: true for every file stb_image reads (common_host.cpp:1223), but for a .dds it is what
+            // translate derives from the file's format -- only the _SRGB DXGI formats (:766-886, :1194); the sampler follows it (:1597-1606)
+            gfxh_dds_info dds;
+            auto colour_format = [&](const std::string& file) {
+                return dds_map_info(dir + file, dds) && !dds.isSRGB ? GFX_TEX_RGBA8_UNORM : GFX_TEX_RGBA8_SRGB;
+            };
+            if (!d.mapKd.empty()) m.texA = gfxh_scene_load_texture(s, (dir + d.mapKd).c_str(), colour_format(d.mapKd));
+            if (!d.mapKs.empty()) m.texB = gfxh_scene_load_texture(s, (dir + d.mapKs).c_str(), simplePbr ? GFX_TEX_RGBA8_UNORM : colour_format(d.mapKs));
             if (simplePbr) {
                 // MaterialConvention::SimplePBR (common_host.cpp:2323-2334, createSimplePBRMaterial :1689-1760): the diffuse slot
                 // holds base colour (+ opacity) behind the sRGB sampler, the specular slot (occlusion, roughness, metallic) behind
@@ -774,9 +905,19 @@ static uint32_t load_obj_impl(gfxh_scene* s, const char* path, int simplePbr) {
                 m.smoothness = 0.0f;
             }
             const std::string& nmap = !d.mapBump.empty() ? d.mapBump : d.mapNormal;   // TEXTURE_HEIGHT first, then TEXTURE_NORMALS (:2278-2282)
-            if (!nmap.empty()) { m.texNormal = gfxh_scene_load_texture(s, (dir + nmap).c_str(), GFX_TEX_RGBA8_UNORM); m.bumpMapType = GFX_BUMP_NORMAL_MAP; }
+            if (!nmap.empty()) {
+                // getBumpMapType (common_host.cpp:890-904) picks the bump reader from the block format of a .dds map: BC1 / BC2 / BC3 /
+                // BC7 -> normal map, BC4 -> height map, BC5 -> two-channel normal map; every other file is a three-channel normal map
+                uint32_t format8 = GFX_TEX_RGBA8_UNORM, bumpType = GFX_BUMP_NORMAL_MAP;
+                if (dds_map_info(dir + nmap, dds) && dds.isBlockCompressed) {
+                    if (dds.bcFormat == GFX_BC4_UNORM || dds.bcFormat == GFX_BC4_SNORM) { format8 = GFX_TEX_R8_UNORM; bumpType = GFX_BUMP_HEIGHT_MAP; }
+                    else if (dds.bcFormat == GFX_BC5_UNORM || dds.bcFormat == GFX_BC5_SNORM) { format8 = GFX_TEX_RG8_UNORM; bumpType = GFX_BUMP_NORMAL_MAP_2CH; }
+                }
+                m.texNormal = gfxh_scene_load_texture(s, (dir + nmap).c_str(), format8);
+                m.bumpMapType = bumpType;
+            }
             if (!d.mapKe.empty()) {
-                m.texEmittance = gfxh_scene_load_texture(s, (dir + d.mapKe).c_str(), GFX_TEX_RGBA8_SRGB);
+                m.texEmittance = gfxh_scene_load_texture(s, (dir + d.mapKe).c_str(), colour_format(d.mapKe));
                 if (m.texEmittance) m.hasEmittance = 1u;
             }
         }
@@ -1233,7 +1374,8 @@ int gfxh_scene_bounds(gfxh_scene* s, float bounds[6]) {
 int gfxh_scene_upload(gfxh_scene* s, gfx_ctx* ctx) {
     for (uint32_t t = 0; t < s->textures.size(); ++t) {
         const Tex& tx = s->textures[t];
-        if (gfx_texture_set(ctx, t + 1, tx.width, tx.height, tx.format, tx.texels.data())) { g_hostError = gfx_last_error(ctx); return 1; }
+        if (tx.isBc ? gfx_texture_set_bc(ctx, t + 1, tx.width, tx.height, tx.bcFormat, tx.blocks.data(), tx.format)
+                    : gfx_texture_set(ctx, t + 1, tx.width, tx.height, tx.format, tx.texels.data())) { g_hostError = gfx_last_error(ctx); return 1; }
     }
     for (uint32_t i = 0; i < s->materials.size(); ++i)
         if (gfx_material_set(ctx, i, &s->materials[i])) { g_hostError = gfx_last_error(ctx); return 1; }

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstring>
 #include "internal.h"
+#include "bc/bc_textures.h"
 #include <cstdlib>
 #include <map>
 #include <array>
@@ -285,25 +286,39 @@ void scene_upload(Context& ctx, hipStream_t stream) {
 
     {   // textures: descriptor table + one texel pool (every texture 16-byte aligned) + the sRGB decode table
         std::vector<DevTexture> descs(std::max<size_t>(ctx.textures.size(), 1));
-        std::vector<uint32_t> pool;
+        std::vector<uint32_t> pool;            // the uncompressed textures, staged on the host
+        std::vector<uint32_t> bcSlots;         // block-compressed slots: a region behind them, reserved on the device only
         for (size_t t = 0; t < ctx.textures.size(); ++t) {
             const HostTexture& ht = ctx.textures[t];
             DevTexture& d = descs[t];
             d.offset = static_cast<uint32_t>(pool.size()); d.width = ht.width; d.height = ht.height; d.format = ht.format;
+            if (ht.width != 0 && bc_texture_is(ctx, static_cast<uint32_t>(t))) { bcSlots.push_back(static_cast<uint32_t>(t)); continue; }
             const size_t words = (ht.texels.size() + 3) / 4;
             const size_t at = pool.size();
             pool.resize(at + ((words + 3) & ~size_t(3)), 0u);
             if (!ht.texels.empty()) std::memcpy(pool.data() + at, ht.texels.data(), ht.texels.size());
         }
         if (pool.empty()) pool.resize(4, 0u);
-        if (pool.size() >= (1ull << 32)) throw HipError("gfx: texel pool exceeds 16 GiB");
+        size_t poolWords = pool.size();
+        for (uint32_t t : bcSlots) {
+            const HostTexture& ht = ctx.textures[t];
+            const size_t bpp = ht.format == GFX_TEX_R8_UNORM ? 1 : (ht.format == GFX_TEX_RG8_UNORM ? 2 : 4);
+            const size_t words = (bpp * ht.width * ht.height + 3) / 4;
+            if (poolWords >= (1ull << 32)) throw HipError("gfx: texel pool exceeds 16 GiB");
+            descs[t].offset = static_cast<uint32_t>(poolWords);
+            poolWords += (words + 3) & ~size_t(3);
+        }
+        if (poolWords >= (1ull << 32)) throw HipError("gfx: texel pool exceeds 16 GiB");
         float lut[256];
         for (int c = 0; c < 256; ++c) {   // sampler_sRGB: degamma of c / 255 (basic_types.h:5396-5402), fp32
             const float v = static_cast<float>(c) / 255.0f;
             lut[c] = v <= 0.04045f ? v / 12.92f : std::pow((v + 0.055f) / 1.055f, 2.4f);
         }
         upload(ctx.dTextures, descs, stream);
-        upload(ctx.dTexelPool, pool, stream);
+        ctx.dTexelPool.reserve(sizeof(uint32_t) * poolWords);
+        GFX_HIP(hipMemcpyAsync(ctx.dTexelPool.p, pool.data(), sizeof(uint32_t) * pool.size(), hipMemcpyHostToDevice, stream));
+        for (uint32_t t : bcSlots)   // behind the pool copy, on the same stream: blocks already resident -> texels, on the device
+            bc_texture_expand(ctx, stream, t, descs[t].width, descs[t].height, descs[t].format, ctx.dTexelPool.as<uint32_t>() + descs[t].offset);
         ctx.dSrgbLut.reserve(sizeof(lut));
         GFX_HIP(hipMemcpyAsync(ctx.dSrgbLut.p, lut, sizeof(lut), hipMemcpyHostToDevice, stream));
         GFX_HIP(hipStreamSynchronize(stream));

@@ -82,6 +82,19 @@ enum gfx_tex_format {
     GFX_TEX_RGBA32F = 4       /* float RGBA, sampler_float (HDR emittance) */
 };
 
+/* Block-compressed formats gfx_texture_set_bc takes (the BC array types of translate, common/common_host.cpp:766-886).
+ * The _sRGB DXGI variants hold the same blocks: sRGB is a property of the gfx_tex_format the slot is sampled as. */
+enum gfx_bc_format {
+    GFX_BC1 = 0,              /* 8-byte blocks: RGB565 endpoints, 4- or 3-colour + transparent palette */
+    GFX_BC2 = 1,              /* 16 bytes: 4-bit alpha + BC1 colour (always four-colour) */
+    GFX_BC3 = 2,              /* 16 bytes: interpolated alpha + BC1 colour (always four-colour) */
+    GFX_BC4_UNORM = 3,        /* 8 bytes: one interpolated channel, decoded as (v, v, v, 255) */
+    GFX_BC4_SNORM = 4,        /*   signed endpoints, remapped from [-127, 127] to [0, 255] */
+    GFX_BC5_UNORM = 5,        /* 16 bytes: two interpolated channels, decoded as (x, y, 0, 255) */
+    GFX_BC5_SNORM = 6,
+    GFX_BC7 = 7               /* 16 bytes: the eight modes of the format; the reserved mode decodes to (0, 0, 0, 0) */
+};
+
 /* restir_di/restir_di_shared.h:182-204 -- same element structs, row-major linear arrays. */
 typedef struct gfx_gbuffer0 { uint32_t instSlot, geomInstSlot, primIndex; uint16_t qbcB, qbcC; } gfx_gbuffer0;
 typedef struct gfx_gbuffer1 { float motionVector[2]; } gfx_gbuffer1;
@@ -136,6 +149,18 @@ int gfx_texture_set(gfx_ctx* ctx, uint32_t texSlot, uint32_t width, uint32_t hei
 /* Inspection: tex2DLod<float4> (gather = 0) or tex2Dgather<float4> of component 0 (gather = 1) of one texture at n
  * coordinates; dUv = device float2[n], dOut = device float4[n].  Runs the functions the shading kernels call. */
 int gfx_texture_sample(gfx_ctx* ctx, void* stream, uint32_t texSlot, const void* dUv, uint32_t n, void* dOut, int gather);
+/* Block-compressed upload (the .dds branch of loadTexture, common/common_host.cpp:1163-1244, where the reference writes the blocks
+ * into a BC array and the texture unit decodes them).  blocks = ceil(width / 4) * ceil(height / 4) blocks of `bcFormat`
+ * (enum gfx_bc_format), row-major, tightly packed: level 0 of a DDS as it lies in the file.  `format` is the 8-bit gfx_tex_format
+ * the slot is sampled as (GFX_TEX_RGBA32F is refused); R8 / RG8 keep the first one / two channels of the decoded RGBA8 texel.
+ * The blocks are copied to the device here and expanded there at every scene upload, so the slot renders bit for bit like the
+ * same texels given to gfx_texture_set; the decoded bytes are those of tools/dds_convert.py.
+ * Same slot and size rules as gfx_texture_set; setting a slot again, by either call, replaces it.  A refused call leaves the
+ * slot as it was. */
+int gfx_texture_set_bc(gfx_ctx* ctx, uint32_t texSlot, uint32_t width, uint32_t height, uint32_t bcFormat, const void* blocks, uint32_t format);
+/* Inspection: the texels of a slot as they lie in the device pool, in the slot's format (tightly packed rows); `bytes` must be
+ * the slot's size exactly.  Uploads the scene first if it is dirty; works for uncompressed and block-compressed slots alike. */
+int gfx_texture_read(gfx_ctx* ctx, void* stream, uint32_t texSlot, void* hostOut, size_t bytes);
 
 /* common/common_host.cpp:1817-1905 createGeometryInstance: host vertex/triangle arrays in,
  * geomInstSlot out.  `vertexStride` >= sizeof(gfx_vertex). */
@@ -684,6 +709,10 @@ int gfx_pt_diag_read(gfx_ctx* ctx, uint64_t diag[8], int reset);
  * `stream`; dDst == NULL makes it a read-only pass over dSrc.  bench.py times both with HIP events for roofline.peak_measured /
  * peak_measured_read_only; no renderer calls it. */
 int gfx_stream_copy(gfx_ctx* ctx, void* dDst, const void* dSrc, size_t bytes, void* stream);
+/* Measurement utility: the expansion gfx_texture_set_bc slots go through at scene upload, on caller-owned device memory and on
+ * `stream`: dBlocks (16-byte aligned) -> dTexels (16-byte aligned, width * height texels of the 8-bit `format`, rows tightly
+ * packed).  tools/bench_bc_expand.py times it with HIP events; no renderer calls it. */
+int gfx_bc_expand(gfx_ctx* ctx, void* stream, uint32_t bcFormat, const void* dBlocks, uint32_t width, uint32_t height, uint32_t format, void* dTexels);
 
 #ifdef __cplusplus
 }

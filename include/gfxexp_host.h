@@ -34,14 +34,39 @@ uint32_t gfxh_scene_add_material_traditional(gfxh_scene* s, const float diffuse[
 uint32_t gfxh_scene_add_material(gfxh_scene* s, const gfx_material* m);
 
 /* Textures.  Slots are 1-based (0 = "no texture" in gfx_material).  gfxh_scene_load_texture is loadTexture
- * (common_host.cpp:1163-1244) for the formats this build decodes itself -- binary PPM / PGM, PFM, uncompressed BMP and
- * TGA; DDS / PNG / JPEG assets are converted offline -- cached per path: 8-bit images are stored as `format8`
- * (GFX_TEX_RGBA8_SRGB for colour maps, GFX_TEX_RGBA8_UNORM for normal maps, GFX_TEX_R8_UNORM / RG8 take the first
- * channels), float images as GFX_TEX_RGBA32F.  Both return the slot, 0 on failure. */
+ * (common_host.cpp:1163-1244) for the formats this build reads itself -- binary PPM / PGM, PFM, uncompressed BMP and
+ * TGA, and .dds / .DDS (level 0; the reference samples level 0 only, common_device.cuh:143-147); PNG / JPEG assets are
+ * converted offline -- cached per path: 8-bit images are stored as `format8` (GFX_TEX_RGBA8_SRGB for colour maps,
+ * GFX_TEX_RGBA8_UNORM for normal maps, GFX_TEX_R8_UNORM / RG8 take the first channels), float images as GFX_TEX_RGBA32F.
+ * A block-compressed .dds stays blocks (gfxh_scene_add_texture_bc) and is sampled as `format8`; an uncompressed RGBA8 /
+ * BGRA8 .dds becomes an ordinary texture.  All three return the slot, 0 on failure. */
 uint32_t gfxh_scene_add_texture(gfxh_scene* s, uint32_t width, uint32_t height, uint32_t format, const void* texels);
 uint32_t gfxh_scene_load_texture(gfxh_scene* s, const char* path, uint32_t format8);
 uint32_t gfxh_scene_num_textures(gfxh_scene* s);
+/* For a block-compressed texture: its extent, the 8-bit format it is sampled as, and *texels = NULL. */
 int gfxh_scene_get_texture(gfxh_scene* s, uint32_t slot, uint32_t* width, uint32_t* height, uint32_t* format, const void** texels);
+/* A texture held as blocks (gfx_texture_set_bc: ceil(width / 4) * ceil(height / 4) blocks of `bcFormat`, row-major, tightly
+ * packed), sampled as the 8-bit `format`.  gfxh_scene_upload hands the blocks to gfx_texture_set_bc; nothing is decoded here. */
+uint32_t gfxh_scene_add_texture_bc(gfxh_scene* s, uint32_t width, uint32_t height, uint32_t bcFormat, const void* blocks, uint32_t format);
+/* The blocks of a block-compressed texture; *blocks = NULL, *bytes = 0 and *bcFormat untouched for an uncompressed one. */
+int gfxh_scene_get_texture_bc(gfxh_scene* s, uint32_t slot, uint32_t* bcFormat, const void** blocks, size_t* bytes);
+
+/* Header of a .dds file (dds::load, common/dds_loader.cpp:207-346): the FourCC codes DXT1 / DXT3 / DXT5 / BC4U / ATI1 / BC4S /
+ * ATI2 / BC5U / BC5S, the DX10 extension with the DXGI formats of BC1-BC5, BC7, R8G8B8A8 and B8G8R8A8 (typeless, UNORM, _SRGB),
+ * and the two uncompressed 32-bit mask layouts.  isSRGB follows translate (common_host.cpp:766-886): only the _SRGB DXGI
+ * formats.  dataOffset / dataBytes locate level 0 inside the file. */
+typedef struct gfxh_dds_info {
+    uint32_t width, height, mipCount;
+    uint32_t isBlockCompressed;   /* 1: bcFormat is an enum gfx_bc_format; 0: 32-bit texels, RGBA or (isBGRA) BGRA order */
+    uint32_t bcFormat;
+    uint32_t isBGRA;
+    uint32_t isSRGB;
+    uint32_t reserved;
+    uint64_t dataOffset, dataBytes;
+} gfxh_dds_info;
+/* Returns 1 with a gfxh_last_error that names the cause for: not a DDS, BC6H, cube maps / arrays / volumes, an unknown format,
+ * an extent of 0 or above 16384, a payload shorter than level 0 needs.  Never reads outside data[0, bytes). */
+int gfxh_dds_parse(const void* data, size_t bytes, gfxh_dds_info* info);
 
 /* Geometry / groups / instances (return slot indices). */
 uint32_t gfxh_scene_add_geom(gfxh_scene* s, const gfx_vertex* v, uint32_t nv, const uint32_t* tris, uint32_t nt, uint32_t matSlot);

@@ -1,10 +1,14 @@
 #!/usr/bin/env python
-"""Offline half of the texture path ("BC-decoded offline"): decodes a .dds file to an image the host loader reads.
+"""Reference decoder of the block-compressed texture path, and the offline PNG converter: decodes a .dds file to an image.
+
+The library reads .dds itself (gfxh_scene_load_texture, gfx_texture_set_bc: the blocks are expanded on the GPU by
+gfxexp_amd/csrc/bc/), and this file is what that decoder is held to, byte for byte (tests/test_bc_decode_cpu.py,
+tests/test_gpu_bc_textures.py); it is no longer the only way in.  It still converts a .dds offline where a plain image is wanted.
 
 The reference uploads block-compressed DDS textures as they are and lets the texture unit decode them (common/dds_loader.cpp:207-346 reads the
 header -- the classic FourCC codes DXT1 / DXT3 / DXT5 / BC4U / BC4S / ATI2 / BC5U / BC5S or the DX10 extension with a DXGI format -- and
 common/common_host.cpp:1163-1244 creates the CUDA array).  This build samples textures in software from uncompressed texels, so the blocks
-are decoded once, offline: BC1, BC2, BC3 (RGBA), BC4 (one channel), BC5 (two channels: tangent-space normal maps, z rebuilt by the
+are decoded once: BC1, BC2, BC3 (RGBA), BC4 (one channel), BC5 (two channels: tangent-space normal maps, z rebuilt by the
 2-channel reader of the renderer), BC7 (all eight modes) and the uncompressed 32-bit RGBA / BGRA layouts; BC6H (HDR) is not decoded.
 Output by extension: .tga (RGBA8, what `gfxh_scene_load_texture` reads with alpha), .ppm (RGB8), .pgm (first channel).
 sRGB variants decode to the same bytes (the loader applies the sRGB table according to how the material uses the texture).

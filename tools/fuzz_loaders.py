@@ -1,4 +1,4 @@
-"""Mutation fuzzing of the host loaders (gfxexp_amd/csrc/host/scene_builder.cpp: EXR / PFM / PNM / BMP / TGA decoders, OBJ + MTL parser) against
+"""Mutation fuzzing of the host loaders (gfxexp_amd/csrc/host/scene_builder.cpp: EXR / PFM / PNM / BMP / TGA decoders, the DDS parser, OBJ + MTL parser) against
 the ASan + UBSan build of the library's host code (tools/asan_cpu_suite.sh builds it and runs this).  Valid files are written here (the EXR
 writer of tests/test_exr_reader.py), then truncated, byte-flipped, given extreme 32-bit fields or spliced; a loader may refuse a file
 (GfxError) or load it -- a sanitizer report is the failure.  usage: fuzz_loaders.py [mutations per seed file, default 400]"""
@@ -25,6 +25,18 @@ seeds['a.bmp'] = b"BM" + struct.pack("<IHHI", 54 + stride * h, 0, 0, 54) + struc
 seeds['b.bmp'] = b"BM" + struct.pack("<IHHI", 54 + 4 * w * h, 0, 0, 54) + struct.pack("<IiiHHIIiiII", 40, w, -h, 1, 32, 3, 4 * w * h, 0, 0, 0, 0) + bytes(4 * w * h)
 seeds['a.tga'] = bytes([0, 0, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0]) + struct.pack("<HH", w, h) + bytes([24, 0x20]) + bytes(3 * w * h)
 seeds['b.tga'] = bytes([3, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0]) + struct.pack("<HH", w, h) + bytes([8, 0]) + b"abc" + bytes(w * h)
+def _dds(fourcc, dxgi, dw, dh, payload, mips=1):
+    hdr = bytearray(128)
+    hdr[:4] = b"DDS "
+    struct.pack_into("<II", hdr, 4, 124, 0x1007 | (0x20000 if mips > 1 else 0))
+    struct.pack_into("<II", hdr, 12, dh, dw)
+    struct.pack_into("<I", hdr, 28, mips)
+    struct.pack_into("<II4s", hdr, 76, 32, 0x4, fourcc)
+    return bytes(hdr) + (struct.pack("<IIIII", dxgi, 3, 0, 1, 0) if fourcc == b"DX10" else b"") + payload
+seeds['a.dds'] = _dds(b"DX10", 99, w, h, nrng.integers(0, 256, 16 * 4 * 3, dtype=np.uint8).tobytes())                    # BC7 sRGB, partial blocks
+seeds['b.dds'] = _dds(b"DXT1", 0, 8, 8, nrng.integers(0, 256, 8 * (4 + 1 + 1 + 1), dtype=np.uint8).tobytes(), mips=4)    # legacy FourCC with a mip chain
+seeds['c.dds'] = _dds(b"DX10", 87, w, h, nrng.integers(0, 256, 4 * w * h, dtype=np.uint8).tobytes())                     # uncompressed BGRA8
+seeds['d.dds'] = _dds(b"ATI2", 0, w, h, nrng.integers(0, 256, 16 * 4 * 3, dtype=np.uint8).tobytes())                     # BC5
 obj = b"""mtllib m.mtl
 v 0 0 0\nv 1 0 0\nv 0 1 0\nv 1 1 0.5
 vt 0 0\nvt 1 0\nvt 0 1\nvt 1 1
@@ -32,13 +44,15 @@ vn 0 0 1\nvn 0 1 0
 usemtl a
 f 1/1/1 2/2/1 3/3/1
 f -1/-1/-1 2//2 3/3
+usemtl c
+f 1/1 2/2 3/3
 usemtl b
 f 1 2 3 4
 g grp
 s off
 f 2/2 4/4 3/3
 """
-mtl = b"""newmtl a\nKd 0.5 0.5 0.5\nKs 0.1 0.1 0.1\nNs 50\nKe 1 1 1\nmap_Kd a.ppm\nmap_Bump -bm 0.5 a.tga\nnewmtl b\nKd 1 0 0\nmap_Ke a.pfm\nmap_Ks b.bmp\n"""
+mtl = b"""newmtl a\nKd 0.5 0.5 0.5\nKs 0.1 0.1 0.1\nNs 50\nKe 1 1 1\nmap_Kd a.ppm\nmap_Bump -bm 0.5 a.tga\nnewmtl b\nKd 1 0 0\nmap_Ke a.pfm\nmap_Ks b.bmp\nnewmtl c\nKd 1 1 1\nmap_Kd a.dds\nmap_Ks b.dds\nmap_Ke c.dds\nmap_bump d.dds\n"""
 for n, d in seeds.items():
     open(os.path.join(tmp, n), 'wb').write(d)
 open(os.path.join(tmp, 'm.mtl'), 'wb').write(mtl)
@@ -71,6 +85,11 @@ for n, d in seeds.items():
             s.load_texture(p); ok += 1
         except api.GfxError:
             bad += 1
+        if n.endswith('.dds'):                                       # the parser on its own, on an exactly sized heap buffer
+            try:
+                api.dds_parse(open(p, 'rb').read())
+            except api.GfxError:
+                pass
 print('images: loaded', ok, 'refused', bad)
 ok = bad = 0
 s = api.HostScene(); s.load_obj(os.path.join(tmp, 's.obj'))
