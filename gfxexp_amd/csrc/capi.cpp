@@ -697,6 +697,7 @@ int gfx_tunable_set(gfx_ctx* ctx, const char* name, int value) {
     else if (n == "pt_regen_min") t.ptRegenMin = in(1, 64);
     else if (n == "fuse_passes") t.fusePasses = in(0, 2);
     else if (n == "block_order") t.blockOrder = in(0, 1);
+    else if (n == "candidate_prefilter") t.candidatePrefilter = in(0, 1);
     else if (n == "nrc_staged_infer") t.nrcStagedInfer = in(0, 3);
     else if (n == "candidate_split") { if (value == 3) throw HipError("gfx_tunable_set: candidate_split is 0 (automatic), 1, 2 or 4"); t.candidateSplit = in(0, 4); }
     else throw HipError("gfx_tunable_set: unknown tunable " + n);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "../../include/gfxexp.h"
 #include "emitter_spans.h"
+#include "emitter_cull.h"
 
 namespace gfx {
 
@@ -127,6 +128,7 @@ struct DevScene {
     const LightGeomRef* lightGeomRefs;   // indexed like the light pools (inst.distOffset + i)
     const EmitterRec* emitterRecs;
     const EmitterRecExtra* emitterRecExtras;   // parallel to emitterRecs
+    const EmitterCull* emitterCull;            // parallel to emitterRecs: the zero-weight pre-test of the candidate pass (emitter_cull.h)
     const float* lightNormalMatrices;          // [16 * matrix index]: the distinct normal matrices of the emitter instances, one 64-byte
                                                // item each (three float4 rows + padding); EmitterRec::flags holds the index
     uint32_t numLightMatrices;

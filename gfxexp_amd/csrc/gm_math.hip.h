@@ -30,11 +30,16 @@ static __device__ unsigned long long g_laneProfile[64];
 #define GFX_CYC_BEGIN unsigned long long cyc__[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }; unsigned long long cycT__ = __builtin_amdgcn_s_memtime(); int cycK__ = 7;
 #define GFX_CYC(k) do { const unsigned long long t__ = __builtin_amdgcn_s_memtime(); cyc__[cycK__] += t__ - cycT__; cycT__ = t__; cycK__ = (k); } while (0)
 #define GFX_CYC_END do { GFX_CYC(7); if ((threadIdx.x & 63) == 0) for (int k__ = 0; k__ < 8; ++k__) atomicAdd(&g_laneProfile[32 + k__], cyc__[k__]); } while (0)
+// a function called between GFX_CYC_BEGIN and GFX_CYC_END that sets marks of its own takes the bracket's state along
+#define GFX_CYC_PARAMS , unsigned long long (&cyc__)[8], unsigned long long& cycT__, int& cycK__
+#define GFX_CYC_ARGS , cyc__, cycT__, cycK__
 #else
 #define GFX_PROF(k) do { } while (0)
 #define GFX_CYC_BEGIN
 #define GFX_CYC(k) do { } while (0)
 #define GFX_CYC_END do { } while (0)
+#define GFX_CYC_PARAMS
+#define GFX_CYC_ARGS
 #endif
 
 constexpr float kPi = 3.14159265358979323846f;

@@ -95,6 +95,7 @@ struct Tunables {
     int traceBatch = 64;             // rays bought per device atomic (32 and 128 are slower)
     int temporalHints = 1;           // primary rays test the triangle their pixel hit one frame ago first (trace.hip)
     int candidateSplit = 0;          // k_initial_candidates: lanes per pixel (1, 2, 4); 0 = by launch size (restir.hip)
+    int candidatePrefilter = 1;      // k_initial_candidates with one lane per pixel: prove zero-weight candidates zero before their record is fetched (emitter_cull.h); 0 = lockstep loop
     int blockOrder = 1;              // k_initial_fused: blocks start by decreasing cost of one frame ago (restir.hip k_order_blocks); 0 = index order
     int fusePasses = 0;              // ReSTIR ray passes as one kernel each (restir.hip k_*_fused): 0 = small launches only, 1 never, 2 always
     int nrcStagedInfer = 0;          // k_nrc_infer_staged (hash-grid levels through LDS): 0 = large batches only, 1 never, 2 always, 3 always in the software-pipelined form k_nrc_infer_piped (nrc.hip)
@@ -123,7 +124,7 @@ struct Context {
     std::vector<HostInstance> insts;
     bool sceneDirty = true;
     // scene (device)
-    DevBuf dMaterials, dGeomInsts, dInsts, dVertices, dTriangles, dSlotPool, dFlatGeoms, dLightW, dLightP, dLightCDF, dLightRefs, dEmitterRecs, dEmitterRecExtras, dLightNormalMatrices, dInstMatrixIndex, dTextures, dTexelPool, dSrgbLut, dEmitterTexRefs;
+    DevBuf dMaterials, dGeomInsts, dInsts, dVertices, dTriangles, dSlotPool, dFlatGeoms, dLightW, dLightP, dLightCDF, dLightRefs, dEmitterRecs, dEmitterRecExtras, dEmitterCull, dLightNormalMatrices, dInstMatrixIndex, dTextures, dTexelPool, dSrgbLut, dEmitterTexRefs;
     bool anyEmittanceTexture = false;
     std::vector<LightGeomRef> hLightRefs;
     uint32_t numEmitterRecs = 0;

@@ -89,13 +89,17 @@ __global__ void k_inst_geom_dists(DevInstance* __restrict__ insts, uint32_t numI
 // pre-transform the emitter triangles (EmitterRec, device_types.h).  One block per instance.
 __global__ void k_emitter_records(DevScene sc, uint32_t numInsts, LightGeomRef* __restrict__ refs, EmitterRec* __restrict__ recs,
                                   EmitterRecExtra* __restrict__ extras, const uint32_t* __restrict__ instMatrixIndex,
-                                  EmitterTexRef* __restrict__ texRefs /* null: no emittance textures in the scene */) {
+                                  EmitterTexRef* __restrict__ texRefs /* null: no emittance textures in the scene */,
+                                  EmitterCull* __restrict__ cull) {
     const uint32_t ii = blockIdx.x;
     if (ii >= numInsts) return;
     const DevInstance* inst = sc.insts + ii;
     if (inst->distOffset == 0xFFFFFFFFu) return;
     const uint32_t matrixBits = (instMatrixIndex[ii] & kEmitterMatrixMask) << kEmitterMatrixShift;
     const m34 xfm = load_m34(inst->transform);
+    float normalMatrix[9];   // the rows light_from_record multiplies the interpolated normal by
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) normalMatrix[3 * r + c] = sc.lightNormalMatrices[16u * (instMatrixIndex[ii] & kEmitterMatrixMask) + 4u * r + c];
     for (uint32_t k = 0; k < inst->numGeomInsts; ++k) {
         const DevGeomInst g = sc.geomInsts[sc.geomInstSlotPool[inst->slotsOffset + k]];
         LightGeomRef* ref = refs + inst->distOffset + k;
@@ -134,6 +138,10 @@ __global__ void k_emitter_records(DevScene sc, uint32_t numInsts, LightGeomRef* 
             float4* dstX = reinterpret_cast<float4*>(extras + recBase + t);
             const float4* srcX = reinterpret_cast<const float4*>(&x);
             dstX[0] = srcX[0]; dstX[1] = srcX[1];
+            // the zero-weight pre-test of the candidate pass (emitter_cull.h): rebuilt with the record, so it follows a moving emitter
+            const bool finiteEmittance = is_finite(e.x) && is_finite(e.y) && is_finite(e.z);
+            const EmitterCull ce = cull_build(normalMatrix, r.nA, !smooth, r.pA, r.pB, r.pC, finiteEmittance);
+            *reinterpret_cast<uint4*>(cull + recBase + t) = make_uint4(ce.octN, f2bits(ce.hLo), ce.cxy, ce.czr);
             if (texRefs) {
                 EmitterTexRef tr;
                 tr.uvA[0] = vA.u; tr.uvA[1] = vA.v; tr.uvB[0] = vB.u; tr.uvB[1] = vB.v; tr.uvC[0] = vC.u; tr.uvC[1] = vC.v;
@@ -368,7 +376,7 @@ void lights_build_static(Context& ctx, hipStream_t stream) {
     if (ni)
         hipLaunchKernelGGL(k_emitter_records, dim3(ni), dim3(64), 0, stream, ctx.devScene(), ni,
                            ctx.dLightRefs.as<LightGeomRef>(), ctx.dEmitterRecs.as<EmitterRec>(), ctx.dEmitterRecExtras.as<EmitterRecExtra>(), ctx.dInstMatrixIndex.as<uint32_t>(),
-                               ctx.anyEmittanceTexture ? ctx.dEmitterTexRefs.as<EmitterTexRef>() : nullptr);
+                               ctx.anyEmittanceTexture ? ctx.dEmitterTexRefs.as<EmitterTexRef>() : nullptr, ctx.dEmitterCull.as<EmitterCull>());
     GFX_HIP(hipGetLastError());
     // keep the host mirrors of the integrals current (read by gfx_lights_read and the launch params)
     GFX_HIP(hipMemcpyAsync(ctx.hGeomInsts.data(), ctx.dGeomInsts.p, sizeof(DevGeomInst) * ng, hipMemcpyDeviceToHost, stream));
@@ -387,7 +395,7 @@ void lights_build_instances(Context& ctx, hipStream_t stream, uint32_t /*bufferI
         if (numInsts)
             hipLaunchKernelGGL(k_emitter_records, dim3(numInsts), dim3(64), 0, stream, ctx.devScene(), numInsts,
                                ctx.dLightRefs.as<LightGeomRef>(), ctx.dEmitterRecs.as<EmitterRec>(), ctx.dEmitterRecExtras.as<EmitterRecExtra>(), ctx.dInstMatrixIndex.as<uint32_t>(),
-                               ctx.anyEmittanceTexture ? ctx.dEmitterTexRefs.as<EmitterTexRef>() : nullptr);
+                               ctx.anyEmittanceTexture ? ctx.dEmitterTexRefs.as<EmitterTexRef>() : nullptr, ctx.dEmitterCull.as<EmitterCull>());
         GFX_HIP(hipGetLastError());
         ctx.emitterRecsDirty = false;
     }

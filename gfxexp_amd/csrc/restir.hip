@@ -220,13 +220,125 @@ GFX_DEV PixelId pixel_of_split_thread(const PixelGrid& g, uint32_t& sub, uint32_
     sub = launchThread & (SPLIT - 1);
     return pixel_of_block_thread(g, (launchThread / SPLIT) / kBlock, (launchThread / SPLIT) % kBlock);
 }
+// Jump of the pixel's PCG32 stream to candidate k of a chunk (every candidate owns four draws); [32] = past a full chunk.
+struct CandidateJumps { LcgJump j[33]; };
+constexpr CandidateJumps make_candidate_jumps() {
+    CandidateJumps t = {};
+    for (uint32_t k = 0; k <= 32u; ++k) t.j[k] = lcg_jump(4u * k);
+    return t;
+}
+__constant__ const CandidateJumps kCandidateJumps = make_candidate_jumps();
+
+// Which light type candidate i samples, and ul remapped for the selection inside it (optix_restir_di_kernels.cu:66-84).
+GFX_DEV void candidate_light_type(const RestirArgs& a, bool envEnabled, uint32_t numCandidates, uint32_t i, float& ul, float& probCurType, bool& sampleEnv) {
+    probCurType = 1.0f; sampleEnv = false;
+    if (envEnabled) {
+        if (*a.scene.lightInstIntegral > 0.0f) {
+            const float prob = fmin2(fmax2(0.25f * numCandidates - i, 0.0f), 1.0f);
+            // prob is 0 or 1 for every candidate count >= 4: x / 1 and (x - 0) / (1 - 0) are x, no division needed
+            if (prob == 1.0f) { probCurType = 0.25f; sampleEnv = true; }
+            else if (prob == 0.0f) probCurType = 1.0f - 0.25f;
+            else if (ul < prob) { probCurType = 0.25f; ul = ul / prob; sampleEnv = true; }
+            else { probCurType = 1.0f - 0.25f; ul = (ul - prob) / (1 - prob); }
+        }
+        else sampleEnv = true;
+    }
+}
+
+// One candidate: its first three draws out of rng, the light sample, target and weight (the fourth draw is the caller's).
+// EVERY lane of the wave must call; lanes with active = false take part in the cooperative record fetch and in nothing else.
+template <bool EMITTER_TEX>
+GFX_DEV void candidate_eval(const RestirArgs& a, uint4* waveBuf, int lane, const EnvMap& env, bool envEnabled, const ShadingPoint& sp,
+                            bool active, uint32_t numCandidates, uint32_t i, Pcg32& rng, LightSample& ls, float& target, float& weight GFX_CYC_PARAMS) {
+    GFX_PROF(0);
+    GFX_CYC(0);   // random numbers, light type, table lookup
+    // ---- what this lane's candidate needs from the tables
+    float probCurType = 1.0f, u0 = 0.0f, u1 = 0.0f;
+    bool sampleEnv = false;
+    LightPick pk; pk.rec = 0; pk.instSlot = 0; pk.density = 0.0f; pk.partialProb = 0.0f; pk.ok = false; pk.table = true;
+    if (active) {
+        float ul = rng.uniform();
+        candidate_light_type(a, envEnabled, numCandidates, i, ul, probCurType, sampleEnv);
+        u0 = rng.uniform();
+        u1 = rng.uniform();
+        if (!sampleEnv) pk = light_select(a.scene, ul);
+    }
+    // ---- the wave gathers the records, then -- their flags name them -- the normal matrices
+    GFX_CYC(1);   // cooperative record fetch (issue, wait, read back), matrix loads issued
+    const bool fetch = active && !sampleEnv && pk.ok;
+    uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0, q2 = q0, q3 = q0;
+    m33 normalMatrix;
+    normalMatrix.r0 = normalMatrix.r1 = normalMatrix.r2 = f3(0.0f);
+    if (__ballot(fetch) != 0ull) {
+        coop_fetch64_issue(fetch ? pk.rec : kCoopNone, reinterpret_cast<const char*>(a.scene.emitterRecs), waveBuf, lane);
+        coop_fetch64_wait();
+        if (fetch) coop_fetch64_read(waveBuf, lane, q0, q1, q2, q3);
+        // the matrix: three 16-byte loads per lane out of the deduplicated table.  Measured alternatives, all slower: a second
+        // cooperative round (+6 %: its wait cannot hide behind arithmetic the way these loads do); the table in LDS with one
+        // 16-wave block per CU (+5 %, 2 100 matrices: bank conflicts of the scattered reads and the coarser block granularity
+        // cost more than the saved L2 sector) -- profiles/r03_experiments.txt
+        if (fetch) normalMatrix = load_m33_rows(a.scene.lightNormalMatrices + 16u * emitter_matrix_index(q3.w));
+    }
+    // ---- the candidate itself
+    GFX_CYC(2);   // point on the emitter (waits for the matrix)
+    if (active) {
+        ls.emittance = f3(0.0f); ls.position = f3(0.0f); ls.normal = f3(0.0f); ls.atInfinity = 0;
+        float pd = 0.0f;
+        // the emittance texture of the candidate is read only when f * G is non-zero: a zero-weight candidate is
+        // never accepted by the reservoir, so its emittance is never observed (finite texels: 0 * Le = 0)
+        PendingEmittance pending; pending.tex = 0u; pending.rec = 0u; pending.bcA = pending.bcB = pending.bcC = 0.0f;
+        if (sampleEnv) sample_env_light(env, a.f.envLightRotation, a.f.envLightPowerCoeff, u0, u1, ls, pd);
+        else if (pk.ok) {
+            GFX_PROF(1);
+            light_from_record<EMITTER_TEX, false>(a.scene, pk, as_float4(q0), as_float4(q1), as_float4(q2), as_float4(q3), normalMatrix, u0, u1, ls, pd,
+                                                  f3(0.0f), EMITTER_TEX ? &pending : nullptr);
+        }
+        GFX_CYC(3);   // shadow-ray geometry, BSDF evaluation, emittance texture
+        const f3 cont = EMITTER_TEX ? direct_lighting_pending(a.scene, sp.pos, sp.vOutLocal, sp.frame, sp.bsdf, ls, pending)
+                                    : direct_lighting(sp.pos, sp.vOutLocal, sp.frame, sp.bsdf, ls);
+        GFX_CYC(4);   // reservoir update
+        pd *= probCurType;
+        target = target_weight(cont);
+        weight = target / pd;
+    }
+}
+
+// Phase A of the two-phase loop: is candidate i, whose first draw is ul, live?  Skipped -- proven to change nothing but
+// streamLength -- is a table pick of a record with a finite non-zero density whose cull entry proves the target zero
+// (emitter_cull.h).  Everything else is live: environment candidates, the search fallback, and a pick without a record, whose
+// 0 / 0 weight has to reach the sum at its place.
+// (Issuing the guide and cull-entry loads of four candidates together changed nothing, 1.03 ms either way: the pass is bound by
+// the L2s' sector rate, not by the latency of these loads -- profiles/r07_experiments.txt 1.)
+GFX_DEV bool candidate_live(const RestirArgs& a, bool envEnabled, const ShadingPoint& sp, uint32_t numCandidates, uint32_t i, float ul) {
+    float probCurType;
+    bool sampleEnv;
+    candidate_light_type(a, envEnabled, numCandidates, i, ul, probCurType, sampleEnv);
+    if (sampleEnv) return true;
+    const LightPick pk = light_select(a.scene, ul);
+    if (!pk.table || !pk.ok) return true;
+    const float pd = pk.density * probCurType;
+    if (!(pd != 0.0f && is_finite(pd))) return true;
+    const uint4 w = *reinterpret_cast<const uint4*>(a.scene.emitterCull + pk.rec);
+    EmitterCull e; e.octN = w.x; e.hLo = bits2f(w.y); e.cxy = w.z; e.czr = w.w;
+    return !cull_proves_zero(e, sp.pos.x, sp.pos.y, sp.pos.z, sp.frame.n.x, sp.frame.n.y, sp.frame.n.z, sp.vOutLocal.z);
+}
+
 // What the candidate loop leaves in registers: the visibility ray of the selected candidate (want: there is one), held by the lane
 // that wrote the pixel's reservoir (writer; with one lane per pixel every lane is one).
 struct CandidateRay { bool writer, want; f3 org, dir; float tmax; };
 // waveBuf: 256 x 16 B of LDS private to the wave (64 emitter records).  EVERY lane of the wave must call.
-template <bool EMITTER_TEX, int SPLIT>
+//
+// PREFILTER (one lane per pixel only): the loop runs in two phases per chunk of up to 32 candidates.  Phase A walks every
+// candidate's place in the pixel's random stream, looks its record up and asks the record's 16-byte cull entry whether the
+// target can be non-zero; the answers are one bit per candidate.  Phase B runs the full candidate -- cooperative fetch, point on
+// the emitter, BSDF, reservoir update -- once per set bit of the wave's fullest lane, each lane on its own lowest set bit, in
+// candidate order.  A skipped candidate would have added +-0 to the sum and lost every acceptance test (u < 0 / sum is false for
+// every sum), so the reservoir, the stream length (set after the loop) and the random state (jumped past the chunk) come out bit
+// for bit as from the lockstep loop.
+template <bool EMITTER_TEX, int SPLIT, bool PREFILTER = false>
 GFX_DEV CandidateRay initial_candidates(const RestirArgs& a, uint4* waveBuf, int lane, const PixelId& px, uint32_t sub) {
     static_assert(SPLIT == 1 || SPLIT == 2 || SPLIT == 4, "a pixel's lanes are an aligned pair or quad");
+    static_assert(!PREFILTER || SPLIT == 1, "the lanes of a split pixel add their weights in lockstep");
     const size_t numPixels = static_cast<size_t>(a.s.imageSizeX) * a.s.imageSizeY;
     const size_t p = px.p;
     const uint32_t bufIdx = a.f.bufferIndex;
@@ -257,72 +369,49 @@ GFX_DEV CandidateRay initial_candidates(const RestirArgs& a, uint4* waveBuf, int
     int lastAccepted = -1;               // SPLIT > 1: the last candidate this lane accepted
     const uint32_t numCandidates = 1u << a.f.log2NumCandidateSamples;
     GFX_CYC_BEGIN
-    for (uint32_t i = sub; i < numCandidates; i += SPLIT) {
-        GFX_PROF(0);
-        GFX_CYC(0);   // random numbers, light type, table lookup
-        // ---- what this lane's candidate needs from the tables
-        float probCurType = 1.0f, u0 = 0.0f, u1 = 0.0f;
-        bool sampleEnv = false;
-        LightPick pk; pk.rec = 0; pk.instSlot = 0; pk.density = 0.0f; pk.partialProb = 0.0f; pk.ok = false; pk.table = true;
-        if (surface) {
-            if (SPLIT > 1 && i >= SPLIT) {                // past the draws of the other lanes' candidates since this lane's last one
-                constexpr LcgJump skip = lcg_jump(4 * (SPLIT - 1));
-                rng.state = rng.state * skip.mul + skip.add;
-            }
-            float ul = rng.uniform();
-            if (envEnabled) {
-                if (*a.scene.lightInstIntegral > 0.0f) {
-                    const float prob = fmin2(fmax2(0.25f * numCandidates - i, 0.0f), 1.0f);
-                    // prob is 0 or 1 for every candidate count >= 4: x / 1 and (x - 0) / (1 - 0) are x, no division needed
-                    if (prob == 1.0f) { probCurType = 0.25f; sampleEnv = true; }
-                    else if (prob == 0.0f) probCurType = 1.0f - 0.25f;
-                    else if (ul < prob) { probCurType = 0.25f; ul = ul / prob; sampleEnv = true; }
-                    else { probCurType = 1.0f - 0.25f; ul = (ul - prob) / (1 - prob); }
+    if (PREFILTER) {
+        for (uint32_t base = 0; base < numCandidates; base += 32u) {
+            const uint32_t chunk = numCandidates - base < 32u ? numCandidates - base : 32u;
+            const uint64_t start = rng.state;
+            // ---- phase A: one bit per candidate that can have a non-zero weight
+            uint32_t live = 0u;
+            GFX_CYC(6);   // phase A: a draw, the table lookup and the cull entry per candidate
+            if (surface) {
+                Pcg32 walk; walk.state = start;
+                for (uint32_t k = 0; k < chunk; ++k) {
+                    const float ul = walk.uniform();
+                    constexpr LcgJump rest = lcg_jump(3);
+                    walk.state = walk.state * rest.mul + rest.add;
+                    if (candidate_live(a, envEnabled, sp, numCandidates, base + k, ul)) { GFX_PROF(6); live |= 1u << k; }
                 }
-                else sampleEnv = true;
             }
-            u0 = rng.uniform();
-            u1 = rng.uniform();
-            if (!sampleEnv) pk = light_select(a.scene, ul);
+            // ---- phase B: the live candidates, each lane in its own candidate order
+            while (__ballot(live != 0u) != 0ull) {
+                const bool active = live != 0u;
+                const uint32_t k = active ? static_cast<uint32_t>(__builtin_ctz(live)) : 0u;
+                live &= live - 1u;
+                const LcgJump jump = kCandidateJumps.j[k];
+                Pcg32 at; at.state = start * jump.mul + jump.add;
+                LightSample ls;
+                float target = 0.0f, weight = 0.0f;
+                candidate_eval<EMITTER_TEX>(a, waveBuf, lane, env, envEnabled, sp, active, numCandidates, base + k, at, ls, target, weight GFX_CYC_ARGS);
+                if (active && reservoir.update(ls, weight, at.uniform())) { GFX_PROF(5); selectedTarget = target; }
+            }
+            const LcgJump past = kCandidateJumps.j[chunk];
+            rng.state = start * past.mul + past.add;
         }
-        // ---- the wave gathers the records, then -- their flags name them -- the normal matrices
-        GFX_CYC(1);   // cooperative record fetch (issue, wait, read back), matrix loads issued
-        const bool fetch = surface && !sampleEnv && pk.ok;
-        uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0, q2 = q0, q3 = q0;
-        m33 normalMatrix;
-        normalMatrix.r0 = normalMatrix.r1 = normalMatrix.r2 = f3(0.0f);
-        if (__ballot(fetch) != 0ull) {
-            coop_fetch64_issue(fetch ? pk.rec : kCoopNone, reinterpret_cast<const char*>(a.scene.emitterRecs), waveBuf, lane);
-            coop_fetch64_wait();
-            if (fetch) coop_fetch64_read(waveBuf, lane, q0, q1, q2, q3);
-            // the matrix: three 16-byte loads per lane out of the deduplicated table.  Measured alternatives, all slower: a second
-            // cooperative round (+6 %: its wait cannot hide behind arithmetic the way these loads do); the table in LDS with one
-            // 16-wave block per CU (+5 %, 2 100 matrices: bank conflicts of the scattered reads and the coarser block granularity
-            // cost more than the saved L2 sector) -- profiles/r03_experiments.txt
-            if (fetch) normalMatrix = load_m33_rows(a.scene.lightNormalMatrices + 16u * emitter_matrix_index(q3.w));
+        reservoir.streamLength = numCandidates;
+    }
+    else
+    for (uint32_t i = sub; i < numCandidates; i += SPLIT) {
+        if (surface && SPLIT > 1 && i >= SPLIT) {         // past the draws of the other lanes' candidates since this lane's last one
+            constexpr LcgJump skip = lcg_jump(4 * (SPLIT - 1));
+            rng.state = rng.state * skip.mul + skip.add;
         }
-        // ---- the candidate itself
-        GFX_CYC(2);   // point on the emitter (waits for the matrix)
+        LightSample ls;
+        float target = 0.0f, weight = 0.0f;
+        candidate_eval<EMITTER_TEX>(a, waveBuf, lane, env, envEnabled, sp, surface, numCandidates, i, rng, ls, target, weight GFX_CYC_ARGS);
         if (surface) {
-            LightSample ls;
-            ls.emittance = f3(0.0f); ls.position = f3(0.0f); ls.normal = f3(0.0f); ls.atInfinity = 0;
-            float pd = 0.0f;
-            // the emittance texture of the candidate is read only when f * G is non-zero: a zero-weight candidate is
-            // never accepted by the reservoir, so its emittance is never observed (finite texels: 0 * Le = 0)
-            PendingEmittance pending; pending.tex = 0u; pending.rec = 0u; pending.bcA = pending.bcB = pending.bcC = 0.0f;
-            if (sampleEnv) sample_env_light(env, a.f.envLightRotation, a.f.envLightPowerCoeff, u0, u1, ls, pd);
-            else if (pk.ok) {
-                GFX_PROF(1);
-                light_from_record<EMITTER_TEX, false>(a.scene, pk, as_float4(q0), as_float4(q1), as_float4(q2), as_float4(q3), normalMatrix, u0, u1, ls, pd,
-                                                      f3(0.0f), EMITTER_TEX ? &pending : nullptr);
-            }
-            GFX_CYC(3);   // shadow-ray geometry, BSDF evaluation, emittance texture
-            const f3 cont = EMITTER_TEX ? direct_lighting_pending(a.scene, sp.pos, sp.vOutLocal, sp.frame, sp.bsdf, ls, pending)
-                                        : direct_lighting(sp.pos, sp.vOutLocal, sp.frame, sp.bsdf, ls);
-            GFX_CYC(4);   // reservoir update
-            pd *= probCurType;
-            const float target = target_weight(cont);
-            const float weight = target / pd;
             if (SPLIT == 1) {
                 if (reservoir.update(ls, weight, rng.uniform())) { GFX_PROF(5); selectedTarget = target; }
             }
@@ -369,7 +458,7 @@ GFX_DEV CandidateRay initial_candidates(const RestirArgs& a, uint4* waveBuf, int
     r.writer = writer; r.want = wantRay; r.org = rayO; r.dir = rayD; r.tmax = rayTmax;
     return r;
 }
-template <bool EMITTER_TEX, int SPLIT>
+template <bool EMITTER_TEX, int SPLIT, bool PREFILTER>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(GFX_INIT_WAVES, GFX_INIT_WAVES))) void k_initial_candidates(RestirArgs a, uint32_t* __restrict__ blockCost) {
     __shared__ __attribute__((aligned(16))) uint4 fetchBuf[(kBlock / 64) * 256];   // per wave: 256 x 16 B = 64 records
     const int lane = threadIdx.x & 63;
@@ -380,7 +469,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(GFX_INIT
     const unsigned long long t0 = blockCost ? __builtin_amdgcn_s_memtime() : 0ull;
     uint32_t sub;
     const PixelId px = pixel_of_split_thread<SPLIT>(a.px, sub, block);
-    const CandidateRay r = initial_candidates<EMITTER_TEX, SPLIT>(a, waveBuf, lane, px, sub);
+    const CandidateRay r = initial_candidates<EMITTER_TEX, SPLIT, PREFILTER>(a, waveBuf, lane, px, sub);
     if (r.writer) {
         const uint32_t slot = emit_ray_at_slot(px, r.want, r.org, r.dir, 0.0f, r.tmax, a);
         if (px.valid) a.pixelRaySlot[px.p] = slot;
@@ -1220,9 +1309,13 @@ void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, u
                 block_order_end(0, grid, cost);
                 break;
             }
+            // one lane per pixel: the two-phase loop that skips provably zero-weight candidates ("candidate_prefilter", emitter_cull.h)
+            const bool prefilter = ctx.tune.candidatePrefilter != 0;
             void (*kernel)(RestirArgs, uint32_t*) = a.scene.emitterTexRefs
-                ? (split == 4 ? k_initial_candidates<true, 4> : split == 2 ? k_initial_candidates<true, 2> : k_initial_candidates<true, 1>)
-                : (split == 4 ? k_initial_candidates<false, 4> : split == 2 ? k_initial_candidates<false, 2> : k_initial_candidates<false, 1>);
+                ? (split == 4 ? k_initial_candidates<true, 4, false> : split == 2 ? k_initial_candidates<true, 2, false>
+                   : prefilter ? k_initial_candidates<true, 1, true> : k_initial_candidates<true, 1, false>)
+                : (split == 4 ? k_initial_candidates<false, 4, false> : split == 2 ? k_initial_candidates<false, 2, false>
+                   : prefilter ? k_initial_candidates<false, 1, true> : k_initial_candidates<false, 1, false>);
             const uint32_t* order = nullptr;
             uint32_t* cost = nullptr;
             block_order_begin(3, grid, split, order, cost);

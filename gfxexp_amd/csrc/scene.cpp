@@ -13,7 +13,7 @@ namespace gfx {
 
 Context::~Context() {
     for (Accel* a : accels) { if (a) { a->nodes.release(); a->links.release(); a->triIds.release(); a->rootBoxes.release(); delete a; } }
-    DevBuf* all[] = { &dMaterials, &dGeomInsts, &dInsts, &dVertices, &dTriangles, &dSlotPool, &dFlatGeoms, &dSubset[0], &dSubset[1], &dLightW, &dLightP, &dLightCDF, &dLightRefs, &dEmitterRecs, &dEmitterRecExtras, &dLightNormalMatrices, &dInstMatrixIndex, &dTextures, &dTexelPool, &dSrgbLut, &dEmitterTexRefs,
+    DevBuf* all[] = { &dMaterials, &dGeomInsts, &dInsts, &dVertices, &dTriangles, &dSlotPool, &dFlatGeoms, &dSubset[0], &dSubset[1], &dLightW, &dLightP, &dLightCDF, &dLightRefs, &dEmitterRecs, &dEmitterRecExtras, &dEmitterCull, &dLightNormalMatrices, &dInstMatrixIndex, &dTextures, &dTexelPool, &dSrgbLut, &dEmitterTexRefs,
                       &rayOrg, &rayDir, &rayOut, &rayHits, &spill, &gbRayOrg, &gbRayDir, &gbRayHits, &gbSpill, &gbCounters, &auxSpill, &auxCounters, &blockOrders[0].cost, &blockOrders[0].order, &blockOrders[1].cost, &blockOrders[1].order, &blockOrders[2].cost, &blockOrders[2].order, &blockOrders[3].cost, &blockOrders[3].order, &blockOrders[4].cost, &blockOrders[4].order, &pixelRaySlot, &shadeScratch, &spatialScratch, &smallCounters,
                       &bTris, &bBoxes, &bKeys, &bKeysAlt, &bVals, &bValsAlt, &bSortTemp, &bNodesLR, &bParents, &bFlags,
                       &bNodeBoxes, &bRanges, &bQueueA, &bQueueB, &bCounters, &dTraceCounters, &dLightInstIntegral, &dLightInstGuide, &dSpans, &dSpanGuide, &dSpanHeader, &dSpanInstBegin,
@@ -44,6 +44,7 @@ DevScene Context::devScene() const {
     s.lightGeomRefs = dLightRefs.as<LightGeomRef>();
     s.emitterRecs = dEmitterRecs.as<EmitterRec>();
     s.emitterRecExtras = dEmitterRecExtras.as<EmitterRecExtra>();
+    s.emitterCull = dEmitterCull.as<EmitterCull>();
     s.lightNormalMatrices = dLightNormalMatrices.as<float>();
     s.numLightMatrices = numLightMatrices;
     s.lightInstIntegral = dLightInstIntegral.as<float>();
@@ -345,6 +346,7 @@ void scene_upload(Context& ctx, hipStream_t stream) {
     upload(ctx.dLightRefs, ctx.hLightRefs, stream);
     ctx.dEmitterRecs.reserve(std::max<size_t>(sizeof(EmitterRec) * ctx.numEmitterRecs, 16));
     ctx.dEmitterRecExtras.reserve(std::max<size_t>(sizeof(EmitterRecExtra) * ctx.numEmitterRecs, 16));
+    ctx.dEmitterCull.reserve(std::max<size_t>(sizeof(EmitterCull) * ctx.numEmitterRecs, 16));
     light_matrices_upload(ctx, stream);
     ctx.dEmitterTexRefs.reserve(std::max<size_t>(ctx.anyEmittanceTexture ? sizeof(EmitterTexRef) * ctx.numEmitterRecs : 0, 16));
     ctx.dLightW.reserve(std::max<size_t>(sizeof(float) * lightPool, 16));

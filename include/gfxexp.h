@@ -685,6 +685,10 @@ int gfx_timing_collect(gfx_ctx* ctx, char names[][48], float* totalMs, uint32_t*
  *                               pixel's candidates round robin and the reservoir is formed as the sequential loop forms it; 0 (default)
  *                               = by launch size: 4 when the launch fills the GPU's wave slots at most ~1.5 times (a row band of an
  *                               8-way split frame), else 1 (GFX_CANDIDATE_SPLIT)
+ *   "candidate_prefilter" 0|1   candidate loop with one lane per pixel as a kernel of its own (a full frame): 1 (default) walks the
+ *                               candidates twice -- first a conservative test on a 16-byte bound per emitter record (csrc/emitter_cull.h)
+ *                               that proves about four candidates in five to have a weight of exactly zero, then the full candidate for
+ *                               the rest only; 0 evaluates every candidate in lockstep.  Same reservoirs, same random streams.
  *   "nrc_staged_infer" 0|1|2    gfx_nrc_infer with the hash-grid encoding: 0 (default) a batch that gives every CU at least one pass of 3 072 queries is
  *                               encoded level by level out of LDS copies of the level tables (one persistent block per CU; same predictions bit for
  *                               bit), smaller batches gather from the tables in place; 1 never, 2 always (GFX_NRC_STAGED_INFER)

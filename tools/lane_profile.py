@@ -13,12 +13,13 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
-SECTIONS = {0: "candidate loop body (RNG, light selection, fetch, shadow-ray geometry, reservoir update)",
+SECTIONS = {0: "candidate loop body (RNG, light selection, fetch, shadow-ray geometry, reservoir update); two-phase loop: once per phase-B iteration",
             1: "light_fetch (record + normal matrix gathers, point on the triangle)",
             2: "emitter faces the shading point (lpCos > 0): BSDF evaluate is called",
             3: "BSDF evaluate past the horizon test (GGX D / G / Fresnel, diffuse lobe)",
             4: "deferred emittance-texture read",
             5: "reservoir accepts the candidate (sample copy)",
+            6: "phase A of the two-phase loop: the candidate is live (lanes = set bits, visits = (wave, candidate) pairs with one)",
             7: "smooth-emitter / fallback extra record",
             8: "after the loop (finalise, shadow ray)"}
 
@@ -61,7 +62,7 @@ def main():
     # where the waves' clock cycles went (GFX_CYC marks in k_initial_candidates; wave-level s_memtime)
     names = {0: "random numbers, light type, table lookup", 1: "cooperative record fetch (issue, wait, read back), matrix loads issued",
              2: "point on the emitter (waits for the matrix)", 3: "shadow-ray geometry, BSDF evaluation, emittance texture", 4: "reservoir update",
-             5: "after the loop", 7: "before the loop"}
+             5: "after the loop", 6: "phase A (draw, table lookup, cull entry per candidate)", 7: "before the loop"}
     cyc = {k: int(out[32 + k]) for k in names}
     total = max(1, sum(cyc.values()))
     print(json.dumps({"workload": "textured" if textured else "plain", "sections": res,
