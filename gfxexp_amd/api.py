@@ -211,7 +211,8 @@ def abi_mirrors():
             "gfxh_exchange_buffer": GfxhExchangeBuffer, "gfxh_exchange_desc": GfxhExchangeDesc, "gfxh_band_plan": GfxhBandPlan,
             "gfxh_nrc_config": GfxhNrcConfig, "gfxh_sdr_config": GfxhSdrConfig,
             "gfx_denoiser_settings": GfxDenoiserSettings, "gfx_denoiser_inputs": GfxDenoiserInputs,
-            "gfx_denoiser_history_buffers": GfxDenoiserHistoryBuffers, "gfx_taa_inputs": GfxTaaInputs, "gfxh_dds_info": GfxhDdsInfo}
+            "gfx_denoiser_history_buffers": GfxDenoiserHistoryBuffers, "gfx_taa_inputs": GfxTaaInputs, "gfxh_dds_info": GfxhDdsInfo,
+            "gfxh_image_desc": GfxhImageDesc}
 
 
 class RcclExchange:
@@ -329,7 +330,7 @@ C_ABI_SYMBOLS = [
 ]
 HOST_ABI_SYMBOLS = [
     "gfxh_scene_create", "gfxh_scene_destroy", "gfxh_last_error", "gfxh_scene_add_material_traditional",
-    "gfxh_scene_add_material", "gfxh_scene_add_texture", "gfxh_scene_load_texture", "gfxh_scene_num_textures", "gfxh_scene_get_texture", "gfxh_scene_add_texture_bc", "gfxh_scene_get_texture_bc", "gfxh_dds_parse", "gfxh_scene_add_geom", "gfxh_scene_add_group", "gfxh_scene_add_instance",
+    "gfxh_scene_add_material", "gfxh_scene_add_texture", "gfxh_scene_load_texture", "gfxh_scene_num_textures", "gfxh_scene_get_texture", "gfxh_scene_add_texture_bc", "gfxh_scene_get_texture_bc", "gfxh_dds_parse", "gfxh_image_info", "gfxh_image_decode_rgba8", "gfxh_scene_add_geom", "gfxh_scene_add_group", "gfxh_scene_add_instance",
     "gfxh_scene_load_obj", "gfxh_scene_load_obj_conv", "gfxh_scene_add_rectangle_textured", "gfxh_scene_add_rectangle", "gfxh_scene_make_street", "gfxh_scene_counts",
     "gfxh_scene_get_material", "gfxh_scene_get_geom", "gfxh_scene_get_group", "gfxh_scene_get_instance",
     "gfxh_scene_bounds", "gfxh_scene_upload", "gfxh_make_transform", "gfxh_make_orientation",
@@ -407,6 +408,56 @@ def dds_parse(data):
         libc.free(C.c_void_p(p))
 
 
+IMAGE_PNG, IMAGE_JPEG = 1, 2
+
+
+class GfxhImageDesc(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("channels", C.c_uint32), ("kind", C.c_uint32)]
+
+
+def _with_heap_copy(data, fn):
+    """fn(pointer, length) on a heap block of exactly len(data) bytes (as dds_parse: a sanitizer build sees any read past the end)"""
+    libc = C.CDLL(None)
+    libc.malloc.restype = C.c_void_p
+    buf = bytes(data)
+    p = libc.malloc(C.c_size_t(max(len(buf), 1)))
+    if not p:
+        raise MemoryError("malloc")
+    try:
+        C.memmove(p, buf, len(buf))
+        return fn(C.c_void_p(p), C.c_size_t(len(buf)))
+    finally:
+        libc.free(C.c_void_p(p))
+
+
+def image_info(data):
+    """gfxh_image_info of the bytes of a PNG or JPEG file: a GfxhImageDesc (nothing is decoded), or GfxError with the cause."""
+    L = lib()
+
+    def run(p, n):
+        info = GfxhImageDesc()
+        if L.gfxh_image_info(p, n, C.byref(info)):
+            raise GfxError(L.gfxh_last_error().decode(errors="replace"))
+        return info
+    return _with_heap_copy(data, run)
+
+
+def image_decode_rgba8(data):
+    """gfxh_image_decode_rgba8: (uint8 [height, width, 4], channels of the file) -- the bytes and the n of the reference's
+    stbi_load(file, &w, &h, &n, 4) -- or GfxError with the cause."""
+    L = lib()
+
+    def run(p, n):
+        info = GfxhImageDesc()
+        if L.gfxh_image_info(p, n, C.byref(info)):
+            raise GfxError(L.gfxh_last_error().decode(errors="replace"))
+        out = np.empty((info.height, info.width, 4), np.uint8)
+        if L.gfxh_image_decode_rgba8(p, n, _p(out), C.c_size_t(out.nbytes)):
+            raise GfxError(L.gfxh_last_error().decode(errors="replace"))
+        return out, int(info.channels)
+    return _with_heap_copy(data, run)
+
+
 def _bc_blocks(blocks, w, h, bc_format):
     b = np.ascontiguousarray(blocks, np.uint8).reshape(-1)
     if bc_format in BC_BLOCK_BYTES and b.size != ((w + 3) // 4) * ((h + 3) // 4) * BC_BLOCK_BYTES[bc_format]:
@@ -465,7 +516,7 @@ class HostScene:
         return slot
 
     def load_texture(self, path, fmt8=0):
-        """An image file (PPM / PGM / PFM / BMP / TGA / EXR) or a .dds, whose block-compressed level 0 stays blocks."""
+        """An image file (PNG / JPEG / PPM / PGM / PFM / BMP / TGA / EXR) or a .dds, whose block-compressed level 0 stays blocks."""
         slot = self.L.gfxh_scene_load_texture(self.h, path.encode(), C.c_uint32(fmt8))
         if slot == 0:
             raise GfxError(self.L.gfxh_last_error().decode(errors="replace"))

@@ -86,6 +86,7 @@ const Field kFields[] = {
     F(gfxh_sdr_config, apply_sRGB_gammaCorrection), F(gfxh_sdr_config, flipY),
     S(gfxh_dds_info), F(gfxh_dds_info, width), F(gfxh_dds_info, height), F(gfxh_dds_info, mipCount), F(gfxh_dds_info, isBlockCompressed), F(gfxh_dds_info, bcFormat),
     F(gfxh_dds_info, isBGRA), F(gfxh_dds_info, isSRGB), F(gfxh_dds_info, reserved), F(gfxh_dds_info, dataOffset), F(gfxh_dds_info, dataBytes),
+    S(gfxh_image_desc), F(gfxh_image_desc, width), F(gfxh_image_desc, height), F(gfxh_image_desc, channels), F(gfxh_image_desc, kind),
 };
 #undef S
 #undef F

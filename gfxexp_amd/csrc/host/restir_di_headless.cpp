@@ -18,7 +18,7 @@
 // Headless options (no counterpart; the reference takes these from its GUI):
 //   -size W H (1920 1080)   -frames N (1)   -renderer restir-biased|restir-unbiased|rearch-biased|rearch-unbiased|pt|regir|nrc
 //   -animate (advance the instance controllers by 1/60 s per frame, :2249-2257)   -accumulate   -bump   -device k
-//   -out path (.exr / .pfm: HDR; .bmp / .ppm: tone-mapped SDR)   -dry-run (parse, build the scene on the host, print it, no GPU)
+//   -out path (.exr / .pfm: HDR; .png / .bmp / .ppm: tone-mapped SDR)   -dry-run (parse, build the scene on the host, print it, no GPU)
 //   -denoise [stages] (5; 0..5): after every frame copy-to-linear, the depth and emissive guides, gfx_denoise and gfxh_restir_outputs_consumed
 //        (the OptiX denoiser call of restir_di_main.cpp:2497-2533 and the order gfxexp_host.h asks for); -out then writes the
 //        denoised beauty (BufferToDisplay::DenoisedBeauty) and the JSON line gains "denoise_ms" (HIP events, all frames)
@@ -31,8 +31,8 @@
 //   and, headless: -max-path-length n (5; 0 = unlimited, :1860-1861)   -no-train   -log10-radiance-scale s (0, :2240)
 //   -nee lights|regir|restir (lights): next-event estimation from the emitter distributions (the reference), from the ReGIR grid, or --
 //        at the first path vertex -- from the pixel's ReSTIR DI reservoir (the two halves of README.md:80-81)
-// Textures are read by the host decoders of scene_builder.cpp (PPM / PGM / PFM / BMP / TGA, OpenEXR); DDS / PNG / JPEG assets have to be
-// decoded offline (the image has no image libraries).
+// Textures are read by the host decoders of scene_builder.cpp and image_codecs.cpp (PNG and JPEG as the reference's stb_image decodes them,
+// .dds with BC1-BC5 / BC7 blocks, PPM / PGM / PFM / BMP / TGA, OpenEXR): an asset tree is used as it is.  -env-texture wants a float image.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>

@@ -21,6 +21,7 @@
 #include <tuple>
 #include <vector>
 #include "../../../include/gfxexp_host.h"
+#include "image_codecs.h"
 
 namespace {
 
@@ -368,110 +369,8 @@ bool pnm_token(const std::vector<uint8_t>& d, size_t& at, std::string& tok) {
 // document (magic, version, attribute list, chunk offset table, chunks of 1 / 16 scanlines each stored channel by channel in
 // alphabetical order); ZIP / RLE chunks are a zlib stream (RFC 1950 / 1951, inflated below) or run lengths over the chunk's bytes
 // after a byte-delta predictor and an even / odd byte split.
-struct BitReader {
-    const uint8_t* p; size_t n, at = 0; uint32_t acc = 0; int have = 0; bool bad = false;
-    uint32_t bits(int k) {
-        while (have < k) { if (at >= n) { bad = true; return 0; } acc |= static_cast<uint32_t>(p[at++]) << have; have += 8; }
-        const uint32_t v = acc & ((k == 32) ? 0xFFFFFFFFu : ((1u << k) - 1u));
-        acc = k >= 32 ? 0 : acc >> k; have -= k;
-        return v;
-    }
-};
-struct Huffman { uint16_t count[16]; uint16_t symbol[288]; };
-void build_huffman(Huffman& h, const uint8_t* lengths, int n) {
-    std::memset(h.count, 0, sizeof(h.count));
-    for (int i = 0; i < n; ++i) ++h.count[lengths[i]];
-    h.count[0] = 0;
-    uint16_t offs[16]; offs[1] = 0;
-    for (int l = 1; l < 15; ++l) offs[l + 1] = static_cast<uint16_t>(offs[l] + h.count[l]);
-    for (int i = 0; i < n; ++i) if (lengths[i]) h.symbol[offs[lengths[i]]++] = static_cast<uint16_t>(i);
-}
-int decode_symbol(BitReader& br, const Huffman& h) {       // canonical code, one bit at a time (RFC 1951 3.2.2)
-    int code = 0, first = 0, index = 0;
-    for (int len = 1; len <= 15; ++len) {
-        code |= static_cast<int>(br.bits(1));
-        if (br.bad) return -1;
-        const int count = h.count[len];
-        if (code - count < first) return h.symbol[index + (code - first)];
-        index += count; first += count; first <<= 1; code <<= 1;
-    }
-    return -1;
-}
-// zlib stream -> exactly `want` bytes; false on any malformed input
-bool inflate_zlib(const uint8_t* src, size_t n, std::vector<uint8_t>& out, size_t want) {
-    static const uint16_t lenBase[29] = { 3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258 };
-    static const uint16_t lenExtra[29] = { 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0 };
-    static const uint16_t distBase[30] = { 1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577 };
-    static const uint16_t distExtra[30] = { 0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13 };
-    if (n < 2 || (src[0] & 0x0F) != 8 || ((src[0] << 8) | src[1]) % 31 != 0 || (src[1] & 0x20)) return false;
-    BitReader br{ src + 2, n - 2 };
-    out.clear(); out.reserve(want);
-    for (bool last = false; !last;) {
-        last = br.bits(1) != 0;
-        const uint32_t type = br.bits(2);
-        if (br.bad) return false;
-        if (type == 0) {
-            br.acc = 0; br.have = 0;                                   // to the next byte boundary
-            if (br.at + 4 > br.n) return false;
-            const uint32_t len = br.p[br.at] | (br.p[br.at + 1] << 8), nlen = br.p[br.at + 2] | (br.p[br.at + 3] << 8);
-            br.at += 4;
-            if ((len ^ 0xFFFFu) != nlen || br.at + len > br.n || out.size() + len > want) return false;
-            out.insert(out.end(), br.p + br.at, br.p + br.at + len);
-            br.at += len;
-            continue;
-        }
-        if (type == 3) return false;
-        Huffman lit, dist;
-        uint8_t lengths[320];
-        if (type == 1) {
-            for (int i = 0; i < 144; ++i) lengths[i] = 8;
-            for (int i = 144; i < 256; ++i) lengths[i] = 9;
-            for (int i = 256; i < 280; ++i) lengths[i] = 7;
-            for (int i = 280; i < 288; ++i) lengths[i] = 8;
-            build_huffman(lit, lengths, 288);
-            for (int i = 0; i < 30; ++i) lengths[i] = 5;
-            build_huffman(dist, lengths, 30);
-        }
-        else {
-            static const uint8_t order[19] = { 16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15 };
-            const int nlen = static_cast<int>(br.bits(5)) + 257, ndist = static_cast<int>(br.bits(5)) + 1, ncode = static_cast<int>(br.bits(4)) + 4;
-            if (br.bad || nlen > 286 || ndist > 30) return false;
-            uint8_t cl[19] = { 0 };
-            for (int i = 0; i < ncode; ++i) cl[order[i]] = static_cast<uint8_t>(br.bits(3));
-            Huffman lc;
-            build_huffman(lc, cl, 19);
-            int i = 0;
-            while (i < nlen + ndist) {
-                const int sym = decode_symbol(br, lc);
-                if (sym < 0) return false;
-                if (sym < 16) { lengths[i++] = static_cast<uint8_t>(sym); continue; }
-                int rep, val = 0;
-                if (sym == 16) { if (i == 0) return false; val = lengths[i - 1]; rep = 3 + static_cast<int>(br.bits(2)); }
-                else if (sym == 17) rep = 3 + static_cast<int>(br.bits(3));
-                else rep = 11 + static_cast<int>(br.bits(7));
-                if (br.bad || i + rep > nlen + ndist) return false;
-                while (rep--) lengths[i++] = static_cast<uint8_t>(val);
-            }
-            if (lengths[256] == 0) return false;
-            build_huffman(lit, lengths, nlen);
-            build_huffman(dist, lengths + nlen, ndist);
-        }
-        for (;;) {
-            const int sym = decode_symbol(br, lit);
-            if (sym < 0) return false;
-            if (sym < 256) { if (out.size() >= want) return false; out.push_back(static_cast<uint8_t>(sym)); continue; }
-            if (sym == 256) break;
-            if (sym > 285) return false;
-            const uint32_t len = lenBase[sym - 257] + br.bits(lenExtra[sym - 257]);
-            const int ds = decode_symbol(br, dist);
-            if (ds < 0 || ds > 29) return false;
-            const uint32_t d = distBase[ds] + br.bits(distExtra[ds]);
-            if (br.bad || d > out.size() || out.size() + len > want) return false;
-            for (uint32_t k = 0; k < len; ++k) out.push_back(out[out.size() - d]);
-        }
-    }
-    return out.size() == want;
-}
+// (inflate_zlib for the ZIP / ZIPS chunks lives in image_codecs.cpp, next to the PNG reader that shares it)
+using gfx_img::inflate_zlib;
 inline float half_to_float(uint16_t h) {
     const uint32_t sign = static_cast<uint32_t>(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3FFu;
     uint32_t bits;
@@ -619,11 +518,18 @@ bool decode_exr(const std::vector<uint8_t>& d, const std::string& path, Image& i
     return true;
 }
 
-// Uncompressed formats (no third-party decoders in this build): binary PPM / PGM (8 bit), PFM, BMP 24 / 32 bit, TGA types 2 / 3
-// (24 / 32 / 8 bit) -- and OpenEXR above.  BC-compressed DDS and PNG files of the original assets are decoded offline (tools/dds_convert.py).
+// By magic, not by extension: PNG and JPEG (image_codecs.cpp: the bytes stbi_load(..., 4) gives the reference, common_host.cpp:1210-1229),
+// OpenEXR above, and the uncompressed formats binary PPM / PGM (8 bit), PFM, BMP 24 / 32 bit, TGA types 2 / 3 (24 / 32 / 8 bit).
+// No third-party decoder in this build.  .dds files take their own branch in gfxh_scene_load_texture.
 bool decode_image(const std::string& path, Image& img, std::string& err) {
     std::vector<uint8_t> d;
     if (!read_file(path, d)) { err = "cannot read " + path; return false; }
+    if (gfx_img::sniff(d.data(), d.size()) != gfx_img::kKindNone) {      // before the TGA test below, which any FF D8 FF E0 would pass
+        gfx_img::Info info;
+        if (!gfx_img::decode(d.data(), d.size(), info, img.rgba8, err)) { err += ": " + path; return false; }
+        img.w = info.width; img.h = info.height;
+        return true;
+    }
     if (d.size() >= 8 && d[0] == 0x76 && d[1] == 0x2f && d[2] == 0x31 && d[3] == 0x01) return decode_exr(d, path, img, err);
     if (d.size() >= 2 && d[0] == 'P' && (d[1] == '6' || d[1] == '5')) {
         size_t at = 2; std::string t;
@@ -708,10 +614,29 @@ bool decode_image(const std::string& path, Image& img, std::string& err) {
             }
         return true;
     }
-    err = "unsupported image format (PPM / PGM / PFM / BMP / TGA uncompressed, EXR): " + path;
+    err = "unsupported image format (PNG, JPEG, PPM / PGM / PFM / BMP / TGA uncompressed, EXR): " + path;
     return false;
 }
 } // namespace
+
+int gfxh_image_info(const void* data, size_t bytes, gfxh_image_desc* info) {
+    gfx_img::Info i; std::string err;
+    if (!data || !info || !gfx_img::info(static_cast<const uint8_t*>(data), bytes, i, err)) { g_hostError = "gfxh_image_info: " + (err.empty() ? std::string("null argument") : err); return 1; }
+    info->width = i.width; info->height = i.height; info->channels = i.channels; info->kind = i.kind;
+    return 0;
+}
+int gfxh_image_decode_rgba8(const void* data, size_t bytes, void* out, size_t capacityBytes) {
+    gfx_img::Info i; std::string err;
+    if (!data || !out) { g_hostError = "gfxh_image_decode_rgba8: null argument"; return 1; }
+    // the header first, so that a buffer that is too small is reported before anything is decoded
+    if (!gfx_img::info(static_cast<const uint8_t*>(data), bytes, i, err)) { g_hostError = "gfxh_image_decode_rgba8: " + err; return 1; }
+    if (capacityBytes < 4ull * i.width * i.height) { g_hostError = "gfxh_image_decode_rgba8: the output buffer holds fewer than 4 * width * height bytes"; return 1; }
+    std::vector<uint8_t> rgba;
+    if (!gfx_img::decode(static_cast<const uint8_t*>(data), bytes, i, rgba, err)) { g_hostError = "gfxh_image_decode_rgba8: " + err; return 1; }
+    if (rgba.size() > capacityBytes) { g_hostError = "gfxh_image_decode_rgba8: the decoded image does not have the size of its header"; return 1; }
+    std::memcpy(out, rgba.data(), rgba.size());
+    return 0;
+}
 
 static bool is_dds_path(const std::string& path) {   // filePath.extension() == ".dds" || ".DDS" (common_host.cpp:1185-1186)
     return path.size() >= 4 && (path.compare(path.size() - 4, 4, ".dds") == 0 || path.compare(path.size() - 4, 4, ".DDS") == 0);
@@ -1712,7 +1637,13 @@ extern "C" int gfxh_save_image_sdr(const char* path, uint32_t width, uint32_t he
             std::fwrite(row.data(), 1, rowBytes, f);
         }
     }
-    else { std::fclose(f); g_hostError = "gfxh_save_image_sdr: .bmp or .ppm"; return 1; }
+    else if (has_ext(path, ".png")) {                                    // stbi_write_png of saveImage (common_host.cpp:2715-2720): 8-bit RGBA, top row first
+        std::vector<uint8_t> file; std::string err;
+        // px holds R | G << 8 | B << 16 | A << 24: on the little-endian hosts this library builds for that is R, G, B, A in memory
+        if (!gfx_img::png_encode_rgba8(reinterpret_cast<const uint8_t*>(px.data()), width, height, file, err)) { std::fclose(f); g_hostError = "gfxh_save_image_sdr: " + err; return 1; }
+        if (std::fwrite(file.data(), 1, file.size(), f) != file.size()) { std::fclose(f); g_hostError = std::string("gfxh_save_image_sdr: short write to ") + path; return 1; }
+    }
+    else { std::fclose(f); g_hostError = "gfxh_save_image_sdr: .bmp or .ppm or .png"; return 1; }
     std::fclose(f);
     return 0;
 }

@@ -68,6 +68,23 @@ typedef struct gfxh_dds_info {
  * an extent of 0 or above 16384, a payload shorter than level 0 needs.  Never reads outside data[0, bytes). */
 int gfxh_dds_parse(const void* data, size_t bytes, gfxh_dds_info* info);
 
+/* PNG and JPEG files held in memory (an archive member, an image embedded in another file); gfxh_scene_load_texture reads the same
+ * two formats from a path.  The decoders return exactly the bytes stbi_load(file, &w, &h, &n, 4) of the reference's stb_image
+ * returns (common_host.cpp:1210-1229): 8-bit RGBA, row 0 first; `channels` is that n, the channel count of the file (1 grey,
+ * 2 grey + alpha, 3 colour, 4 colour + alpha; a tRNS chunk counts as alpha, CMYK counts as 3).  PNG: every colour type and
+ * bit depth, Adam7, no gamma handling; JPEG: Huffman-coded 8-bit sequential and progressive.  Arithmetic-coded, lossless,
+ * hierarchical and 12-bit JPEG, Apple CgBI PNG and an extent of 0 or above 16384 are refused. */
+enum gfxh_image_kind { GFXH_IMAGE_PNG = 1, GFXH_IMAGE_JPEG = 2 };
+typedef struct gfxh_image_desc {
+    uint32_t width, height;
+    uint32_t channels;
+    uint32_t kind;                /* enum gfxh_image_kind */
+} gfxh_image_desc;
+/* The header only; nothing is decoded.  Returns 1 with a gfxh_last_error that names the cause. */
+int gfxh_image_info(const void* data, size_t bytes, gfxh_image_desc* info);
+/* Decodes into out[0, 4 * width * height); capacityBytes below that is an error.  Never reads outside data[0, bytes). */
+int gfxh_image_decode_rgba8(const void* data, size_t bytes, void* out, size_t capacityBytes);
+
 /* Geometry / groups / instances (return slot indices). */
 uint32_t gfxh_scene_add_geom(gfxh_scene* s, const gfx_vertex* v, uint32_t nv, const uint32_t* tris, uint32_t nt, uint32_t matSlot);
 uint32_t gfxh_scene_add_group(gfxh_scene* s, const uint32_t* geomSlots, uint32_t n);
@@ -468,7 +485,8 @@ const char* gfxh_nrc_last_error(void);
 /* ---- output chain (common/common_host.cpp:2725-2922 saveImage / saveImageHDR) -------------------------------------
  * rgba: host copy of a float4 accumulation buffer (gfx_read_device of the beauty buffer), row-major, top row first.
  * SDR: optional tone map on the luminance (1 - exp(-brightnessScale * Y), chroma kept), optional sRGB gamma, 8 bits
- * per channel as min(uint(v * 255), 255); written as 24-bit .bmp or binary .ppm by extension.  HDR: the fp32 values
+ * per channel as min(uint(v * 255), 255); written as 24-bit .bmp, binary .ppm or 8-bit RGBA .png (as the reference's saveImage
+ * writes; the contract is the decoded pixels, not the bytes of its writer) by extension.  HDR: the fp32 values
  * times brightnessScale as a .pfm (the reference writes the same numbers as an OpenEXR file through tinyexr). */
 typedef struct gfxh_sdr_config {
     float alphaForOverride;              /* kept for layout parity with SDRImageSaverConfig (common_host.h:1520-1532); unused */

@@ -1,0 +1,262 @@
+"""CPU: the PNG / JPEG readers and the PNG writer of the host layer (gfxexp_amd/csrc/host/image_codecs.cpp).
+
+The yardstick is the reference's own decoder: tests/golden/images holds, for every input file, the bytes and the channel count its
+stbi_load(file, &w, &h, &n, 4) returned (make_image_golden.py compiled it at development time; nothing of it is in this tree).  The
+condition is byte for byte on EVERY valid fixture -- no tolerance and no fixture left out -- through gfxh_image_decode_rgba8 and
+through gfxh_scene_load_texture.  The refusal group must be refused (the two 20000-wide files, which the reference decodes, by the
+library's own 16384 limit).  Truncated and mutated files need only be safe: refused, or decoded to an image within the limit; the
+same schedule runs under AddressSanitizer + UBSan in test_the_readers_under_sanitizers."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from gfxexp_amd import api
+from tests import image_fixtures as F
+
+C = api.C
+CHANNELS = {api.TEX_RGBA8_SRGB: 4, api.TEX_RGBA8_UNORM: 4, api.TEX_RG8_UNORM: 2, api.TEX_R8_UNORM: 1}
+
+
+def _same(tag, got, want):
+    assert got.shape == want.shape, (tag, got.shape, want.shape)
+    bad = np.argwhere((got != want).reshape(got.shape[0], got.shape[1], -1).any(-1))
+    assert len(bad) == 0, "%s: %d of %d pixels differ, first at (y, x) = %s: %s, reference %s" % (
+        tag, len(bad), got.shape[0] * got.shape[1], tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])])
+
+
+def test_the_fixture_set_is_the_one_the_issue_names():
+    names = F.valid_names()
+    png, jpg = [n for n in names if n.endswith(".png")], [n for n in names if n.endswith(".jpg")]
+    assert len(png) >= 30 and len(jpg) >= 16
+    for needed in ("rgb8", "rgba8", "g8", "la8", "pal1", "pal2", "pal4", "pal8", "pal4_trns", "g1", "g2", "g4", "g16", "ga16", "rgb16", "rgba16",
+                   "rgb8_filter0", "rgb8_filter1", "rgb8_filter2", "rgb8_filter3", "rgb8_filter4", "rgb8_stored", "g8_trns", "rgb8_trns", "rgb16_trns",
+                   "rgb8_1x1", "rgba8_3x5", "adam7_g2", "adam7_g4", "adam7_ga16", "adam7_rgb8", "adam7_rgb16", "adam7_rgba16", "adam7_pal4_trns"):
+        assert needed + ".png" in png, needed
+    for needed in ("base444", "base422", "base420", "prog444", "prog420", "prog422_64", "optimised", "restart3", "q30", "q100", "grey_base", "grey_prog",
+                   "cmyk_adobe", "base420_1x1", "base420_9x17", "base420_16x16", "own_440", "own_h4v1", "own_rgb_ids", "sof1_patch"):
+        assert needed + ".jpg" in jpg, needed
+    assert set(F.refused_names()) == {"refuse_sof3.jpg", "refuse_sof9.jpg", "refuse_12bit.jpg", "refuse_zero_width.jpg", "refuse_zero_width.png",
+                                      "refuse_filter7.png", "refuse_depth3.png"}
+    assert set(F.oversize_names()) == {"oversize_20000.png", "oversize_20000.jpg"}
+
+
+@pytest.mark.parametrize("name", F.valid_names())
+def test_decode_equals_the_reference_decoder(built_lib, name):
+    want, n = F.golden(name)
+    data = F.inputs()[name]
+    info = api.image_info(data)
+    assert (info.width, info.height, info.channels) == (want.shape[1], want.shape[0], n)
+    assert info.kind == (api.IMAGE_PNG if name.endswith(".png") else api.IMAGE_JPEG)
+    got, got_n = api.image_decode_rgba8(data)
+    assert got_n == n
+    _same(name, got, want)
+
+
+@pytest.mark.parametrize("name", F.valid_names())
+def test_load_texture_equals_the_reference_decoder(built_lib, tmp_path, name):
+    """by magic, not by extension: the file is stored under a name that says nothing"""
+    want, _ = F.golden(name)
+    path = F.write_file(tmp_path, name)
+    blind = os.path.join(str(tmp_path), "texture.bin")
+    os.replace(path, blind)
+    s = api.HostScene()
+    slot = s.load_texture(blind, api.TEX_RGBA8_SRGB)
+    (got_slot, w, h, fmt, texels), = s.textures()
+    assert (got_slot, w, h, fmt) == (slot, want.shape[1], want.shape[0], api.TEX_RGBA8_SRGB)
+    _same(name, texels.reshape(h, w, 4), want)
+
+
+@pytest.mark.parametrize("name", ["rgba8.png", "adam7_ga16.png", "base422.jpg", "prog420.jpg"])
+def test_format_requests_and_the_cache(built_lib, tmp_path, name):
+    want, _ = F.golden(name)
+    path = F.write_file(tmp_path, name)
+    s = api.HostScene()
+    slots = {}
+    for fmt in (api.TEX_RGBA8_SRGB, api.TEX_RGBA8_UNORM, api.TEX_R8_UNORM, api.TEX_RG8_UNORM):
+        slots[fmt] = s.load_texture(path, fmt)
+    assert sorted(slots.values()) == [1, 2, 3, 4]
+    for fmt, slot in slots.items():                                 # cached per path and format: no new slot
+        assert s.load_texture(path, fmt) == slot
+    assert len(s.textures()) == 4
+    for slot, w, h, fmt, texels in s.textures():
+        assert slots[fmt] == slot
+        _same("%s as format %d" % (name, fmt), texels.reshape(h, w, CHANNELS[fmt]), want[..., :CHANNELS[fmt]])
+    other = F.write_file(tmp_path, "g8.png")
+    assert s.load_texture(other, api.TEX_RGBA8_SRGB) == 5
+
+
+@pytest.mark.parametrize("name", F.refused_names() + F.oversize_names())
+def test_refusals(built_lib, tmp_path, name):
+    data = F.inputs()[name]
+    with pytest.raises(api.GfxError) as e:
+        api.image_decode_rgba8(data)
+    if name.startswith("oversize"):
+        assert "larger than 16384" in str(e.value)
+        with pytest.raises(api.GfxError, match="larger than 16384"):
+            api.image_info(data)
+    s = api.HostScene()
+    with pytest.raises(api.GfxError) as e2:
+        s.load_texture(F.write_file(tmp_path, name), api.TEX_RGBA8_SRGB)
+    assert name in str(e2.value) and (not name.startswith("oversize") or "larger than 16384" in str(e2.value))
+    assert s.textures() == []
+
+
+def test_entry_point_arguments(built_lib):
+    L = api.lib()
+    data = F.inputs()["rgb8.png"]
+    want, _ = F.golden("rgb8.png")
+    info = api.GfxhImageDesc()
+    out = np.zeros(want.nbytes, np.uint8)
+    assert L.gfxh_image_info(None, C.c_size_t(0), C.byref(info)) == 1
+    assert L.gfxh_image_info(data, C.c_size_t(len(data)), None) == 1
+    assert L.gfxh_image_decode_rgba8(data, C.c_size_t(len(data)), None, C.c_size_t(0)) == 1
+    assert L.gfxh_image_decode_rgba8(data, C.c_size_t(len(data)), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes - 1)) == 1
+    assert "fewer than" in L.gfxh_last_error().decode() and not out.any()
+    assert L.gfxh_image_decode_rgba8(data, C.c_size_t(len(data)), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes)) == 0
+    assert np.array_equal(out.reshape(want.shape), want)
+    for junk in (b"", b"\x89PNG", b"\xff\xd8", b"BM" + bytes(60), bytes(64)):
+        with pytest.raises(api.GfxError, match="neither a PNG nor a JPEG"):
+            api.image_info(junk)
+    assert api.abi_mirrors()["gfxh_image_desc"] is api.GfxhImageDesc and api.abi_layout()["gfxh_image_desc"]["size"] == 16
+
+
+def _safe(data):
+    """decoded (1) or refused (0); a decode has to stay within the library's limit"""
+    try:
+        rgba, n = api.image_decode_rgba8(data)
+    except api.GfxError:
+        return 0
+    assert 1 <= rgba.shape[0] <= F.MAX_DIM and 1 <= rgba.shape[1] <= F.MAX_DIM and n in (1, 2, 3, 4)
+    return 1
+
+
+def _fuzz_counts(index, name):
+    data = F.inputs()[name]
+    prefixes = [_safe(data[:n]) for n in range(len(data))]
+    mutated = [_safe(m) for m in F.mutations(data, index)]
+    return (sum(prefixes), len(prefixes) - sum(prefixes), sum(mutated), len(mutated) - sum(mutated))
+
+
+@pytest.mark.parametrize("index,name", list(enumerate(F.FUZZ_SEEDS)))
+def test_prefixes_and_mutations_are_safe(built_lib, index, name):
+    counts = _fuzz_counts(index, name)
+    assert counts[0] + counts[1] == len(F.inputs()[name]) and counts[2] + counts[3] == F.FUZZ_MUTATIONS
+    # the whole file decodes and a prefix that stops inside the image data does not claim to be the whole image
+    assert counts[1] > len(F.inputs()[name]) // 2
+    info = api.GfxhImageDesc()
+    data = F.inputs()[name]
+    for n in range(0, len(data), 7):
+        api.lib().gfxh_image_info(data[:n], C.c_size_t(n), C.byref(info))
+
+
+def test_the_readers_under_sanitizers(built_lib, tmp_path):
+    """the same prefixes and mutations through image_codecs.cpp built alone with -fsanitize=address,undefined (an executable of its
+    own: no preloading, nothing near the GPU library); its decoded / refused counts equal the in-library ones"""
+    from tests.native import build_image_fuzz
+    try:
+        exe = build_image_fuzz.build()
+    except build_image_fuzz.Unavailable as e:
+        pytest.skip(str(e))
+    paths = [F.write_file(tmp_path, n) for n in F.FUZZ_SEEDS]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe] + paths, capture_output=True, text=True, timeout=900, env=env)
+    if r.returncode != 0 and "ASan runtime does not come first" in r.stderr:
+        pytest.skip("the sanitizer runtime cannot start in this environment: " + r.stderr.strip().splitlines()[0])
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = r.stdout.split("\n")
+    for index, name in enumerate(F.FUZZ_SEEDS):
+        words = lines[index].split()
+        assert words[0] == name and words[1] == "prefixes" and words[4] == "mutations"
+        assert (int(words[2]), int(words[3]), int(words[5]), int(words[6])) == _fuzz_counts(index, name), name
+
+
+# ---------------------------------------------------------------- PNG out
+@pytest.mark.parametrize("w,h", [(1, 1), (37, 19), (1920, 1080)])
+def test_saved_png_holds_the_tonemapped_pixels(built_lib, tmp_path, w, h):
+    rng = np.random.default_rng(w * 31 + h)
+    y, x = np.mgrid[0:h, 0:w].astype(np.float32)
+    rgba = np.stack([x / w * 3, y / h * 2, (x + y) % 17 / 8, np.full_like(x, 1.0)], -1).astype(np.float32)
+    rgba[..., :3] += rng.random((h, w, 3), dtype=np.float32) * 0.3
+    rgba[h // 2:, :, 3] = 0.25
+    cfg = api.GfxhSdrConfig(-1.0, 1.5, 1, 1, 0)
+    px = api.tonemap_sdr(rgba, w, h, cfg)
+    want = np.stack([px & 255, (px >> 8) & 255, (px >> 16) & 255, px >> 24], -1).astype(np.uint8)
+    path = str(tmp_path / "frame.png")
+    api.save_image_sdr(path, rgba, w, h, cfg)
+    with open(path, "rb") as f:
+        data = f.read()
+    _same("zlib + numpy", F.read_png_rgba8(data), want)
+    got, n = api.image_decode_rgba8(data)
+    assert n == 4
+    _same("own reader", got, want)
+    assert len(set(want[..., 3].reshape(-1).tolist())) == (2 if h > 1 else 1)
+    with pytest.raises(api.GfxError, match=".png"):
+        api.save_image_sdr(str(tmp_path / "frame.gif"), rgba, w, h, cfg)
+
+
+# ---------------------------------------------------------------- OBJ + MTL
+QUAD_OBJ = ("mtllib quad.mtl\nv -1 0 -1\nv 1 0 -1\nv 1 0 1\nv -1 0 1\nvt 0 0\nvt 1 0\nvt 1 1\nvt 0 1\nvn 0 1 0\n"
+            "usemtl tiles\nf 1/1/1 4/4/1 3/3/1 2/2/1\n")
+MAPS = {"a": "rgba8.png", "b": "base420.jpg", "n": "adam7_rgb8.png", "e": "prog444.jpg"}
+
+
+def _write_quad(directory, compressed):
+    os.makedirs(directory)
+    names = {}
+    for key, fixture in MAPS.items():
+        if compressed:
+            names[key] = key + os.path.splitext(fixture)[1]
+            F.write_file(directory, fixture)
+            os.replace(os.path.join(directory, fixture), os.path.join(directory, names[key]))
+        else:
+            names[key] = key + ".tga"
+            F.write_tga(os.path.join(directory, names[key]), F.golden(fixture)[0])
+    with open(os.path.join(directory, "quad.mtl"), "w") as f:
+        f.write("newmtl tiles\nKd 0.5 0.4 0.3\nKs 0.1 0.1 0.1\nNs 40\nKe 0 0 0\nmap_Kd %s\nmap_Ks %s\nmap_bump %s\nmap_Ke %s\n" % (names["a"], names["b"], names["n"], names["e"]))
+    with open(os.path.join(directory, "quad.obj"), "w") as f:
+        f.write(QUAD_OBJ)
+    return os.path.join(directory, "quad.obj")
+
+
+def test_an_mtl_with_png_and_jpg_maps_equals_the_same_scene_with_tga_maps(built_lib, tmp_path):
+    scenes = []
+    for compressed in (True, False):
+        s = api.HostScene()
+        s.load_obj(_write_quad(str(tmp_path / ("c" if compressed else "t")), compressed))
+        scenes.append(s)
+    a, b = scenes
+    assert len(a.textures()) == 4
+    for (slot, w, h, fmt, texels), other in zip(a.textures(), b.textures()):
+        assert (slot, w, h, fmt) == other[:4] and np.array_equal(texels, other[4]), slot
+    ma, mb = a.materials(), b.materials()
+    assert len(ma) == len(mb) == 1 and bytes(ma[0]) == bytes(mb[0])
+    m = ma[0]
+    fm = {t[0]: t for t in a.textures()}
+    assert m.texA and m.texB and m.texNormal and m.texEmittance and m.hasEmittance == 1 and m.bumpMapType == api.BUMP_NORMAL_MAP
+    assert fm[m.texA][3] == api.TEX_RGBA8_SRGB and fm[m.texB][3] == api.TEX_RGBA8_SRGB and fm[m.texNormal][3] == api.TEX_RGBA8_UNORM
+    for slot, fixture in ((m.texA, "rgba8.png"), (m.texB, "base420.jpg"), (m.texNormal, "adam7_rgb8.png"), (m.texEmittance, "prog444.jpg")):
+        want = F.golden(fixture)[0]
+        _same(fixture, fm[slot][4].reshape(want.shape), want)
+
+
+def test_a_textured_rectangle_takes_a_jpeg(built_lib, tmp_path):
+    path = F.write_file(tmp_path, "q100.jpg")
+    s = api.HostScene()
+    g = api.lib().gfxh_scene_add_rectangle_textured(s.h, C.c_float(2.0), C.c_float(2.0), (C.c_float * 3)(5, 5, 5), path.encode())
+    assert g != 0xFFFFFFFF
+    (slot, w, h, fmt, texels), = s.textures()
+    want = F.golden("q100.jpg")[0]
+    assert fmt == api.TEX_RGBA8_SRGB
+    _same("q100.jpg", texels.reshape(want.shape), want)
+
+
+def test_the_command_line_builds_a_scene_from_png_and_jpg_maps(built_lib, tmp_path):
+    """-dry-run: the scene is built on the host and printed; the four maps of the MTL became four textures (none on the parent
+    commit, where a map that cannot be read leaves the immediate value in place)"""
+    from tests.test_headless_cli import _run
+    obj = _write_quad(str(tmp_path / "c"), True)
+    d = _run(["-name", "quad", "-obj", obj, 1.0, "trad", "-name", "panel", "-emittance", 5, 5, 5, "-rect-emitter-tex", F.write_file(tmp_path, "grey_base.jpg"),
+              "-rectangle", 1.0, 1.0, "-inst", "quad", "-inst", "panel", "-dry-run"])
+    assert d["textures"] == 5

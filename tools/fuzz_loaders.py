@@ -1,4 +1,5 @@
-"""Mutation fuzzing of the host loaders (gfxexp_amd/csrc/host/scene_builder.cpp: EXR / PFM / PNM / BMP / TGA decoders, the DDS parser, OBJ + MTL parser) against
+"""Mutation fuzzing of the host loaders (gfxexp_amd/csrc/host/scene_builder.cpp: EXR / PFM / PNM / BMP / TGA decoders, the DDS parser, OBJ + MTL parser;
+image_codecs.cpp: the PNG and JPEG readers, seeded with fixtures of tests/golden/images) against
 the ASan + UBSan build of the library's host code (tools/asan_cpu_suite.sh builds it and runs this).  Valid files are written here (the EXR
 writer of tests/test_exr_reader.py), then truncated, byte-flipped, given extreme 32-bit fields or spliced; a loader may refuse a file
 (GfxError) or load it -- a sanitizer report is the failure.  usage: fuzz_loaders.py [mutations per seed file, default 400]"""
@@ -7,6 +8,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from gfxexp_amd import api
 from tests import test_exr_reader as X
+from tests import image_fixtures as IMG
 rng = random.Random(7)
 nrng = np.random.default_rng(3)
 tmp = tempfile.mkdtemp()
@@ -37,6 +39,8 @@ seeds['a.dds'] = _dds(b"DX10", 99, w, h, nrng.integers(0, 256, 16 * 4 * 3, dtype
 seeds['b.dds'] = _dds(b"DXT1", 0, 8, 8, nrng.integers(0, 256, 8 * (4 + 1 + 1 + 1), dtype=np.uint8).tobytes(), mips=4)    # legacy FourCC with a mip chain
 seeds['c.dds'] = _dds(b"DX10", 87, w, h, nrng.integers(0, 256, 4 * w * h, dtype=np.uint8).tobytes())                     # uncompressed BGRA8
 seeds['d.dds'] = _dds(b"ATI2", 0, w, h, nrng.integers(0, 256, 16 * 4 * 3, dtype=np.uint8).tobytes())                     # BC5
+for name in ("rgba16.png", "adam7_pal4_trns.png", "g2.png", "rgb8_stored.png", "base420.jpg", "prog420.jpg", "restart3.jpg", "cmyk_adobe.jpg", "own_h4v1.jpg"):
+    seeds[name] = IMG.inputs()[name]                                                                                     # PNG / JPEG: palette, Adam7, 16 bit; restarts, progressive, CMYK
 obj = b"""mtllib m.mtl
 v 0 0 0\nv 1 0 0\nv 0 1 0\nv 1 1 0.5
 vt 0 0\nvt 1 0\nvt 0 1\nvt 1 1
@@ -85,6 +89,11 @@ for n, d in seeds.items():
             s.load_texture(p); ok += 1
         except api.GfxError:
             bad += 1
+        if n.endswith(('.png', '.jpg')):                             # the memory entry points, on an exactly sized heap buffer
+            try:
+                api.image_decode_rgba8(open(p, 'rb').read())
+            except api.GfxError:
+                pass
         if n.endswith('.dds'):                                       # the parser on its own, on an exactly sized heap buffer
             try:
                 api.dds_parse(open(p, 'rb').read())
