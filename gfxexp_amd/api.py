@@ -212,7 +212,7 @@ def abi_mirrors():
             "gfxh_nrc_config": GfxhNrcConfig, "gfxh_sdr_config": GfxhSdrConfig,
             "gfx_denoiser_settings": GfxDenoiserSettings, "gfx_denoiser_inputs": GfxDenoiserInputs,
             "gfx_denoiser_history_buffers": GfxDenoiserHistoryBuffers, "gfx_taa_inputs": GfxTaaInputs, "gfxh_dds_info": GfxhDdsInfo,
-            "gfxh_image_desc": GfxhImageDesc}
+            "gfxh_image_desc": GfxhImageDesc, "gfx_tfdm_params": GfxTfdmParams, "gfx_tfdm_hit": GfxTfdmHit}
 
 
 class RcclExchange:
@@ -327,10 +327,11 @@ C_ABI_SYMBOLS = [
     "gfx_nrc_get_params", "gfx_nrc_inference_image", "gfx_nrc_inference_image_async", "gfx_nrc_params_checksum", "gfx_nrc_set_render_params",
     "gfx_read_device", "gfx_timing_enable", "gfx_timing_collect", "gfx_counters_enable", "gfx_counters_read", "gfx_trace_diag_read", "gfx_pt_diag_read",
     "gfx_tunable_set", "gfx_stream_copy", "gfx_bc_expand",
+    "gfx_tfdm_default_params", "gfx_tfdm_create", "gfx_tfdm_set_params", "gfx_tfdm_destroy", "gfx_tfdm_trace", "gfx_tfdm_read", "gfx_tfdm_size",
 ]
 HOST_ABI_SYMBOLS = [
     "gfxh_scene_create", "gfxh_scene_destroy", "gfxh_last_error", "gfxh_scene_add_material_traditional",
-    "gfxh_scene_add_material", "gfxh_scene_add_texture", "gfxh_scene_load_texture", "gfxh_scene_num_textures", "gfxh_scene_get_texture", "gfxh_scene_add_texture_bc", "gfxh_scene_get_texture_bc", "gfxh_dds_parse", "gfxh_image_info", "gfxh_image_decode_rgba8", "gfxh_scene_add_geom", "gfxh_scene_add_group", "gfxh_scene_add_instance",
+    "gfxh_scene_add_material", "gfxh_scene_add_texture", "gfxh_scene_load_texture", "gfxh_scene_num_textures", "gfxh_scene_get_texture", "gfxh_scene_add_texture_bc", "gfxh_scene_get_texture_bc", "gfxh_dds_parse", "gfxh_image_info", "gfxh_image_decode_rgba8", "gfxh_tfdm_load_height", "gfxh_tfdm_free_height", "gfxh_scene_add_geom", "gfxh_scene_add_group", "gfxh_scene_add_instance",
     "gfxh_scene_load_obj", "gfxh_scene_load_obj_conv", "gfxh_scene_add_rectangle_textured", "gfxh_scene_add_rectangle", "gfxh_scene_make_street", "gfxh_scene_counts",
     "gfxh_scene_get_material", "gfxh_scene_get_geom", "gfxh_scene_get_group", "gfxh_scene_get_instance",
     "gfxh_scene_bounds", "gfxh_scene_upload", "gfxh_make_transform", "gfxh_make_orientation",
@@ -641,6 +642,27 @@ def make_camera(width, height, pos, roll=0.0, pitch=0.0, yaw=0.0, fov_y_deg=50.0
     lib().gfxh_make_orientation(C.c_float(roll), C.c_float(pitch), C.c_float(yaw), ori)
     cam.orientation = ori
     return cam
+
+
+def camera_rays(cam, width, height, tmin=0.0, tmax=3.0e38):
+    """Pinhole primary rays through the pixel centres of a gfx_camera (the camera model of restir_di_shared.h:51-59), row 0 first:
+    (origin | tmin, direction | tmax) float32 [width * height, 4] each, the layout gfx_trace and gfx_tfdm_trace take."""
+    ori = np.array(list(cam.orientation), np.float32).reshape(3, 3)
+    vh = np.float32(2 * np.tan(np.float32(cam.fovY) * np.float32(0.5)))
+    vw = np.float32(cam.aspect) * vh
+    xs = (np.arange(width, dtype=np.float32) + np.float32(0.5)) / np.float32(width)
+    ys = (np.arange(height, dtype=np.float32) + np.float32(0.5)) / np.float32(height)
+    X, Y = np.meshgrid(xs, ys)
+    local = np.stack([vw * (np.float32(0.5) - X), vh * (np.float32(0.5) - Y), np.ones_like(X)], -1).reshape(-1, 3)
+    d = local @ ori.T
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    org = np.zeros((width * height, 4), np.float32)
+    org[:, :3] = np.array(list(cam.position), np.float32)
+    org[:, 3] = tmin
+    dirs = np.zeros((width * height, 4), np.float32)
+    dirs[:, :3] = d
+    dirs[:, 3] = tmax
+    return org, dirs
 
 
 def band_plan(height, band_begin, band_end, radius_rows, num_spatial_passes, max_motion_rows=0):
@@ -1170,6 +1192,117 @@ class TemporalAA:
     def close(self):
         if self.h:
             self.L.gfx_taa_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+TFDM_BOX, TFDM_TWO_TRIANGLE = 0, 1
+TFDM_READ_PYRAMID, TFDM_READ_AABBS, TFDM_READ_RECORDS, TFDM_READ_NODES, TFDM_READ_HEIGHTS = range(5)
+TFDM_HIT_DTYPE = np.dtype([("dist", "<f4"), ("bcB", "<f4"), ("bcC", "<f4"), ("primIndex", "<u4"), ("normal", "<f4", 3), ("frontFace", "<u4")])
+TFDM_NODE_DTYPE = np.dtype([("lo", "<f4", 3), ("first", "<u4"), ("hi", "<f4", 3), ("count", "<u4")])
+TFDM_RECORD_BYTES = 192
+
+
+class GfxTfdmParams(C.Structure):
+    _fields_ = [("hOffset", C.c_float), ("hScale", C.c_float), ("hBias", C.c_float), ("texScale", C.c_float * 2), ("texRotation", C.c_float),
+                ("texOffset", C.c_float * 2), ("targetMipLevel", C.c_uint32), ("localIntersection", C.c_uint32)]
+
+
+class GfxTfdmHit(C.Structure):
+    _fields_ = [("dist", C.c_float), ("bcB", C.c_float), ("bcC", C.c_float), ("primIndex", C.c_uint32), ("normal", C.c_float * 3), ("frontFace", C.c_uint32)]
+
+
+def tfdm_params(h_offset=0.0, h_scale=1.0, h_bias=0.0, tex_scale=(1.0, 1.0), tex_rotation=0.0, tex_offset=(0.0, 0.0), target_mip_level=0,
+                local_intersection=TFDM_TWO_TRIANGLE):
+    """gfx_tfdm_params; tex_rotation in degrees."""
+    p = GfxTfdmParams()
+    lib().gfx_tfdm_default_params(C.byref(p))
+    p.hOffset, p.hScale, p.hBias, p.texRotation = h_offset, h_scale, h_bias, tex_rotation
+    p.texScale[0], p.texScale[1] = tex_scale
+    p.texOffset[0], p.texOffset[1] = tex_offset
+    p.targetMipLevel, p.localIntersection = int(target_mip_level), int(local_intersection)
+    return p
+
+
+def tfdm_load_height(path):
+    """gfxh_tfdm_load_height: float32 [size, size], the first channel of an image or .dds file as c / 255."""
+    size, ptr = C.c_uint32(), C.POINTER(C.c_float)()
+    if lib().gfxh_tfdm_load_height(os.fsencode(path), C.byref(size), C.byref(ptr)):
+        raise GfxError(lib().gfxh_last_error().decode(errors="replace"))
+    try:
+        return np.ctypeslib.as_array(ptr, shape=(size.value, size.value)).copy()
+    finally:
+        lib().gfxh_tfdm_free_height(ptr)
+
+
+class Tfdm:
+    """gfx_tfdm: a base mesh displaced by a height map, queried by rays without tessellation (csrc/tfdm/).  vertices: VERTEX_DTYPE
+    array; triangles: [n, 3] uint32; heights: one float32 [size, size] array (the library makes the mips) or the list of all
+    log2(size) + 1 levels.  Rays and results are device pointers (ints), in the layout of Context.trace."""
+
+    def __init__(self, ctx, vertices, triangles, heights, params=None, stream=0):
+        self.L = lib()
+        self.ctx = ctx
+        v = np.ascontiguousarray(vertices, VERTEX_DTYPE)
+        t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+        levels = [heights] if isinstance(heights, np.ndarray) else list(heights)
+        levels = [np.ascontiguousarray(a, np.float32) for a in levels]
+        if not levels or levels[0].ndim != 2 or levels[0].shape[0] != levels[0].shape[1]:
+            raise GfxError("Tfdm: the height map must be square (gfx_tfdm_create takes one size)")
+        self.size = int(levels[0].shape[0])
+        ptrs = (C.POINTER(C.c_float) * len(levels))(*[a.ctypes.data_as(C.POINTER(C.c_float)) for a in levels])
+        h = C.c_void_p()
+        ctx._check(self.L.gfx_tfdm_create(ctx.h, C.c_void_p(stream), _p(v), C.c_uint32(v.itemsize), C.c_uint32(len(v)), _p(t), C.c_uint32(len(t)),
+                                          ptrs, C.c_uint32(len(levels)), C.c_uint32(self.size), C.byref(params) if params is not None else None, C.byref(h)))
+        self.h = h
+        self.num_triangles = len(t)
+
+    def set_params(self, params, stream=0):
+        self.ctx._check(self.L.gfx_tfdm_set_params(self.ctx.h, C.c_void_p(stream), self.h, C.byref(params)))
+
+    def trace(self, mode, d_ray_org, d_ray_dir, num_rays, d_out, d_counters=0, stream=0):
+        """CLOSEST: d_out = TFDM_HIT_DTYPE[num_rays]; ANY: uint32[num_rays].  d_counters: device u64[4], added to."""
+        self.ctx._check(self.L.gfx_tfdm_trace(self.ctx.h, C.c_void_p(stream), self.h, C.c_int(mode), C.c_void_p(d_ray_org), C.c_void_p(d_ray_dir),
+                                              C.c_uint32(num_rays), C.c_void_p(d_out), C.c_void_p(d_counters or None)))
+
+    def size_of(self, what, level=0):
+        n = C.c_size_t()
+        self.ctx._check(self.L.gfx_tfdm_size(self.ctx.h, self.h, C.c_int(what), C.c_uint32(level), C.byref(n)))
+        return n.value
+
+    def device_bytes(self):
+        return self.size_of(-1)
+
+    def _read(self, what, level, dtype):
+        out = np.zeros(self.size_of(what, level), np.uint8)
+        self.ctx._check(self.L.gfx_tfdm_read(self.ctx.h, self.h, C.c_int(what), C.c_uint32(level), _p(out), C.c_size_t(out.nbytes)))
+        return out.view(dtype)
+
+    def read_pyramid(self, level):
+        w = self.size >> level
+        return self._read(TFDM_READ_PYRAMID, level, np.float32).reshape(w, w, 2)
+
+    def read_heights(self, level):
+        w = self.size >> level
+        return self._read(TFDM_READ_HEIGHTS, level, np.float32).reshape(w, w)
+
+    def read_aabbs(self):
+        return self._read(TFDM_READ_AABBS, 0, np.float32).reshape(-1, 6)
+
+    def read_records(self):
+        return self._read(TFDM_READ_RECORDS, 0, np.uint8).reshape(-1, TFDM_RECORD_BYTES)
+
+    def read_nodes(self):
+        return self._read(TFDM_READ_NODES, 0, TFDM_NODE_DTYPE)
+
+    def close(self):
+        if self.h:
+            self.L.gfx_tfdm_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -9,12 +9,14 @@
 #include "denoise/denoise.h"
 #include "denoise/taa.h"
 #include "bc/bc_textures.h"
+#include "tfdm/tfdm.h"
 
 using namespace gfx;
 
 struct gfx_ctx { Context c; };
 struct gfx_denoiser { Denoiser d; };
 struct gfx_taa { TemporalAA t; };
+struct gfx_tfdm { TfdmObject o; };
 
 static thread_local std::string g_createError;
 
@@ -714,6 +716,64 @@ int gfx_bc_expand(gfx_ctx* ctx, void* stream, uint32_t bcFormat, const void* dBl
     GFX_TRY(ctx)
     if (!dBlocks || !dTexels) throw HipError("gfx_bc_expand: null pointer");
     bc_expand_launch(static_cast<hipStream_t>(stream), bcFormat, dBlocks, width, height, format, dTexels);
+    GFX_CATCH(ctx)
+}
+
+int gfx_tfdm_default_params(gfx_tfdm_params* out) {
+    if (!out) return 1;
+    tfdm_default_params(out);
+    return 0;
+}
+int gfx_tfdm_create(gfx_ctx* ctx, void* stream, const void* vertices, uint32_t stride, uint32_t numVertices, const uint32_t* triangles, uint32_t numTriangles,
+                    const float* const* heightLevels, uint32_t numLevels, uint32_t size, const gfx_tfdm_params* params, gfx_tfdm** out) {
+    GFX_TRY(ctx)
+    if (!out) throw HipError("gfx_tfdm_create: null output handle");
+    *out = nullptr;
+    gfx_tfdm_params p;
+    if (params) p = *params;
+    else tfdm_default_params(&p);
+    std::unique_ptr<gfx_tfdm> t(new gfx_tfdm());
+    t->o.device = ctx->c.device;
+    try { tfdm_init(t->o, static_cast<hipStream_t>(stream), vertices, stride, numVertices, triangles, numTriangles, heightLevels, numLevels, size, p); }
+    catch (...) { tfdm_release(t->o); throw; }
+    *out = t.release();
+    GFX_CATCH(ctx)
+}
+int gfx_tfdm_set_params(gfx_ctx* ctx, void* stream, gfx_tfdm* obj, const gfx_tfdm_params* params) {
+    GFX_TRY(ctx)
+    if (!obj || !params) throw HipError("gfx_tfdm_set_params: null object or parameters");
+    if (obj->o.device != ctx->c.device) throw HipError("gfx_tfdm_set_params: the object belongs to another device");
+    tfdm_set_params(obj->o, static_cast<hipStream_t>(stream), *params);
+    GFX_CATCH(ctx)
+}
+int gfx_tfdm_destroy(gfx_tfdm* obj) {
+    if (!obj) return 1;
+    int prev = -1;
+    const bool switched = hipGetDevice(&prev) == hipSuccess && prev != obj->o.device && hipSetDevice(obj->o.device) == hipSuccess;
+    (void)hipDeviceSynchronize();
+    tfdm_release(obj->o);
+    if (switched) (void)hipSetDevice(prev);
+    delete obj;
+    return 0;
+}
+int gfx_tfdm_trace(gfx_ctx* ctx, void* stream, gfx_tfdm* obj, int mode, const void* dRayOrgTmin, const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters) {
+    GFX_TRY(ctx)
+    if (!obj) throw HipError("gfx_tfdm_trace: null object");
+    if (obj->o.device != ctx->c.device) throw HipError("gfx_tfdm_trace: the object belongs to another device");
+    ScopedKernelTimer timer(ctx->c, static_cast<hipStream_t>(stream), "k_tfdm_trace");
+    tfdm_trace(obj->o, static_cast<hipStream_t>(stream), mode, dRayOrgTmin, dRayDirTmax, numRays, dOut, dCounters);
+    GFX_CATCH(ctx)
+}
+int gfx_tfdm_read(gfx_ctx* ctx, gfx_tfdm* obj, int what, uint32_t level, void* hostOut, size_t bytes) {
+    GFX_TRY(ctx)
+    if (!obj) throw HipError("gfx_tfdm_read: null object");
+    tfdm_read(obj->o, what, level, hostOut, bytes);
+    GFX_CATCH(ctx)
+}
+int gfx_tfdm_size(gfx_ctx* ctx, gfx_tfdm* obj, int what, uint32_t level, size_t* bytes) {
+    GFX_TRY(ctx)
+    if (!obj || !bytes) throw HipError("gfx_tfdm_size: null object or output");
+    *bytes = tfdm_size(obj->o, what, level);
     GFX_CATCH(ctx)
 }
 

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cctype>
 #include <cstring>
 #include <fstream>
@@ -22,6 +23,8 @@
 #include <vector>
 #include "../../../include/gfxexp_host.h"
 #include "image_codecs.h"
+#include <hip/hip_runtime.h>          // the function attributes of bc_decode.hip.h (the build sends this file through hipcc)
+#include "../bc/bc_decode.hip.h"
 
 namespace {
 
@@ -693,6 +696,65 @@ uint32_t gfxh_scene_load_texture(gfxh_scene* s, const char* path, uint32_t forma
     if (slot) s->textureCache[key] = slot;
     return slot;
 }
+
+extern "C++" {
+namespace {
+template <uint32_t F>
+void bc_first_channel(const uint8_t* blocks, uint32_t w, uint32_t h, std::vector<uint8_t>& out) {
+    for (uint32_t y = 0; y < h; ++y)
+        for (uint32_t x = 0; x < w; ++x) out[static_cast<size_t>(y) * w + x] = static_cast<uint8_t>(gfx::bc::image_texel<F>(blocks, w, x, y) & 0xFFu);
+}
+}
+} // extern "C++"
+
+// The height texture of tfdm_main.cpp:2218-2255 as gfx_tfdm_create takes it: first channel, c / 255.
+int gfxh_tfdm_load_height(const char* path, uint32_t* size, float** heights) {
+    if (!path || !size || !heights) { g_hostError = "gfxh_tfdm_load_height: null argument"; return 1; }
+    *size = 0; *heights = nullptr;
+    uint32_t w = 0, h = 0;
+    std::vector<uint8_t> first;
+    try {
+        if (is_dds_path(path)) {
+            std::vector<uint8_t> file;
+            gfxh_dds_info info;
+            if (!read_file(path, file)) { g_hostError = std::string("cannot open ") + path; return 1; }
+            if (gfxh_dds_parse(file.data(), file.size(), &info)) { g_hostError += std::string(": ") + path; return 1; }
+            w = info.width; h = info.height;
+            first.resize(static_cast<size_t>(w) * h);
+            const uint8_t* data = file.data() + info.dataOffset;
+            if (!info.isBlockCompressed) for (size_t i = 0; i < first.size(); ++i) first[i] = data[4 * i + (info.isBGRA ? 2 : 0)];
+            else switch (info.bcFormat) {
+                case GFX_BC1: bc_first_channel<gfx::bc::kBC1>(data, w, h, first); break;
+                case GFX_BC2: bc_first_channel<gfx::bc::kBC2>(data, w, h, first); break;
+                case GFX_BC3: bc_first_channel<gfx::bc::kBC3>(data, w, h, first); break;
+                case GFX_BC4_UNORM: bc_first_channel<gfx::bc::kBC4U>(data, w, h, first); break;
+                case GFX_BC4_SNORM: bc_first_channel<gfx::bc::kBC4S>(data, w, h, first); break;
+                case GFX_BC5_UNORM: bc_first_channel<gfx::bc::kBC5U>(data, w, h, first); break;
+                case GFX_BC5_SNORM: bc_first_channel<gfx::bc::kBC5S>(data, w, h, first); break;
+                case GFX_BC7: bc_first_channel<gfx::bc::kBC7>(data, w, h, first); break;
+                default: g_hostError = std::string("gfxh_tfdm_load_height: unknown block format in ") + path; return 1;
+            }
+        }
+        else {
+            Image img; std::string err;
+            if (!decode_image(path, img, err)) { g_hostError = err; return 1; }
+            if (img.isFloat) { g_hostError = std::string("gfxh_tfdm_load_height: a float image is no 8-bit height map: ") + path; return 1; }
+            w = img.w; h = img.h;
+            first.resize(static_cast<size_t>(w) * h);
+            for (size_t i = 0; i < first.size(); ++i) first[i] = img.rgba8[4 * i];
+        }
+    }
+    catch (const std::exception& e) { g_hostError = std::string("gfxh_tfdm_load_height: ") + e.what(); return 1; }
+    // tfdm_main.cpp:2236-2239
+    if (w != h) { g_hostError = std::string("gfxh_tfdm_load_height: the height map is not square: ") + path; return 1; }
+    if (w == 0 || (w & (w - 1u)) != 0u) { g_hostError = std::string("gfxh_tfdm_load_height: the height map's size is no power of two: ") + path; return 1; }
+    float* out = static_cast<float*>(std::malloc(sizeof(float) * first.size()));
+    if (!out) { g_hostError = "gfxh_tfdm_load_height: out of memory"; return 1; }
+    for (size_t i = 0; i < first.size(); ++i) out[i] = static_cast<float>(first[i]) / 255.0f;
+    *size = w; *heights = out;
+    return 0;
+}
+void gfxh_tfdm_free_height(float* heights) { std::free(heights); }
 
 uint32_t gfxh_scene_add_geom(gfxh_scene* s, const gfx_vertex* v, uint32_t nv, const uint32_t* tris, uint32_t nt, uint32_t matSlot) {
     Geom g;

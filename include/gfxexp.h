@@ -718,6 +718,60 @@ int gfx_stream_copy(gfx_ctx* ctx, void* dDst, const void* dSrc, size_t bytes, vo
  * packed).  tools/bench_bc_expand.py times it with HIP events; no renderer calls it. */
 int gfx_bc_expand(gfx_ctx* ctx, void* stream, uint32_t bcFormat, const void* dBlocks, uint32_t width, uint32_t height, uint32_t format, void* dTexels);
 
+/* ---------------------------------------------------------------- tessellation-free displacement mapping (TFDM) ----------
+ * A height map displaces a base triangle mesh along its interpolated vertex normals; rays are intersected with the displaced
+ * surface without building its micro-triangles, by descending a min-max pyramid of the map with affine-arithmetic bounds
+ * (the reference's tfdm/ program).  The query stands next to gfx_trace: rays are given in the object
+ * space of the base mesh, in gfx_trace's layout (origin | tmin, direction | tmax), and a ray's tmax lets the caller chain
+ * the query behind gfx_trace for a scene that mixes plain and displaced geometry: trace the plain geometry first, hand its
+ * hit distance in as tmax, and a displaced hit that comes back is the closer one.  Displaced primitives inside the scene
+ * BVH8 and the renderers are not part of this interface. */
+typedef struct gfx_tfdm gfx_tfdm;                       /* opaque; owns heights, pyramid, records, AABBs, tree */
+enum gfx_tfdm_local { GFX_TFDM_BOX = 0, GFX_TFDM_TWO_TRIANGLE = 1 };   /* LocalIntersectionType, tfdm/tfdm_shared.h; Bilinear and BSpline are not built */
+/* DisplacementParameters, tfdm/tfdm_shared.h, with the texture transform as the scale / rotation (degrees) / offset it is made
+ * from (tfdm_main.cpp:2580-2588).  The height of a map value h is hOffset + preScale * hScale * (h - hBias) with preScale =
+ * 1 / sqrt(texScale[0] * texScale[1]) (tfdm_intersection_kernels.h:54-59).  targetMipLevel: the map level whose texels are
+ * intersected (0 = the finest).  A transformed texture coordinate times the map's size must stay below 2^24 in magnitude (texel
+ * indices are exact as floats up to there); gfx_tfdm_create and gfx_tfdm_set_params refuse anything beyond, a texOffset of 3e5
+ * for example -- reduce it modulo 1. */
+typedef struct gfx_tfdm_params { float hOffset, hScale, hBias; float texScale[2], texRotation, texOffset[2];
+                                 uint32_t targetMipLevel, localIntersection; } gfx_tfdm_params;
+/* closest-hit record of gfx_tfdm_trace (DisplacedSurfaceAttributes + the hit kind, tfdm_intersection_kernels.h:537-561), 32 B.
+ * bcB / bcC are barycentrics on the BASE triangle primIndex; normal is the unit normal of the displaced surface in object space.
+ * Miss: dist = the ray's tmax, primIndex = GFX_INVALID_SLOT, the rest zero. */
+typedef struct gfx_tfdm_hit { float dist, bcB, bcC; uint32_t primIndex; float normal[3]; uint32_t frontFace; } gfx_tfdm_hit;
+/* hOffset 0, hScale 1, hBias 0, unit texture transform, level 0, two triangles per texel. */
+int gfx_tfdm_default_params(gfx_tfdm_params* out);
+/* tfdm_main.cpp:2218-2255 (the height sampler and its mips), :2492-2545 (the pyramid launches and computeAABBs), :780-843 (the
+ * per-triangle matrices).  vertices / triangles are host arrays as for gfx_geom_create (stride >= sizeof(gfx_vertex); position,
+ * normal and texCoord are used); heightLevels are host arrays of fp32 heights in [0, 1], level k of (size >> k)^2 texels, rows
+ * tightly packed.  numLevels is 1 (the library makes the coarser levels by the 2 x 2 mean ((a + b) + (c + d)) * 0.25f) or
+ * log2(size) + 1.  The map is square and `size` a power of two up to 8192, as the reference demands (tfdm_main.cpp:2236-2239);
+ * 1 <= numTriangles <= 2^20.  Anything else is refused with a message. */
+int gfx_tfdm_create(gfx_ctx* ctx, void* stream, const void* vertices, uint32_t stride, uint32_t numVertices,
+                    const uint32_t* triangles, uint32_t numTriangles,
+                    const float* const* heightLevels, uint32_t numLevels, uint32_t size,
+                    const gfx_tfdm_params* params, gfx_tfdm** out);
+/* New parameters for an object (the GUI edits of tfdm_main.cpp:2576-2600): records, AABBs and the tree are made again, the
+ * pyramid is kept.  A refused call leaves the object as it was. */
+int gfx_tfdm_set_params(gfx_ctx* ctx, void* stream, gfx_tfdm* obj, const gfx_tfdm_params* params);
+int gfx_tfdm_destroy(gfx_tfdm* obj);
+/* One ray per entry, optixTrace against the custom-primitive GAS of the reference (tfdm_intersection_kernels.h:16-35 for the
+ * per-triangle boxes, :39-562 for the surface).  mode GFX_TRACE_CLOSEST: dOut = gfx_tfdm_hit[numRays]; GFX_TRACE_ANY: dOut =
+ * uint32_t[numRays] (1 = occluded).  Closest-hit ties on the distance go to the lower primitive index.  dCounters (optional,
+ * device u64[4], added to): texel AABB tests, leaf (local intersection) tests, rays, base triangles tested -- the reference's
+ * TraversalStats (tfdm_shared.h) and one more.  dRayOrgTmin, dRayDirTmax and a closest-hit dOut must be 16-byte aligned (they
+ * are read and written as float4), an any-hit dOut 4-byte, dCounters 8-byte; a misaligned pointer is refused. */
+int gfx_tfdm_trace(gfx_ctx* ctx, void* stream, gfx_tfdm* obj, int mode, const void* dRayOrgTmin, const void* dRayDirTmax,
+                   uint32_t numRays, void* dOut, void* dCounters);
+/* Inspection.  PYRAMID: level `level` as (min, max) float pairs, (size >> level)^2 of them; HEIGHTS: that level of the height
+ * map; AABBS: six floats (min, max) per triangle; RECORDS: the 192-byte per-triangle records; NODES: the 32-byte tree nodes
+ * (csrc/tfdm/tfdm_core.hip.h).  `bytes` must be the exact size (gfx_tfdm_size). */
+enum gfx_tfdm_read_what { GFX_TFDM_READ_PYRAMID = 0, GFX_TFDM_READ_AABBS = 1, GFX_TFDM_READ_RECORDS = 2, GFX_TFDM_READ_NODES = 3, GFX_TFDM_READ_HEIGHTS = 4 };
+int gfx_tfdm_read(gfx_ctx* ctx, gfx_tfdm* obj, int what, uint32_t level, void* hostOut, size_t bytes);
+/* Size in bytes of what gfx_tfdm_read(what, level) returns; with what = -1 the device bytes the object owns in all. */
+int gfx_tfdm_size(gfx_ctx* ctx, gfx_tfdm* obj, int what, uint32_t level, size_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,6 +85,14 @@ int gfxh_image_info(const void* data, size_t bytes, gfxh_image_desc* info);
 /* Decodes into out[0, 4 * width * height); capacityBytes below that is an error.  Never reads outside data[0, bytes). */
 int gfxh_image_decode_rgba8(const void* data, size_t bytes, void* out, size_t capacityBytes);
 
+/* A height map for gfx_tfdm_create (the height texture of tfdm_main.cpp:2218-2255): the first channel of a .png / .jpg / .tga /
+ * .bmp / .ppm / .pgm file or of level 0 of a .dds (BC1-BC5, BC7 decoded on the host by the expansion kernels' own decoder, or
+ * uncompressed 32-bit), as c / 255 in fp32, row 0 first.  *heights is size * size floats from malloc, to be handed back to
+ * gfxh_tfdm_free_height.  Maps that are not square or whose size is no power of two are refused (tfdm_main.cpp:2236-2239), and so
+ * are float images.  Returns 1 with a gfxh_last_error that names the cause. */
+int gfxh_tfdm_load_height(const char* path, uint32_t* size, float** heights);
+void gfxh_tfdm_free_height(float* heights);
+
 /* Geometry / groups / instances (return slot indices). */
 uint32_t gfxh_scene_add_geom(gfxh_scene* s, const gfx_vertex* v, uint32_t nv, const uint32_t* tris, uint32_t nt, uint32_t matSlot);
 uint32_t gfxh_scene_add_group(gfxh_scene* s, const uint32_t* geomSlots, uint32_t n);

@@ -1,0 +1,128 @@
+"""gfx_tfdm_trace against the only other way to trace a height-mapped surface, the tessellated mesh in the scene BVH8.
+
+    python tools/bench_tfdm.py [--size 1024] [--iters 20] [--width 1920] [--height 1080] [--step-timeout 300]
+
+1920 x 1080 primary rays on a procedural size x size height map: on the unit quad and on the teapot (15 704 base triangles), for
+the Box and the TwoTriangle local intersection at map levels 0 and 2; and the same quad rays through gfx_trace on the quad
+tessellated to 2 x size x size triangles.  Per variant: microseconds per launch (HIP events around --iters launches after a
+warm-up), Mrays/s, texel AABB tests / leaf tests / base triangles per ray from a counting launch of its own, and the device bytes
+of either representation.  Prints one JSON line.
+
+Every GPU step is a child process of its own under a time limit (--step-timeout seconds); the first step that fails or runs out of
+time ends the run, and nothing more is started on the GPU after it."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+
+STEPS = ["tfdm_quad", "tfdm_teapot", "mesh_quad"]
+VARIANTS = [("two_triangle_l0", 1, 0), ("two_triangle_l2", 1, 2), ("box_l0", 0, 0), ("box_l2", 0, 2)]
+
+
+def _arg(argv, name, default):
+    return type(default)(argv[argv.index(name) + 1]) if name in argv else default
+
+
+def timed(fn, iters, warmup=3):
+    import torch
+    for _ in range(warmup):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e-3 / iters
+
+
+def step(name, size, iters, w, h):
+    import torch
+    from gfxexp_amd import api
+    import tfdm_common as K
+    heights = K.procedural_map(size)
+    mesh = "teapot" if name == "tfdm_teapot" else "quad"
+    v, t, pos, target, up = K.base_mesh(mesh)
+    h_scale = 0.05 * K.extent(v) if mesh == "quad" else 0.01 * K.extent(v)
+    org, dirs = api.camera_rays(K.look_at_camera(w, h, pos, target, up=up), w, h)
+    n = w * h
+    d_org, d_dir = torch.from_numpy(org).cuda(), torch.from_numpy(dirs).cuda()
+    d_out = torch.zeros(n * 8, dtype=torch.int32, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    ctx = api.Context(0)
+    out = {"base_triangles": int(len(t)), "rays": n}
+    if name == "mesh_quad":
+        mv, mt = K.tessellated_quad(heights, h_scale)
+        s = api.HostScene()
+        g = s.add_geom(mv, mt, s.add_material_traditional((0.5, 0.5, 0.5), (0, 0, 0), 0.3))
+        s.add_instance(s.add_group([g]), api.make_transform())
+        s.upload(ctx)
+        accel = ctx.accel_build()
+        st = ctx.accel_stats(accel)
+        secs = timed(lambda: ctx.trace(accel, api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), stream=stream), iters)
+        hits = d_out.cpu().numpy().view(api.HIT_DTYPE)[:n]
+        d_cnt = torch.zeros(4, dtype=torch.int64, device="cuda")
+        ctx.trace(accel, api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), d_counters=d_cnt.data_ptr(), stream=stream)
+        torch.cuda.synchronize()
+        cnt = d_cnt.cpu().numpy()
+        # 64-byte nodes and triangle records, a 16-byte link per node, 12 bytes of ids per record; and the scene's own vertex / index buffers
+        out.update({"triangles": int(len(mt)), "us": round(secs * 1e6, 1), "Mrays_per_s": round(n / secs / 1e6, 1),
+                    "hit_share": round(float((hits["triIndex"] != api.GFX_INVALID_SLOT).mean()), 4),
+                    "bvh_bytes": int(st["nodes"] * (64 + 16) + st["triRecords"] * (64 + 12)), "scene_geometry_bytes": int(mv.nbytes + mt.nbytes),
+                    "node_fetches_per_ray": round(float(cnt[0]) / n, 2), "triangle_fetches_per_ray": round(float(cnt[1]) / n, 2)})
+        return out
+    out["variants"] = {}
+    tf = None
+    for vname, local, level in VARIANTS:
+        gp = api.tfdm_params(h_scale=h_scale, target_mip_level=level, local_intersection=local)
+        if tf is None:
+            tf = api.Tfdm(ctx, v, t, heights, gp)
+        else:
+            tf.set_params(gp)
+        secs = timed(lambda: tf.trace(api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), stream=stream), iters)
+        hits = d_out.cpu().numpy().view(api.TFDM_HIT_DTYPE)[:n]
+        d_cnt = torch.zeros(4, dtype=torch.int64, device="cuda")
+        tf.trace(api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), d_cnt.data_ptr(), stream=stream)
+        torch.cuda.synchronize()
+        cnt = d_cnt.cpu().numpy()
+        out["variants"][vname] = {"us": round(secs * 1e6, 1), "Mrays_per_s": round(n / secs / 1e6, 1),
+                                  "hit_share": round(float((hits["primIndex"] != api.GFX_INVALID_SLOT).mean()), 4),
+                                  "aabb_tests_per_ray": round(float(cnt[0]) / n, 2), "leaf_tests_per_ray": round(float(cnt[1]) / n, 2),
+                                  "base_triangles_per_ray": round(float(cnt[3]) / n, 2)}
+    out["device_bytes"] = tf.device_bytes()
+    out["pyramid_and_heights_bytes"] = tf.size_of(api.TFDM_READ_PYRAMID, 0) * 4 // 3 + tf.size_of(api.TFDM_READ_HEIGHTS, 0) * 4 // 3
+    return out
+
+
+def main(argv):
+    size, iters = _arg(argv, "--size", 1024), _arg(argv, "--iters", 20)
+    w, h = _arg(argv, "--width", 1920), _arg(argv, "--height", 1080)
+    if "--step" in argv:
+        print("STEP_RESULT " + json.dumps(step(argv[argv.index("--step") + 1], size, iters, w, h)))
+        return 0
+    limit = _arg(argv, "--step-timeout", 300)
+    result = {"metric": "tfdm_trace", "size": size, "iters": iters, "width": w, "height": h}
+    for name in STEPS:
+        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name, "--size", str(size), "--iters", str(iters),
+               "--width", str(w), "--height", str(h)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("STEP_RESULT ")]
+        if r.returncode != 0 or not line:
+            result["failed_step"] = {"name": name, "exit_status": r.returncode, "stderr_tail": r.stderr[-2000:]}
+            print(json.dumps(result))
+            return 1
+        result[name] = json.loads(line[-1][len("STEP_RESULT "):])
+    q, m = result["tfdm_quad"], result["mesh_quad"]
+    result["memory_ratio_mesh_over_tfdm"] = round((m["bvh_bytes"] + m["scene_geometry_bytes"]) / q["device_bytes"], 2)
+    print(json.dumps(result))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))

@@ -1,0 +1,88 @@
+"""Shared by tools/tfdm_view.py, tools/bench_tfdm.py and the TFDM tests: procedural height maps, the base meshes, a look-at camera."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from gfxexp_amd import api
+
+ASSETS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "assets")
+
+
+def procedural_map(n):
+    """Two sines and a ripple, quantised to 8 bits like a height texture: float32 c / 255, [n, n]."""
+    y, x = np.mgrid[0:n, 0:n]
+    h = 0.5 + 0.25 * np.sin(2 * np.pi * 3 * x / n) * np.cos(2 * np.pi * 2 * y / n) + 0.2 * np.sin(2 * np.pi * (5 * x + 7 * y) / n) \
+        + 0.04 * np.sin(2 * np.pi * 37 * x / n) * np.sin(2 * np.pi * 41 * y / n)
+    return (np.round(np.clip(h, 0, 1) * 255).astype(np.float32) / np.float32(255)).astype(np.float32)
+
+
+def quad_mesh():
+    """Unit quad in z = 0, normal +z, uv = xy, split along the TL-BR diagonal: TL TR BR, TL BR BL."""
+    v = np.zeros(4, api.VERTEX_DTYPE)
+    v["position"] = [(0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0)]
+    v["normal"] = (0, 0, 1)
+    v["texCoord0Dir"] = (1, 0, 0)
+    v["texCoord"] = [(0, 0), (1, 0), (1, 1), (0, 1)]
+    return v, np.array([[0, 1, 2], [0, 2, 3]], np.uint32)
+
+
+def obj_mesh(name):
+    s = api.HostScene()
+    s.load_obj(os.path.join(ASSETS, name))
+    vs, ts, base = [], [], 0
+    for v, t, _ in s.geoms():
+        vs.append(v)
+        ts.append(t + base)
+        base += len(v)
+    return np.concatenate(vs), np.concatenate(ts).astype(np.uint32)
+
+
+def base_mesh(name):
+    """(vertices, triangles, camera position, look-at point, up)"""
+    if name == "quad":
+        v, t = quad_mesh()
+        return v, t, (0.5, -0.75, 0.8), (0.5, 0.45, 0.0), (0, 0, 1)
+    v, t = obj_mesh({"bunny": "stanford_bunny_309_faces.obj", "teapot": "teapot.obj"}[name])
+    lo, hi = v["position"].min(0).astype(np.float64), v["position"].max(0).astype(np.float64)
+    c, r = 0.5 * (lo + hi), 0.5 * float(np.linalg.norm(hi - lo))
+    return v, t, tuple(c + np.array([0.6, 0.9, 2.0]) * r), tuple(c), (0, 1, 0)
+
+
+def extent(v):
+    return float((v["position"].max(0) - v["position"].min(0)).max())
+
+
+def look_at_camera(width, height, pos, target, fov_y_deg=42.0, up=(0, 0, 1)):
+    """A gfx_camera at `pos` looking at `target` (orientation columns: left, up, forward)."""
+    f = np.asarray(target, np.float64) - np.asarray(pos, np.float64)
+    f /= np.linalg.norm(f)
+    left = np.cross(np.asarray(up, np.float64), f)
+    left /= np.linalg.norm(left)
+    cam = api.GfxCamera()
+    cam.aspect = float(width) / float(height)
+    cam.fovY = float(np.radians(fov_y_deg))
+    cam.position = (C.c_float * 3)(*[float(x) for x in pos])
+    cam.orientation = (C.c_float * 9)(*np.stack([left, np.cross(f, left), f], axis=1).astype(np.float32).reshape(9).tolist())
+    return cam
+
+
+def tessellated_quad(heights, h_scale):
+    """The displaced unit quad of quad_mesh() as ordinary triangles, two per texel (TL TR BR, TL BR BL): corner heights are the mean of
+    the four texels around the corner with repeat wrap, as the query samples them."""
+    n = heights.shape[0]
+    h = heights.astype(np.float64)
+    i = np.arange(n + 1)
+    a, b = (i - 1) % n, i % n
+    corner = 0.25 * (h[np.ix_(a, a)] + h[np.ix_(a, b)] + h[np.ix_(b, a)] + h[np.ix_(b, b)])
+    gy, gx = np.mgrid[0:n + 1, 0:n + 1]
+    v = np.zeros((n + 1) * (n + 1), api.VERTEX_DTYPE)
+    v["position"] = np.stack([gx.ravel() / n, gy.ravel() / n, (h_scale * corner).ravel()], 1)
+    v["normal"] = (0, 0, 1)
+    v["texCoord0Dir"] = (1, 0, 0)
+    v["texCoord"] = np.stack([gx.ravel() / n, gy.ravel() / n], 1)
+    y, x = np.mgrid[0:n, 0:n]
+    tl = (y * (n + 1) + x).ravel()
+    tr, bl, br = tl + 1, tl + n + 1, tl + n + 2
+    t = np.concatenate([np.stack([tl, tr, br], 1), np.stack([tl, br, bl], 1)]).astype(np.uint32)
+    return v, t
