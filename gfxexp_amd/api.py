@@ -212,7 +212,7 @@ def abi_mirrors():
             "gfxh_nrc_config": GfxhNrcConfig, "gfxh_sdr_config": GfxhSdrConfig,
             "gfx_denoiser_settings": GfxDenoiserSettings, "gfx_denoiser_inputs": GfxDenoiserInputs,
             "gfx_denoiser_history_buffers": GfxDenoiserHistoryBuffers, "gfx_taa_inputs": GfxTaaInputs, "gfxh_dds_info": GfxhDdsInfo,
-            "gfxh_image_desc": GfxhImageDesc, "gfx_tfdm_params": GfxTfdmParams, "gfx_tfdm_hit": GfxTfdmHit}
+            "gfxh_image_desc": GfxhImageDesc, "gfx_tfdm_params": GfxTfdmParams, "gfx_tfdm_hit": GfxTfdmHit, "gfx_scene_hit": GfxSceneHit}
 
 
 class RcclExchange:
@@ -328,6 +328,7 @@ C_ABI_SYMBOLS = [
     "gfx_read_device", "gfx_timing_enable", "gfx_timing_collect", "gfx_counters_enable", "gfx_counters_read", "gfx_trace_diag_read", "gfx_pt_diag_read",
     "gfx_tunable_set", "gfx_stream_copy", "gfx_bc_expand",
     "gfx_tfdm_default_params", "gfx_tfdm_create", "gfx_tfdm_set_params", "gfx_tfdm_destroy", "gfx_tfdm_trace", "gfx_tfdm_read", "gfx_tfdm_size",
+    "gfx_tfdm_set_create", "gfx_tfdm_set_add", "gfx_tfdm_set_transform", "gfx_tfdm_set_commit", "gfx_tfdm_set_read", "gfx_tfdm_set_destroy", "gfx_trace_scene",
 ]
 HOST_ABI_SYMBOLS = [
     "gfxh_scene_create", "gfxh_scene_destroy", "gfxh_last_error", "gfxh_scene_add_material_traditional",
@@ -1310,6 +1311,81 @@ class Tfdm:
             self.close()
         except Exception:
             pass
+
+
+SCENE_PLAIN = 0x80000000
+SCENE_HIT_DTYPE = np.dtype([("dist", "<f4"), ("bcB", "<f4"), ("bcC", "<f4"), ("index", "<u4"), ("normal", "<f4", 3), ("where", "<u4")])
+TFDM_INSTANCE_DTYPE = np.dtype([("objToWorld", "<f4", 12), ("worldToObj", "<f4", 12), ("boxLo", "<f4", 3), ("userId", "<u4"), ("boxHi", "<f4", 3), ("pad0", "<u4"),
+                                ("nodes", "<u8"), ("records", "<u8"), ("heights", "<u8"), ("pyramid", "<u8"), ("params", "<u4", 8)])
+TFDM_SET_MAX_INSTANCES = 1024
+
+
+class GfxSceneHit(C.Structure):
+    _fields_ = [("dist", C.c_float), ("bcB", C.c_float), ("bcC", C.c_float), ("index", C.c_uint32), ("normal", C.c_float * 3), ("where", C.c_uint32)]
+
+
+def _xfm12(m):
+    x = np.ascontiguousarray(m, np.float32).reshape(-1)
+    if x.size == 16:
+        x = x[:12]
+    if x.size != 12:
+        raise GfxError("a transform is 12 floats (row-major 3 x 4)")
+    return np.ascontiguousarray(x)
+
+
+class TfdmSet:
+    """gfx_tfdm_set: Tfdm objects under object-to-world transforms (row-major 3 x 4, or a 4 x 4 whose last row is dropped), the
+    displaced instances of trace_scene.  commit() before the first query, and again after add / set_transform / a member's
+    Tfdm.set_params.  The set keeps its members alive."""
+
+    def __init__(self, ctx):
+        self.L = lib()
+        self.ctx = ctx
+        self.objects = []
+        h = C.c_void_p()
+        ctx._check(self.L.gfx_tfdm_set_create(ctx.h, C.byref(h)))
+        self.h = h
+
+    def __len__(self):
+        return len(self.objects)
+
+    def add(self, obj, obj_to_world, user_id=0):
+        x = _xfm12(obj_to_world)
+        index = C.c_uint32()
+        self.ctx._check(self.L.gfx_tfdm_set_add(self.h, obj.h, _p(x), C.c_uint32(user_id), C.byref(index)))
+        self.objects.append(obj)
+        return index.value
+
+    def set_transform(self, index, obj_to_world):
+        x = _xfm12(obj_to_world)
+        self.ctx._check(self.L.gfx_tfdm_set_transform(self.h, C.c_uint32(index), _p(x)))
+
+    def commit(self, stream=0):
+        self.ctx._check(self.L.gfx_tfdm_set_commit(self.ctx.h, C.c_void_p(stream), self.h))
+
+    def read(self):
+        """The committed InstanceRecord table (TFDM_INSTANCE_DTYPE)."""
+        out = np.zeros(len(self.objects), TFDM_INSTANCE_DTYPE)
+        self.ctx._check(self.L.gfx_tfdm_set_read(self.ctx.h, self.h, _p(out), C.c_size_t(out.nbytes)))
+        return out
+
+    def close(self):
+        if self.h:
+            self.L.gfx_tfdm_set_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def trace_scene(ctx, accel, tfdm_set, mode, d_ray_org, d_ray_dir, num_rays, d_out, d_counters=0, stream=0):
+    """gfx_trace_scene: world rays against the BVH8 `accel` (0: none) and the displaced instances of `tfdm_set` (None: none).
+    CLOSEST: d_out = SCENE_HIT_DTYPE[num_rays]; ANY: uint32[num_rays].  d_counters: device u64[8], added to."""
+    ctx._check(lib().gfx_trace_scene(ctx.h, C.c_void_p(stream), C.c_uint64(accel or 0), tfdm_set.h if tfdm_set is not None else None, C.c_int(mode),
+                                     C.c_void_p(d_ray_org), C.c_void_p(d_ray_dir), C.c_uint32(num_rays), C.c_void_p(d_out), C.c_void_p(d_counters or None)))
 
 
 class RestirRenderer:

@@ -10,13 +10,18 @@
 #include "denoise/taa.h"
 #include "bc/bc_textures.h"
 #include "tfdm/tfdm.h"
+#include "tfdm/tfdm_set.h"
 
 using namespace gfx;
 
-struct gfx_ctx { Context c; };
+struct gfx_ctx {
+    Context c;
+    DevBuf scenePlain;      // gfx_hit[numRays]: the plain phase of a closest-hit gfx_trace_scene without an instance set (tfdm_set.hip)
+};
 struct gfx_denoiser { Denoiser d; };
 struct gfx_taa { TemporalAA t; };
 struct gfx_tfdm { TfdmObject o; };
+struct gfx_tfdm_set { TfdmSet s; gfx_ctx* ctx; };
 
 static thread_local std::string g_createError;
 
@@ -88,6 +93,7 @@ void gfx_ctx_destroy(gfx_ctx* ctx) {
     if (!ctx) return;
     (void)hipDeviceSynchronize();
     bc_textures_drop(ctx->c);
+    ctx->scenePlain.release();
     delete ctx;
 }
 
@@ -774,6 +780,61 @@ int gfx_tfdm_size(gfx_ctx* ctx, gfx_tfdm* obj, int what, uint32_t level, size_t*
     GFX_TRY(ctx)
     if (!obj || !bytes) throw HipError("gfx_tfdm_size: null object or output");
     *bytes = tfdm_size(obj->o, what, level);
+    GFX_CATCH(ctx)
+}
+
+int gfx_tfdm_set_create(gfx_ctx* ctx, gfx_tfdm_set** out) {
+    GFX_TRY(ctx)
+    if (!out) throw HipError("gfx_tfdm_set_create: null output handle");
+    *out = new gfx_tfdm_set();
+    (*out)->s.device = ctx->c.device;
+    (*out)->ctx = ctx;
+    GFX_CATCH(ctx)
+}
+int gfx_tfdm_set_add(gfx_tfdm_set* set, gfx_tfdm* obj, const float objToWorld[12], uint32_t userId, uint32_t* index) {
+    if (!set) return 1;
+    GFX_TRY(set->ctx)
+    const uint32_t k = tfdm_set_add(set->s, obj ? &obj->o : nullptr, objToWorld, userId);
+    if (index) *index = k;
+    GFX_CATCH(set->ctx)
+}
+int gfx_tfdm_set_transform(gfx_tfdm_set* set, uint32_t index, const float objToWorld[12]) {
+    if (!set) return 1;
+    GFX_TRY(set->ctx)
+    tfdm_set_transform(set->s, index, objToWorld);
+    GFX_CATCH(set->ctx)
+}
+int gfx_tfdm_set_commit(gfx_ctx* ctx, void* stream, gfx_tfdm_set* set) {
+    GFX_TRY(ctx)
+    if (!set) throw HipError("gfx_tfdm_set_commit: null set");
+    if (set->s.device != ctx->c.device) throw HipError("gfx_tfdm_set_commit: the set belongs to another device");
+    tfdm_set_commit(set->s, static_cast<hipStream_t>(stream));
+    GFX_CATCH(ctx)
+}
+int gfx_tfdm_set_read(gfx_ctx* ctx, gfx_tfdm_set* set, void* hostOut, size_t bytes) {
+    GFX_TRY(ctx)
+    if (!set) throw HipError("gfx_tfdm_set_read: null set");
+    if (set->s.device != ctx->c.device) throw HipError("gfx_tfdm_set_read: the set belongs to another device");
+    tfdm_set_read(set->s, hostOut, bytes);
+    GFX_CATCH(ctx)
+}
+int gfx_tfdm_set_destroy(gfx_tfdm_set* set) {
+    if (!set) return 1;
+    int prev = -1;
+    const bool switched = hipGetDevice(&prev) == hipSuccess && prev != set->s.device && hipSetDevice(set->s.device) == hipSuccess;
+    (void)hipDeviceSynchronize();
+    tfdm_set_release(set->s);
+    if (switched) (void)hipSetDevice(prev);
+    delete set;
+    return 0;
+}
+int gfx_trace_scene(gfx_ctx* ctx, void* stream, uint64_t accel, gfx_tfdm_set* set, int mode, const void* dRayOrgTmin, const void* dRayDirTmax,
+                    uint32_t numRays, void* dOut, void* dCounters) {
+    GFX_TRY(ctx)
+    DevAccel dev;
+    if (accel) dev = find_accel(ctx, accel)->dev();
+    trace_scene(ctx->c, static_cast<hipStream_t>(stream), accel ? &dev : nullptr, set ? &set->s : nullptr, ctx->scenePlain, mode, dRayOrgTmin, dRayDirTmax,
+                numRays, dOut, dCounters);
     GFX_CATCH(ctx)
 }
 

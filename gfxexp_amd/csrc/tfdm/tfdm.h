@@ -14,6 +14,9 @@ struct TfdmObject {
     std::vector<float> positions, normals, texCoords;   // 9 / 9 / 6 floats per triangle, vertex order A B C
     DevBuf heights, pyramid;            // all levels behind one another (tfdm::level_offset)
     DevBuf records, aabbs, nodes;       // TriRecord[numTriangles], Box[numTriangles], Node[numNodes]
+    tfdm::Node root;                    // nodes[0] on the host: an instance's world box is made from it (tfdm_instance.hip.h)
+    uint64_t generation = 0;            // bumped whenever records / aabbs / nodes become new buffers (create, set_params): an instance
+                                        // record that holds the old pointers is stale (tfdm_set.hip)
 };
 
 void tfdm_default_params(gfx_tfdm_params* out);

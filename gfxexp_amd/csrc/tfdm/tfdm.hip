@@ -20,6 +20,7 @@
 #include <cstring>
 #include "tfdm.h"
 #include "tfdm_build.h"
+#include "tfdm_lds_stack.hip.h"
 
 namespace gfx {
 
@@ -53,18 +54,7 @@ __global__ void __launch_bounds__(64) k_tfdm_prim_aabbs(const TriRecord* __restr
     aabbs[i] = prim_aabb(records[i], pyramid, p);
 }
 
-// push() beyond kStackDepth would drop the entry; tfdm_core.hip.h asserts that the deepest tree build_tree makes fits
-struct LdsStack {
-    uint2* col; int sp;
-    __device__ __forceinline__ void push(uint32_t n, float e) { if (sp < kStackDepth) { col[sp * kTraceBlock] = make_uint2(n, f2b(e)); ++sp; } }
-    __device__ __forceinline__ void pop(uint32_t& n, float& e) { --sp; const uint2 v = col[sp * kTraceBlock]; n = v.x; e = b2f(v.y); }
-    __device__ __forceinline__ bool empty() const { return sp == 0; }
-};
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
+using LdsStack = LdsColumnStack<kTraceBlock>;      // tfdm_lds_stack.hip.h
 
 template <bool ANY_HIT>
 __global__ void __launch_bounds__(kTraceBlock) k_tfdm_trace(const Node* __restrict__ nodes, const TriRecord* __restrict__ records, const float* __restrict__ heights,
@@ -137,6 +127,8 @@ void build_geometry(TfdmObject& o, hipStream_t stream, const gfx_tfdm_params& g)
         o.records.release(); o.aabbs.release(); o.nodes.release();
         o.records = records; o.aabbs = aabbs; o.nodes = nodes;
         o.numNodes = static_cast<uint32_t>(tree.size());
+        o.root = tree[0];
+        ++o.generation;
         o.pub = g;
         o.params = p;
     }

@@ -1,0 +1,191 @@
+// tfdm_set.hip -- plain and displaced instances in one ray query (gfx_trace_scene): what one optixTrace on an instance AS of
+// triangle GASes and custom-primitive GASes does in the reference (tfdm/tfdm_main.cpp:2620-2640).  Two phases on one stream:
+//
+//   plain phase      the scene BVH8 through the persistent k_trace (trace_launch), unchanged: its refill keeps the lanes of a
+//                    wave busy, which a one-wave block beside a TFDM descent could not
+//   instance phase   k_scene_instances<ANY_HIT>: one ray per lane, one wave per block (the launch shape of k_tfdm_trace and for
+//                    its reason, tfdm.hip).  A lane starts from the plain result and walks the instance table in index order; the
+//                    record is read through the wave-uniform loop index, so the matrices, Params and pointers live in scalar
+//                    registers.  A lane whose ray passes the instance's padded world box takes the ray to object space and runs
+//                    tfdm::trace_ray with tmax = its best distance so far (tfdm_instance.hip.h: that is the merge rule); an
+//                    instance no lane of the wave enters is skipped by ballot.
+//
+// Register count, scratch and occupancy: DESIGN.md section 15.
+#include <cstring>
+#include "tfdm_set.h"
+#include "tfdm_lds_stack.hip.h"
+
+namespace gfx {
+
+using namespace tfdm;
+
+namespace {
+
+constexpr int kSceneBlock = 64;
+using SceneStack = LdsColumnStack<kSceneBlock>;
+
+template <bool ANY_HIT>
+__global__ void __launch_bounds__(kSceneBlock) k_scene_instances(const InstanceRecord* __restrict__ table, uint32_t numInstances, const float4* __restrict__ rayOrgTmin,
+                                                                 const float4* __restrict__ rayDirTmax, uint32_t numRays, const void* plain, void* out,
+                                                                 unsigned long long* __restrict__ counters) {
+    __shared__ uint2 s_stack[kStackDepth * kSceneBlock];
+    const uint32_t i = blockIdx.x * kSceneBlock + threadIdx.x;
+    const bool live = i < numRays;
+    TraceStats ts;
+    ts.aabbTests = 0u; ts.leafTests = 0u; ts.primTests = 0u;
+    uint32_t boxTests = 0u, traversals = 0u;
+    V3 org = v3(0.0f, 0.0f, 0.0f), dir = v3(0.0f, 0.0f, 1.0f);
+    float tmin = 0.0f;
+    SceneHit best = scene_miss(0.0f);
+    bool occluded = false;
+    if (live) {
+        const float4 o = rayOrgTmin[i], d = rayDirTmax[i];
+        org = v3(o.x, o.y, o.z); dir = v3(d.x, d.y, d.z); tmin = o.w;
+        best = scene_miss(d.w);
+        if (plain) {
+            if (ANY_HIT) occluded = static_cast<const uint32_t*>(plain)[i] != 0u;
+            else {
+                const float4 h = static_cast<const float4*>(plain)[i];          // a gfx_hit
+                best = scene_start(d.w, h.x, h.y, h.z, f2b(h.w));
+            }
+        }
+    }
+    const V3 inv = v3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
+    SceneStack stack;
+    stack.col = s_stack + threadIdx.x;
+    stack.sp = 0;
+    bool open = live && !occluded;               // the lane still looks for a hit
+    for (uint32_t k = 0; k < numInstances; ++k) {
+        const InstanceRecord& r = table[k];
+        bool enter = false;
+        if (open) { ++boxTests; enter = world_box_hit(r, org, inv, tmin, best.dist); }
+        if (__ballot(enter) == 0ull) continue;
+        if (enter) {
+            ++traversals;
+            if (scene_instance<ANY_HIT>(r, k, org, dir, tmin, stack, best, ts) && ANY_HIT) { occluded = true; open = false; }
+        }
+    }
+    if (live) {
+        if (ANY_HIT) static_cast<uint32_t*>(out)[i] = occluded ? 1u : 0u;
+        else {
+            float4* h = static_cast<float4*>(out) + 2u * i;
+            h[0] = make_float4(best.dist, best.bcB, best.bcC, b2f(best.index));
+            h[1] = make_float4(best.normal.x, best.normal.y, best.normal.z, b2f(best.where));
+        }
+    }
+    if (counters) {                      // per wave, one atomic each
+        const uint32_t a = wave_sum(ts.aabbTests), l = wave_sum(ts.leafTests), n = wave_sum(live ? 1u : 0u), t = wave_sum(ts.primTests);
+        const uint32_t b = wave_sum(boxTests), v = wave_sum(traversals);
+        if ((threadIdx.x & 63u) == 0) {
+            atomicAdd(counters + 0, a); atomicAdd(counters + 1, l); atomicAdd(counters + 2, n); atomicAdd(counters + 3, t);
+            atomicAdd(counters + 4, b); atomicAdd(counters + 5, v);
+        }
+    }
+}
+
+void check_member(const TfdmSet& s, const TfdmObject* obj) {
+    if (!obj) throw HipError("gfx_tfdm_set: null object");
+    if (obj->device != s.device) throw HipError("gfx_tfdm_set: the object belongs to another device");
+}
+
+} // namespace
+
+uint32_t tfdm_set_add(TfdmSet& s, TfdmObject* obj, const float objToWorld[12], uint32_t userId) {
+    check_member(s, obj);
+    if (!objToWorld) throw HipError("gfx_tfdm_set_add: null transform");
+    if (s.members.size() >= kMaxInstances) throw HipError("gfx_tfdm_set_add: a set holds at most 1024 instances");
+    TfdmSet::Member m;
+    m.obj = obj; m.userId = userId; m.generation = 0;
+    std::memcpy(m.objToWorld, objToWorld, sizeof(m.objToWorld));
+    s.members.push_back(m);
+    s.dirty = true;
+    return static_cast<uint32_t>(s.members.size() - 1);
+}
+
+void tfdm_set_transform(TfdmSet& s, uint32_t index, const float objToWorld[12]) {
+    if (index >= s.members.size()) throw HipError("gfx_tfdm_set_transform: no such instance");
+    if (!objToWorld) throw HipError("gfx_tfdm_set_transform: null transform");
+    std::memcpy(s.members[index].objToWorld, objToWorld, sizeof(s.members[index].objToWorld));
+    s.dirty = true;
+}
+
+// The records are derived into a fresh table and swapped in only when every one of them worked.
+void tfdm_set_commit(TfdmSet& s, hipStream_t stream) {
+    std::vector<InstanceRecord> recs(s.members.size());
+    for (size_t k = 0; k < s.members.size(); ++k) {
+        const TfdmSet::Member& m = s.members[k];
+        const TfdmObject& o = *m.obj;
+        const char* err = make_instance(m.objToWorld, o.root, o.nodes.as<Node>(), o.records.as<TriRecord>(), o.heights.as<float>(), o.pyramid.as<F2>(), o.params,
+                                        m.userId, recs[k]);
+        if (err) throw HipError("gfx_tfdm_set_commit: instance " + std::to_string(k) + ": " + err);
+    }
+    if (!recs.empty()) {
+        s.table.reserve(sizeof(InstanceRecord) * recs.size());
+        GFX_HIP(hipMemcpyAsync(s.table.p, recs.data(), sizeof(InstanceRecord) * recs.size(), hipMemcpyHostToDevice, stream));
+        GFX_HIP(hipStreamSynchronize(stream));       // `recs` is pageable memory
+    }
+    s.host.swap(recs);
+    for (TfdmSet::Member& m : s.members) m.generation = m.obj->generation;
+    s.dirty = false;
+}
+
+void tfdm_set_read(TfdmSet& s, void* hostOut, size_t bytes) {
+    if (s.dirty) throw HipError("gfx_tfdm_set_read: the set has an add or a transform that is not committed");
+    const size_t need = sizeof(InstanceRecord) * s.host.size();
+    if (bytes != need || (need && !hostOut)) throw HipError("gfx_tfdm_set_read: the buffer must hold exactly 192 bytes per instance");
+    if (!need) return;
+    GFX_HIP(hipDeviceSynchronize());
+    GFX_HIP(hipMemcpy(hostOut, s.table.p, need, hipMemcpyDeviceToHost));
+}
+
+void tfdm_set_release(TfdmSet& s) { s.table.release(); s.plain.release(); }
+
+void trace_scene(Context& ctx, hipStream_t stream, const DevAccel* accel, TfdmSet* set, DevBuf& fallbackPlain, int mode, const void* dRayOrgTmin,
+                 const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters) {
+    if (mode != GFX_TRACE_CLOSEST && mode != GFX_TRACE_ANY) throw HipError("gfx_trace_scene: unknown mode");
+    if (set) {
+        if (set->device != ctx.device) throw HipError("gfx_trace_scene: the instance set belongs to another device");
+        if (set->dirty) throw HipError("gfx_trace_scene: the instance set has an add or a transform that is not committed (gfx_tfdm_set_commit)");
+        for (size_t k = 0; k < set->members.size(); ++k)
+            if (set->members[k].generation != set->members[k].obj->generation)
+                throw HipError("gfx_trace_scene: instance " + std::to_string(k) + "'s object had gfx_tfdm_set_params after the set was committed; commit the set again");
+    }
+    if (numRays == 0) return;
+    if (!dRayOrgTmin || !dRayDirTmax || !dOut) throw HipError("gfx_trace_scene: null ray or output buffer");
+    // rays are read as float4 and a closest hit is written as two float4; an any-hit answer is one uint32
+    const bool any = mode == GFX_TRACE_ANY;
+    const uintptr_t outMask = any ? 3u : 15u;
+    if ((reinterpret_cast<uintptr_t>(dRayOrgTmin) & 15u) || (reinterpret_cast<uintptr_t>(dRayDirTmax) & 15u) || (reinterpret_cast<uintptr_t>(dOut) & outMask))
+        throw HipError("gfx_trace_scene: the ray buffers and a closest-hit output must be 16-byte aligned (an any-hit output 4-byte)");
+    if (reinterpret_cast<uintptr_t>(dCounters) & 7u) throw HipError("gfx_trace_scene: the counters must be 8-byte aligned");
+    const uint32_t numInstances = set ? static_cast<uint32_t>(set->host.size()) : 0u;
+    const float4* org = static_cast<const float4*>(dRayOrgTmin);
+    const float4* dir = static_cast<const float4*>(dRayDirTmax);
+    // Plain phase.  An any-hit answer has the output's own format: k_trace writes it in place and the instance phase goes over
+    // it.  A closest hit is a 16-byte gfx_hit that the instance phase widens, so it goes through a buffer.
+    const void* plain = nullptr;
+    if (accel) {
+        void* dst = dOut;
+        if (!any) {
+            DevBuf& buf = set ? set->plain : fallbackPlain;
+            buf.reserve(sizeof(gfx_hit) * static_cast<size_t>(numRays));
+            dst = buf.p;
+        }
+        TraceLaunch t;
+        t.accel = *accel;
+        t.rayOrgTmin = org; t.rayDirTmax = dir;
+        t.numRays = numRays; t.numRaysPtr = nullptr; t.out = dst; t.mode = mode;
+        trace_launch(ctx, stream, t);
+        plain = dst;
+        if (any && numInstances == 0 && !dCounters) return;
+    }
+    const uint32_t blocks = (numRays + kSceneBlock - 1u) / kSceneBlock;
+    const InstanceRecord* table = numInstances ? set->table.as<InstanceRecord>() : nullptr;
+    unsigned long long* cnt = static_cast<unsigned long long*>(dCounters);
+    ScopedKernelTimer timer(ctx, stream, "k_scene_instances");
+    if (any) k_scene_instances<true><<<blocks, kSceneBlock, 0, stream>>>(table, numInstances, org, dir, numRays, plain, dOut, cnt);
+    else k_scene_instances<false><<<blocks, kSceneBlock, 0, stream>>>(table, numInstances, org, dir, numRays, plain, dOut, cnt);
+    GFX_HIP(hipGetLastError());
+}
+
+} // namespace gfx

@@ -724,8 +724,9 @@ int gfx_bc_expand(gfx_ctx* ctx, void* stream, uint32_t bcFormat, const void* dBl
  * (the reference's tfdm/ program).  The query stands next to gfx_trace: rays are given in the object
  * space of the base mesh, in gfx_trace's layout (origin | tmin, direction | tmax), and a ray's tmax lets the caller chain
  * the query behind gfx_trace for a scene that mixes plain and displaced geometry: trace the plain geometry first, hand its
- * hit distance in as tmax, and a displaced hit that comes back is the closer one.  Displaced primitives inside the scene
- * BVH8 and the renderers are not part of this interface. */
+ * hit distance in as tmax, and a displaced hit that comes back is the closer one.  gfx_trace_scene below does that chain in
+ * one call, for any number of displaced instances under their own transforms; the G-buffer pass and the renderers do not
+ * see displaced geometry. */
 typedef struct gfx_tfdm gfx_tfdm;                       /* opaque; owns heights, pyramid, records, AABBs, tree */
 enum gfx_tfdm_local { GFX_TFDM_BOX = 0, GFX_TFDM_TWO_TRIANGLE = 1 };   /* LocalIntersectionType, tfdm/tfdm_shared.h; Bilinear and BSpline are not built */
 /* DisplacementParameters, tfdm/tfdm_shared.h, with the texture transform as the scale / rotation (degrees) / offset it is made
@@ -771,6 +772,40 @@ enum gfx_tfdm_read_what { GFX_TFDM_READ_PYRAMID = 0, GFX_TFDM_READ_AABBS = 1, GF
 int gfx_tfdm_read(gfx_ctx* ctx, gfx_tfdm* obj, int what, uint32_t level, void* hostOut, size_t bytes);
 /* Size in bytes of what gfx_tfdm_read(what, level) returns; with what = -1 the device bytes the object owns in all. */
 int gfx_tfdm_size(gfx_ctx* ctx, gfx_tfdm* obj, int what, uint32_t level, size_t* bytes);
+
+/* ---------------------------------------------------------------- plain and displaced instances in one query -------------
+ * A set of displaced instances: gfx_tfdm objects under object-to-world transforms (row-major 3 x 4, as
+ * gfx_instance_set_transform takes them), at most 1024.  One object may be added many times; objects and the context must
+ * outlive the set.  gfx_tfdm_set_commit derives one 192-byte record per instance (csrc/tfdm/tfdm_instance.hip.h
+ * InstanceRecord: both matrices, the padded world box, the object's device pointers and parameters, userId) and uploads the
+ * table; a transform that is not finite or is singular is refused there and the committed table stays.  gfx_tfdm_set_params
+ * on a member gives the object new device buffers, so the set must be committed again before the next query.  Errors of the
+ * functions without a context argument are reported through the context the set was created on (gfx_last_error). */
+typedef struct gfx_tfdm_set gfx_tfdm_set;
+int gfx_tfdm_set_create(gfx_ctx* ctx, gfx_tfdm_set** out);
+int gfx_tfdm_set_add(gfx_tfdm_set* set, gfx_tfdm* obj, const float objToWorld[12], uint32_t userId, uint32_t* index);
+int gfx_tfdm_set_transform(gfx_tfdm_set* set, uint32_t index, const float objToWorld[12]);
+int gfx_tfdm_set_commit(gfx_ctx* ctx, void* stream, gfx_tfdm_set* set);
+/* The committed InstanceRecord table, 192 bytes per instance (`bytes` must be exactly that), for tests. */
+int gfx_tfdm_set_read(gfx_ctx* ctx, gfx_tfdm_set* set, void* hostOut, size_t bytes);
+int gfx_tfdm_set_destroy(gfx_tfdm_set* set);
+
+/* closest-hit record of gfx_trace_scene, 32 B (what a renderer needs from a displaced hit: tfdm/tfdm_shared.h:570-577).
+ *   miss                       dist = the ray's tmax, where = index = GFX_INVALID_SLOT, the rest zero
+ *   plain hit                  where = GFX_SCENE_PLAIN, dist / bcB / bcC / index as gfx_hit (index = triIndex), normal zero
+ *   displaced hit, instance k  where = k << 1 | frontFace, index = the base primIndex, bcB / bcC on the base triangle, normal =
+ *                              the unit WORLD-space normal (the object-space normal through the instance's normal matrix) */
+typedef struct gfx_scene_hit { float dist, bcB, bcC; uint32_t index; float normal[3]; uint32_t where; } gfx_scene_hit;
+#define GFX_SCENE_PLAIN 0x80000000u
+/* One optixTrace on an instance AS that mixes triangle GASes and custom-primitive GASes (tfdm/tfdm_main.cpp:2620-2640): world
+ * rays in gfx_trace's layout against the BVH8 `accel` (0: none) and the displaced instances of `set` (NULL: none).  The closest
+ * hit wins; on equal distance a plain hit beats a displaced one and a lower instance index a higher one.  mode
+ * GFX_TRACE_CLOSEST: dOut = gfx_scene_hit[numRays]; GFX_TRACE_ANY: dOut = uint32_t[numRays] (1 = occluded).  Distances are the
+ * world ray's parameter (object-space directions are not renormalised).  dCounters (optional, device u64[8], added to): [0..3]
+ * as gfx_tfdm_trace, [4] world-box tests, [5] object-space traversals started.  Alignment as gfx_tfdm_trace.  A set with an
+ * uncommitted add or transform, or with a member whose gfx_tfdm_set_params ran after the commit, is refused with a message. */
+int gfx_trace_scene(gfx_ctx* ctx, void* stream, uint64_t accel, gfx_tfdm_set* set, int mode, const void* dRayOrgTmin, const void* dRayDirTmax,
+                    uint32_t numRays, void* dOut, void* dCounters);
 
 #ifdef __cplusplus
 }

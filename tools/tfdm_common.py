@@ -86,3 +86,36 @@ def tessellated_quad(heights, h_scale):
     tr, bl, br = tl + 1, tl + n + 1, tl + n + 2
     t = np.concatenate([np.stack([tl, tr, br], 1), np.stack([tl, br, bl], 1)]).astype(np.uint32)
     return v, t
+
+
+def affine(linear, translation):
+    """Row-major 3 x 4 float32 from a 3 x 3 linear part and a translation."""
+    m = np.zeros((3, 4), np.float64)
+    m[:, :3], m[:, 3] = linear, translation
+    return m.astype(np.float32)
+
+
+def rotation_x(degrees):
+    c, s = np.cos(np.radians(degrees)), np.sin(np.radians(degrees))
+    return np.array([[1, 0, 0], [0, c, -s], [0, s, c]], np.float64)
+
+
+def mixed_scene(map_size):
+    """The scene of tools/tfdm_view.py --scene and tools/bench_scene_trace.py, z up: a plain teapot (15 704 triangles in the BVH8)
+    standing on a displaced 4 x 4 ground quad, and a second displaced quad as a tilted wall behind it; both quads share one
+    height map of map_size x map_size.  Returns (HostScene of the plain part, (vertices, triangles, heights, params) of the
+    displaced object, [(objToWorld, userId)] of its instances, camera position, look-at point)."""
+    s = api.HostScene()
+    g = s.load_obj(os.path.join(ASSETS, "teapot.obj"))
+    tv, _ = obj_mesh("teapot.obj")
+    lo, hi = tv["position"].min(0).astype(np.float64), tv["position"].max(0).astype(np.float64)
+    k = 1.6 / float((hi - lo).max())
+    up = rotation_x(90.0)                                   # the teapot's y axis becomes z
+    centre = 0.5 * (lo + hi)
+    # its footprint centred on the ground quad, its lowest point just above the crests of the ground (0.08)
+    s.add_instance(g, affine(k * up, (-k * centre[0], k * centre[2], 0.08 - k * lo[1])))
+    v, t = quad_mesh()
+    gp = api.tfdm_params(h_scale=0.02, tex_scale=(1.0, 1.0))            # in object space: 0.08 under the ground's scale of 4
+    ground = affine(np.diag([4.0, 4.0, 4.0]), (-2.0, -2.0, 0.0))
+    wall = affine(rotation_x(70.0) @ np.diag([4.0, 2.5, 4.0]), (-2.0, 2.0, 0.0))
+    return s, (v, t, procedural_map(map_size), gp), [(ground, 1), (wall, 2)], (0.6, -4.2, 2.2), (0.0, 0.3, 0.6)

@@ -5,7 +5,13 @@
 
 --height: a .png / .jpg / .tga / .dds height map (gfxh_tfdm_load_height); without it a procedural map of --size.  --scale is
 relative to the mesh's extent.  Writes <out>_normal.png (n * 0.5 + 0.5 in object space) and <out>_depth.png (near = bright), and
-prints the hit share and the traversal counters per ray."""
+prints the hit share and the traversal counters per ray.
+
+    python tools/tfdm_view.py --scene [--size 256] [--width 960] [--height-px 540] [--out tfdm_view]
+
+--scene: a plain teapot on a displaced ground quad with a second displaced quad as a tilted wall (tfdm_common.mixed_scene), through
+ONE gfx_trace_scene call.  Writes <out>_normal.png (world-space normals of the displaced hits; plain hits grey), <out>_depth.png
+and <out>_instance.png (plain geometry grey, every displaced instance a colour of its own, misses black)."""
 import argparse
 import json
 import os
@@ -18,6 +24,61 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gfxexp_amd import api  # noqa: E402
 import tfdm_common as K  # noqa: E402
+
+
+def _depth_image(dist, hit, n):
+    depth = np.zeros((n, 4), np.float32)
+    depth[:, 3] = 1
+    if hit.any():
+        d = dist[hit]
+        depth[hit, :3] = (1.0 - 0.9 * (d - d.min()) / max(float(d.max() - d.min()), 1e-30))[:, None]
+    return depth
+
+
+def scene_view(a):
+    plain, (v, t, heights, gp), instances, pos, target = K.mixed_scene(a.size)
+    ctx = api.Context(0)
+    plain.upload(ctx)
+    accel = ctx.accel_build()
+    tf = api.Tfdm(ctx, v, t, heights, gp)
+    tset = api.TfdmSet(ctx)
+    for m, uid in instances:
+        tset.add(tf, m, uid)
+    tset.commit()
+    w, h = a.width, a.height_px
+    n = w * h
+    org, dirs = api.camera_rays(K.look_at_camera(w, h, pos, target), w, h)
+    d_org, d_dir = torch.from_numpy(org).cuda(), torch.from_numpy(dirs).cuda()
+    d_out = torch.zeros(n * 8, dtype=torch.int32, device="cuda")
+    d_cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
+    api.trace_scene(ctx, accel, tset, api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), d_cnt.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    hits = d_out.cpu().numpy().view(api.SCENE_HIT_DTYPE)
+    cnt = d_cnt.cpu().numpy()
+    where = hits["where"]
+    miss, is_plain = where == api.GFX_INVALID_SLOT, where == api.SCENE_PLAIN
+    disp = ~miss & ~is_plain
+    sdr = api.sdr_config(brightness=1.0, tone_map=False, gamma=False)
+    img = np.zeros((n, 4), np.float32)
+    img[:, 3] = 1
+    img[is_plain, :3] = 0.5
+    img[disp, :3] = hits["normal"][disp] * 0.5 + 0.5
+    api.save_image_sdr(a.out + "_normal.png", img, w, h, sdr)
+    api.save_image_sdr(a.out + "_depth.png", _depth_image(hits["dist"], ~miss, n), w, h, sdr)
+    palette = np.array([(0.9, 0.3, 0.2), (0.2, 0.6, 0.9), (0.3, 0.8, 0.3), (0.9, 0.8, 0.2), (0.7, 0.3, 0.8), (0.2, 0.8, 0.8)], np.float32)
+    ids = np.zeros((n, 4), np.float32)
+    ids[:, 3] = 1
+    ids[is_plain, :3] = 0.5
+    ids[disp, :3] = palette[(where[disp] >> 1) % len(palette)]
+    api.save_image_sdr(a.out + "_instance.png", ids, w, h, sdr)
+    print(json.dumps({"scene": "teapot on displaced ground, displaced wall", "size": int(heights.shape[0]), "instances": len(tset), "rays": n,
+                      "plain_share": round(float(is_plain.mean()), 4),
+                      "instance_shares": [round(float((disp & (where >> 1 == k)).mean()), 4) for k in range(len(tset))],
+                      "miss_share": round(float(miss.mean()), 4), "aabb_tests_per_ray": round(float(cnt[0]) / n, 2),
+                      "leaf_tests_per_ray": round(float(cnt[1]) / n, 2), "world_box_tests_per_ray": round(float(cnt[4]) / n, 2),
+                      "traversals_per_ray": round(float(cnt[5]) / n, 2),
+                      "images": [a.out + "_normal.png", a.out + "_depth.png", a.out + "_instance.png"]}))
+    return 0
 
 
 def main():
@@ -33,7 +94,10 @@ def main():
     ap.add_argument("--width", type=int, default=960)
     ap.add_argument("--height-px", type=int, default=540)
     ap.add_argument("--out", default="tfdm_view")
+    ap.add_argument("--scene", action="store_true")
     a = ap.parse_args()
+    if a.scene:
+        return scene_view(a)
     heights = api.tfdm_load_height(a.height) if a.height else K.procedural_map(a.size)
     v, t, pos, target, up = K.base_mesh(a.mesh)
     gp = api.tfdm_params(h_scale=a.scale * K.extent(v), tex_scale=(a.tex_scale, a.tex_scale), tex_rotation=a.rotation, target_mip_level=a.level,
