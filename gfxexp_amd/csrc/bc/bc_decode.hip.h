@@ -18,6 +18,7 @@
 #include <cstdint>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>          // the function attributes below; a host compiler needs no HIP header
 #define GFX_BC_FN __host__ __device__ __forceinline__
 #else
 #define GFX_BC_FN inline

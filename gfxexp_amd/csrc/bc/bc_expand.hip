@@ -69,8 +69,6 @@ __global__ __launch_bounds__(256) void k_bc_expand(const uint8_t* __restrict__ b
     }
 }
 
-uint32_t bc_block_bytes(uint32_t bcFormat) { return bc::block_bytes(bcFormat); }
-
 template <uint32_t BC>
 static void launch_format(hipStream_t stream, const void* dBlocks, uint32_t width, uint32_t height, uint32_t format, void* dTexels) {
     const uint32_t perRow = (width + 3u) / 4u, n = perRow * ((height + 3u) / 4u);   // <= 4096 * 4096

@@ -13,8 +13,6 @@ namespace gfx {
 
 struct Context;
 
-// bytes per block of an enum gfx_bc_format value, 0 for an unknown one
-uint32_t bc_block_bytes(uint32_t bcFormat);
 // Copies the blocks of slot `texSlot` to the device (synchronous, set-up time) and remembers them; replaces earlier blocks of the slot.
 // Throws and leaves the table as it was when the allocation or the copy fails.
 void bc_texture_store(Context& ctx, uint32_t texSlot, uint32_t bcFormat, const void* blocks, size_t bytes);

@@ -8,7 +8,9 @@
 #include "internal.h"
 #include "denoise/denoise.h"
 #include "denoise/taa.h"
+#include "bc/bc_decode.hip.h"
 #include "bc/bc_textures.h"
+#include "host/tex_format.h"
 #include "tfdm/tfdm.h"
 #include "tfdm/tfdm_set.h"
 
@@ -116,14 +118,8 @@ int gfx_texture_set(gfx_ctx* ctx, uint32_t texSlot, uint32_t width, uint32_t hei
     GFX_TRY(ctx)
     if (texSlot == 0 || texSlot > (1u << 20)) throw HipError("gfx_texture_set: texture slots are 1-based");
     if (width == 0 || height == 0 || width > 16384 || height > 16384) throw HipError("gfx_texture_set: bad size");   // TexDimInfo: 14 bits
-    size_t bpp = 0;
-    switch (format) {
-    case GFX_TEX_RGBA8_SRGB: case GFX_TEX_RGBA8_UNORM: bpp = 4; break;
-    case GFX_TEX_R8_UNORM: bpp = 1; break;
-    case GFX_TEX_RG8_UNORM: bpp = 2; break;
-    case GFX_TEX_RGBA32F: bpp = 16; break;
-    default: throw HipError("gfx_texture_set: unknown format");
-    }
+    const size_t bpp = tex_bytes_per_texel(format);
+    if (!bpp) throw HipError("gfx_texture_set: unknown format");
     if (!texels) throw HipError("gfx_texture_set: null texels");
     if (ctx->c.textures.size() <= texSlot) ctx->c.textures.resize(texSlot + 1);
     HostTexture& t = ctx->c.textures[texSlot];
@@ -134,15 +130,11 @@ int gfx_texture_set(gfx_ctx* ctx, uint32_t texSlot, uint32_t width, uint32_t hei
     GFX_CATCH(ctx)
 }
 
-static size_t texel_bytes(uint32_t format) {
-    return format == GFX_TEX_RGBA32F ? 16 : (format == GFX_TEX_RG8_UNORM ? 2 : (format == GFX_TEX_R8_UNORM ? 1 : 4));
-}
-
 int gfx_texture_set_bc(gfx_ctx* ctx, uint32_t texSlot, uint32_t width, uint32_t height, uint32_t bcFormat, const void* blocks, uint32_t format) {
     GFX_TRY(ctx)
     if (texSlot == 0 || texSlot > (1u << 20)) throw HipError("gfx_texture_set_bc: texture slots are 1-based");
     if (width == 0 || height == 0 || width > 16384 || height > 16384) throw HipError("gfx_texture_set_bc: bad size");
-    const uint32_t blockBytes = bc_block_bytes(bcFormat);
+    const uint32_t blockBytes = bc::block_bytes(bcFormat);
     if (blockBytes == 0) throw HipError("gfx_texture_set_bc: unknown block-compressed format");
     if (format == GFX_TEX_RGBA32F) throw HipError("gfx_texture_set_bc: blocks expand into an 8-bit format, not GFX_TEX_RGBA32F");
     if (format != GFX_TEX_RGBA8_SRGB && format != GFX_TEX_RGBA8_UNORM && format != GFX_TEX_R8_UNORM && format != GFX_TEX_RG8_UNORM)
@@ -163,7 +155,7 @@ int gfx_texture_read(gfx_ctx* ctx, void* stream, uint32_t texSlot, void* hostOut
     Context& c = ctx->c;
     if (texSlot == 0 || texSlot >= c.textures.size() || c.textures[texSlot].width == 0) throw HipError("gfx_texture_read: texture slot was never set");
     const HostTexture& t = c.textures[texSlot];
-    if (!hostOut || bytes != texel_bytes(t.format) * t.width * t.height) throw HipError("gfx_texture_read: the buffer must hold the slot's texels exactly");
+    if (!hostOut || bytes != tex_bytes_per_texel(t.format) * t.width * t.height) throw HipError("gfx_texture_read: the buffer must hold the slot's texels exactly");
     hipStream_t s = static_cast<hipStream_t>(stream);
     scene_upload(c, s);
     DevTexture d;

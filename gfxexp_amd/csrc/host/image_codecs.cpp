@@ -12,7 +12,7 @@
 
 namespace gfx_img {
 
-// ---- inflate (RFC 1950 / 1951): shared by the PNG reader and the ZIP / ZIPS chunks of the OpenEXR reader in scene_builder.cpp ----
+// ---- inflate (RFC 1950 / 1951): shared by the PNG reader and the ZIP / ZIPS chunks of the OpenEXR reader in image_formats.cpp ----
 namespace {
 struct BitReader {
     const uint8_t* p; size_t n, at = 0; uint32_t acc = 0; int have = 0; bool bad = false;

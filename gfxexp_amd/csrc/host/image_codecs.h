@@ -1,5 +1,5 @@
 // image_codecs.h -- PNG and JPEG readers and a PNG writer of the host layer (plain C++17: no HIP header, no global state, so the
-// translation unit also builds alone for the sanitizer driver in tests/native/image_fuzz.cpp).
+// translation unit also builds alone for the sanitizer driver in tests/native/image_fuzz.cpp; image_formats.h holds the other readers).
 //
 // Output contract of both readers: exactly the bytes stbi_load(file, &w, &h, &n, 4) of the reference's ext/stb_image.h (v2.25)
 // returns -- 8-bit RGBA, row 0 first -- plus n, the channel count of the file.  DESIGN.md section 13 lists what that pins.
@@ -11,7 +11,7 @@
 
 namespace gfx_img {
 
-constexpr uint32_t kMaxDim = 16384;      // = kMaxTextureDim of scene_builder.cpp: a dimension above it is refused before any arithmetic
+constexpr uint32_t kMaxDim = 16384;      // TexDimInfo packs 14 bits per dimension: every reader and the scene container refuse a larger one before any arithmetic
 
 enum Kind : uint32_t { kKindNone = 0, kKindPng = 1, kKindJpeg = 2 };
 

@@ -31,7 +31,7 @@
 //   and, headless: -max-path-length n (5; 0 = unlimited, :1860-1861)   -no-train   -log10-radiance-scale s (0, :2240)
 //   -nee lights|regir|restir (lights): next-event estimation from the emitter distributions (the reference), from the ReGIR grid, or --
 //        at the first path vertex -- from the pixel's ReSTIR DI reservoir (the two halves of README.md:80-81)
-// Textures are read by the host decoders of scene_builder.cpp and image_codecs.cpp (PNG and JPEG as the reference's stb_image decodes them,
+// Textures are read by the host decoders of image_formats.cpp and image_codecs.cpp (PNG and JPEG as the reference's stb_image decodes them,
 // .dds with BC1-BC5 / BC7 blocks, PPM / PGM / PFM / BMP / TGA, OpenEXR): an asset tree is used as it is.  -env-texture wants a float image.
 #include <cmath>
 #include <cstdio>

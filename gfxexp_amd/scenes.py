@@ -1,6 +1,7 @@
 """Procedural scenes of the benchmarks (no dependency on tests/ or oracle/).
 
-street scenes come from the host builder `gfxh_scene_make_street` (gfxexp_amd/csrc/host/scene_builder.cpp):
+street scenes come from the host builder `gfxh_scene_make_street` (gfxexp_amd/csrc/host/street_scene.cpp;
+tests/golden/street_digest.json pins the scenes of small_street and bench_street byte for byte):
 instanced facades, props, lamps (pole + emissive box head) and emissive signs."""
 import os
 

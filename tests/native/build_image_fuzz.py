@@ -1,4 +1,4 @@
-"""Builds tests/native/image_fuzz: image_fuzz.cpp + gfxexp_amd/csrc/host/image_codecs.cpp alone, with g++ -fsanitize=address,undefined,
+"""Builds tests/native/image_fuzz: image_fuzz.cpp + gfxexp_amd/csrc/host/image_codecs.cpp and image_formats.cpp alone, with g++ -fsanitize=address,undefined,
 as an executable (a sanitized executable brings its own runtime; nothing is preloaded and nothing of it goes near the GPU library).
 build() returns the path, or raises Unavailable with the reason when there is no g++ or no sanitizer runtime to link against."""
 import os
@@ -8,8 +8,10 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 EXE = os.path.join(HERE, "image_fuzz")
-SOURCES = [os.path.join(HERE, "image_fuzz.cpp"), os.path.join(ROOT, "gfxexp_amd", "csrc", "host", "image_codecs.cpp")]
-HEADERS = [os.path.join(ROOT, "gfxexp_amd", "csrc", "host", "image_codecs.h")]
+HOST = os.path.join(ROOT, "gfxexp_amd", "csrc", "host")
+SOURCES = [os.path.join(HERE, "image_fuzz.cpp"), os.path.join(HOST, "image_codecs.cpp"), os.path.join(HOST, "image_formats.cpp")]
+HEADERS = [os.path.join(HOST, "image_codecs.h"), os.path.join(HOST, "image_formats.h"), os.path.join(HOST, "..", "bc", "bc_decode.hip.h"),
+           os.path.join(ROOT, "include", "gfxexp_host.h"), os.path.join(ROOT, "include", "gfxexp.h")]
 
 
 class Unavailable(RuntimeError):

@@ -1,4 +1,4 @@
-"""CPU: the host loader's OpenEXR reader (gfxexp_amd/csrc/host/scene_builder.cpp decode_exr) -- the format the reference reads its
+"""CPU: the host loader's OpenEXR reader (gfxexp_amd/csrc/host/image_formats.cpp decode_exr) -- the format the reference reads its
 environment texture from (loadEnvTexture -> tinyexr LoadEXR, common/common_host.cpp:2674).
 
 The files are written here, byte by byte from the OpenEXR file-layout document, with Python's zlib as the compressor -- an encoder that

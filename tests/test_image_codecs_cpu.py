@@ -5,7 +5,8 @@ stbi_load(file, &w, &h, &n, 4) returned (make_image_golden.py compiled it at dev
 condition is byte for byte on EVERY valid fixture -- no tolerance and no fixture left out -- through gfxh_image_decode_rgba8 and
 through gfxh_scene_load_texture.  The refusal group must be refused (the two 20000-wide files, which the reference decodes, by the
 library's own 16384 limit).  Truncated and mutated files need only be safe: refused, or decoded to an image within the limit; the
-same schedule runs under AddressSanitizer + UBSan in test_the_readers_under_sanitizers."""
+same schedule runs under AddressSanitizer + UBSan in test_the_readers_under_sanitizers, and test_every_reader_under_sanitizers does
+the same for the readers of host/image_formats.cpp (EXR / PFM / PNM / BMP / TGA, the DDS header)."""
 import os
 import subprocess
 
@@ -170,6 +171,62 @@ def test_the_readers_under_sanitizers(built_lib, tmp_path):
         words = lines[index].split()
         assert words[0] == name and words[1] == "prefixes" and words[4] == "mutations"
         assert (int(words[2]), int(words[3]), int(words[5]), int(words[6])) == _fuzz_counts(index, name), name
+
+
+def _load_counts_and_crc(directory, index, name, data):
+    """the library's side of the schedule: gfxh_scene_load_texture on a fresh scene per input (the texture cache is keyed by path), the
+    input stored under the seed's extension; and the CRC-32 of what the whole file became"""
+    import zlib
+    path = os.path.join(str(directory), "in_" + name)
+
+    def loads(d):
+        with open(path, "wb") as f:
+            f.write(d)
+        s = api.HostScene()
+        try:
+            ok = s.load_texture(path) != 0
+        except api.GfxError:
+            ok = False
+        s.close()
+        return int(ok)
+    prefixes = [loads(data[:n]) for n in range(len(data))]
+    mutated = [loads(m) for m in F.mutations(data, index, F.READER_MUTATIONS)]
+    with open(path, "wb") as f:
+        f.write(data)
+    s = api.HostScene()
+    s.load_texture(path)
+    (t,) = s.textures()
+    crc = zlib.crc32((t[6] if t[4] is None else t[4]).tobytes()) & 0xFFFFFFFF
+    return (sum(prefixes), len(prefixes) - sum(prefixes), sum(mutated), len(mutated) - sum(mutated)), crc
+
+
+def test_every_reader_under_sanitizers(built_lib, tmp_path):
+    """EXR / PFM / PNM / BMP / TGA and the DDS header parser (host/image_formats.cpp), built alone with -fsanitize=address,undefined
+    next to image_codecs.cpp: every prefix and READER_MUTATIONS single-byte mutations of every seed of image_fixtures.reader_seeds()
+    through the dispatch the library uses.  The driver checks each result (1 <= w, h <= 16384; one buffer of 4 w h elements; a DDS
+    level 0 inside the file); its decoded / refused counts equal the library's through gfxh_scene_load_texture, and what it decodes
+    each whole seed to has the checksum of the texture the hipcc-built library made of it."""
+    from tests.native import build_image_fuzz
+    try:
+        exe = build_image_fuzz.build()
+    except build_image_fuzz.Unavailable as e:
+        pytest.skip(str(e))
+    seeds = F.reader_seeds()
+    assert len(seeds) == 16 and sorted(os.path.splitext(n)[1] for n in seeds) == [".bmp"] * 2 + [".dds"] * 4 + [".exr"] * 4 + [".pfm"] * 2 + [".pgm", ".ppm"] + [".tga"] * 2
+    paths = [F.write_file(tmp_path, n, d) for n, d in seeds.items()]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe, "-m", str(F.READER_MUTATIONS)] + paths, capture_output=True, text=True, timeout=900, env=env)
+    if r.returncode != 0 and "ASan runtime does not come first" in r.stderr:
+        pytest.skip("the sanitizer runtime cannot start in this environment: " + r.stderr.strip().splitlines()[0])
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = r.stdout.split("\n")
+    for index, (name, data) in enumerate(seeds.items()):
+        words = lines[index].split()
+        assert words[0] == name and words[1] == "prefixes" and words[4] == "mutations" and words[7] == "crc"
+        counts, crc = _load_counts_and_crc(tmp_path, index, name, data)
+        assert counts[0] + counts[1] == len(data) and counts[2] + counts[3] == F.READER_MUTATIONS
+        assert (int(words[2]), int(words[3]), int(words[5]), int(words[6])) == counts, name
+        assert int(words[8], 16) == crc, name
 
 
 # ---------------------------------------------------------------- PNG out

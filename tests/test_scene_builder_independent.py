@@ -1,4 +1,4 @@
-"""An independent check of the host scene builder's OBJ / MTL conversion (gfxh_scene_load_obj, scene_builder.cpp): a reader
+"""An independent check of the host scene builder's OBJ / MTL conversion (gfxh_scene_load_obj, host/obj_loader.cpp): a reader
 written here from the Wavefront format alone (no shared code, no vertex welding) must describe the same triangle soup,
 material by material, and the same immediate material values (createTriangleMeshes, common/common_host.cpp:2181-2430:
 one geometry per material in order of first use, assimp's FlipUVs / JoinIdenticalVertices / face normals where the file
