@@ -329,6 +329,7 @@ C_ABI_SYMBOLS = [
     "gfx_tunable_set", "gfx_stream_copy", "gfx_bc_expand",
     "gfx_tfdm_default_params", "gfx_tfdm_create", "gfx_tfdm_set_params", "gfx_tfdm_destroy", "gfx_tfdm_trace", "gfx_tfdm_read", "gfx_tfdm_size",
     "gfx_tfdm_set_create", "gfx_tfdm_set_add", "gfx_tfdm_set_transform", "gfx_tfdm_set_commit", "gfx_tfdm_set_read", "gfx_tfdm_set_destroy", "gfx_trace_scene",
+    "gfx_scene_bind_displaced", "gfx_restir_primary_rays",
 ]
 HOST_ABI_SYMBOLS = [
     "gfxh_scene_create", "gfxh_scene_destroy", "gfxh_last_error", "gfxh_scene_add_material_traditional",
@@ -906,6 +907,23 @@ class Context:
     def restir_launch(self, pass_id, width, height, stream=0):
         self._check(self.L.gfx_restir_launch(self.h, C.c_void_p(stream), C.c_int(pass_id), C.c_uint32(width), C.c_uint32(height)))
 
+    def restir_primary_rays(self, width, height, d_ray_org, d_ray_dir, stream=0):
+        """The primary rays the G-buffer pass of the current parameters generates (row-major float4 pairs, gfx_trace's layout);
+        reads rngBuffer when jittering is on and leaves it as it is."""
+        self._check(self.L.gfx_restir_primary_rays(self.h, C.c_void_p(stream), C.c_uint32(width), C.c_uint32(height), C.c_void_p(d_ray_org), C.c_void_p(d_ray_dir)))
+
+    def bind_displaced(self, tfdm_set, geom_slots=()):
+        """gfx_scene_bind_displaced: the G-buffer pass and the baseline path tracer render the displaced instances of `tfdm_set`
+        (None: unbind); geom_slots[k] is the ungrouped geometry instance k is shaded with.  Every other renderer pass is refused
+        while a set is bound."""
+        if tfdm_set is None:
+            self._check(self.L.gfx_scene_bind_displaced(self.h, None, None, C.c_uint32(0)))
+            self._displaced = None
+            return
+        slots = np.ascontiguousarray(geom_slots, np.uint32).reshape(-1)
+        self._check(self.L.gfx_scene_bind_displaced(self.h, tfdm_set.h, _p(slots), C.c_uint32(len(slots))))
+        self._displaced = tfdm_set          # the binding does not own the set: keep it alive
+
     def nrc_inference_image(self, net, which):
         """(device pointer, bytes) of the packed inference image gfx_nrc_infer reads: 0 = MLP fragments, 1 = hash grid."""
         ptr, n = C.c_void_p(), C.c_uint64()
@@ -1314,6 +1332,7 @@ class Tfdm:
 
 
 SCENE_PLAIN = 0x80000000
+GBUFFER_DISPLACED = 0x80000000       # GFX_GBUFFER_DISPLACED: gbuffer0.instSlot of a displaced pixel = GBUFFER_DISPLACED | set index
 SCENE_HIT_DTYPE = np.dtype([("dist", "<f4"), ("bcB", "<f4"), ("bcC", "<f4"), ("index", "<u4"), ("normal", "<f4", 3), ("where", "<u4")])
 TFDM_INSTANCE_DTYPE = np.dtype([("objToWorld", "<f4", 12), ("worldToObj", "<f4", 12), ("boxLo", "<f4", 3), ("userId", "<u4"), ("boxHi", "<f4", 3), ("pad0", "<u4"),
                                 ("nodes", "<u8"), ("records", "<u8"), ("heights", "<u8"), ("pyramid", "<u8"), ("params", "<u4", 8)])

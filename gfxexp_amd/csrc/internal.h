@@ -83,6 +83,18 @@ struct RestirParams {
 };
 
 struct NrcNet;
+struct TfdmSet;
+
+// A set of displaced instances the renderer passes see (gfx_scene_bind_displaced; tfdm/tfdm_set.hip).  geomSlots[k]: the geometry
+// instance k is shaded with.  The passes keep their own hit buffers here, so a gfx_trace_scene of the application (which uses the
+// set's or its own) never shares one with a frame.
+struct DisplacedBinding {
+    TfdmSet* set = nullptr;          // not owned
+    std::vector<uint32_t> geomSlots;
+    DevBuf dGeomSlots;               // uint32[instances]
+    DevBuf gbHits;                   // gfx_scene_hit per launch slot of the G-buffer pass (Context::gbRayHits stays its plain phase and hint store)
+    DevBuf ptHits, ptPlain;          // path tracer, extension trace: gfx_scene_hit / gfx_hit per queue entry
+};
 
 // Scheduling knobs of a context (none changes a result).  Defaults are the measured best on MI355X; gfx_ctx_create
 // overrides them from the environment (GFX_PIXEL_MAP, GFX_SUPER_X, GFX_SUPER_Y, GFX_TRACE_BLOCKS_PER_CU, GFX_TRACE_REFILL,
@@ -181,6 +193,7 @@ struct Context {
     // path tracer scratch (pathtrace.hip)
     DevBuf ptPending, ptExtOrg, ptExtDir, ptExtOwner, ptState;
     DevBuf rearchSlots;
+    DisplacedBinding displaced;
     DevBuf nrcState, neeTrainIdx;
     DevBuf nrcQueryCount;            // u32: inference batch size of the NRC frame (GFX_PT_NRC_COUNT_QUERIES)
     // build scratch

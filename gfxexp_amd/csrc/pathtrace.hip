@@ -26,6 +26,8 @@
 #include "pass_common.hip.h"
 #include "restir_common.hip.h"
 #include "trace_local.hip.h"
+#include "tfdm/tfdm_set.h"
+#include "tfdm/displaced_surface.hip.h"
 
 namespace gfx {
 
@@ -554,6 +556,139 @@ __global__ __launch_bounds__(kPtBlock) void k_pt_bounce(PtArgs a) {
         path.contribution = f3(s1.x, s1.y, s1.z);
     }
     const uint32_t what = pt_next_vertex<REGIR>(a, active, h, rayOrg, rayDir, static_cast<const uint64_t*>(a.s.rngBuffer) + pixel, path);
+    if (what & kPtHitSurface) {
+        static_cast<uint64_t*>(a.s.rngBuffer)[pixel] = path.rng.state;
+        a.state[2ull * pixel] = make_float4(path.alpha.x, path.alpha.y, path.alpha.z, path.dirPDensity);
+    }
+    if (what & (kPtHitSurface | kPtMissAdded)) a.state[2ull * pixel + 1] = make_float4(path.contribution.x, path.contribution.y, path.contribution.z, 0.0f);
+    push_vertex(a, pixel, path.pos, path.o);
+}
+
+// ---------------------------------------------------------------- displaced instances bound (gfx_scene_bind_displaced)
+// Sibling kernels of k_pt_first / k_pt_bounce for a scene whose traces are the scene query (tfdm/tfdm_set.hip): a lane on a plain
+// pixel / hit runs the code above, a lane on a displaced one takes its surface point from tfdm/displaced_surface.hip.h.  Ray-origin
+// offset, front-face test, Russian roulette, NEE and BSDF sampling are the same code; a displaced surface never emits
+// (gfx_scene_bind_displaced refuses such a material) and has no bump mapping, as in the reference.
+GFX_DEV tfdm::BaseVertex pt_base_vertex(const DevVertex& v) {
+    tfdm::BaseVertex b;
+    b.texCoord0Dir = tfdm::v3(v.tx, v.ty, v.tz); b.u = v.u; b.v = v.v;
+    return b;
+}
+struct PtBaseTriangle { tfdm::BaseVertex a, b, c; uint32_t materialSlot; };
+GFX_DEV PtBaseTriangle pt_base_triangle(const PtArgs& a, uint32_t geomInstSlot, uint32_t primIndex) {
+    const DevGeomInst g = a.scene.geomInsts[geomInstSlot];
+    const uint32_t* tri = a.scene.triangles + 3ull * (g.triangleOffset + primIndex);
+    PtBaseTriangle t;
+    t.a = pt_base_vertex(load_vertex(a.scene.vertices + g.vertexOffset + tri[0]));
+    t.b = pt_base_vertex(load_vertex(a.scene.vertices + g.vertexOffset + tri[1]));
+    t.c = pt_base_vertex(load_vertex(a.scene.vertices + g.vertexOffset + tri[2]));
+    t.materialSlot = g.materialSlot;
+    return t;
+}
+// The first vertex on a displaced pixel: position and normals restored from G-buffers 2 / 3 (tfdm/gpu_kernels/
+// optix_pathtracing_kernels.cu:119-126), tangent and texture coordinate from the base triangle.
+GFX_DEV void pt_first_setup_displaced(const PtArgs& a, const DisplacedArgs& d, size_t p, uint4 g0, PtPath& path, PtSetup& su) {
+    const uint32_t bufIdx = a.f.bufferIndex;
+    reset_vertex_out(path.o);
+    path.alpha = f3(1.0f);
+    path.dirPDensity = 0.0f;
+    const float bcB = decode_bc(g0.w & 0xFFFF), bcC = decode_bc(g0.w >> 16);
+    const PtBaseTriangle t = pt_base_triangle(a, g0.y, g0.z);
+    const float4 g2 = static_cast<const float4*>(a.s.gbuffer2[bufIdx])[p];
+    const uint4 g3 = static_cast<const uint4*>(a.s.gbuffer3[bufIdx])[p];
+    const tfdm::V3 ngv = tfdm::ds_decode_dir(f2bits(g2.w));
+    tfdm::V3 nsv = tfdm::ds_decode_dir(g3.x), tcv;
+    float tu, tv;
+    tfdm::displaced_frame(d.table[g0.x & ~GFX_GBUFFER_DISPLACED], t.a, t.b, t.c, bcB, bcC, nsv, tcv, tu, tv);
+    const f3 ng(ngv.x, ngv.y, ngv.z), ns(nsv.x, nsv.y, nsv.z), tc0(tcv.x, tcv.y, tcv.z);
+    f3 pos(g2.x, g2.y, g2.z);
+    const Camera cam = load_camera(a.f.camera);
+    path.rng.state = static_cast<const uint64_t*>(a.s.rngBuffer)[p];
+    const gfx_material& mat = a.scene.materials[t.materialSlot];
+    const f3 vOut = unit(cam.pos - pos);
+    const float frontHit = dot(vOut, ng) >= 0.0f ? 1.0f : -1.0f;
+    path.pos = offset_ray_origin(pos, frontHit * ng);
+    su.frame = Frame(ns, tc0);
+    su.vOutLocal = su.frame.to_local(vOut);
+    path.contribution = f3(0.0f);
+    su.bsdf.setup(a.scene, mat, tu, tv);
+    su.shade = true;
+}
+__global__ __launch_bounds__(kPtBlock) void k_pt_first_scene(PtArgs a, DisplacedArgs d) {
+    const PixelId px = pixel_of_thread(a.px);
+    const size_t p = px.p;
+    PtPath path;
+    PtSetup su;
+    uint4 g0 = make_uint4(0xFFFFFFFFu, 0, 0, 0);
+    if (px.valid) g0 = static_cast<const uint4*>(a.s.gbuffer0[a.f.bufferIndex])[p];
+    bool surface;
+    if (g0.x != 0xFFFFFFFFu && (g0.x & GFX_GBUFFER_DISPLACED)) { pt_first_setup_displaced(a, d, p, g0, path, su); surface = true; }
+    else surface = pt_first_setup<false>(a, px, path, su);
+    const EnvMap env = load_env(a.s);
+    const bool envEnabled = env.present() && a.f.enableEnvLight;
+    shade_vertex<false>(a, su.shade, env, envEnabled, path.pos, su.vOutLocal, su.frame, su.bsdf, path.rng, path.alpha, path.contribution, path.dirPDensity, path.o);
+    if (surface) static_cast<uint64_t*>(a.s.rngBuffer)[p] = path.rng.state;
+    if (px.valid) {
+        a.state[2 * p] = make_float4(path.alpha.x, path.alpha.y, path.alpha.z, path.dirPDensity);
+        a.state[2 * p + 1] = make_float4(path.contribution.x, path.contribution.y, path.contribution.z, 0.0f);
+    }
+    push_vertex(a, static_cast<uint32_t>(p), path.pos, path.o);
+}
+// A later vertex on a displaced surface: everything from the hit (optix_pathtracing_kernels.cu:289-301).
+GFX_DEV uint32_t pt_next_setup_displaced(const PtArgs& a, const DisplacedArgs& d, const tfdm::SceneHit& sh, f3 rayOrg, f3 rayDir, const uint64_t* rngBuf, PtPath& path,
+                                         PtSetup& su) {
+    reset_vertex_out(path.o);
+    const uint32_t k = sh.where >> 1;
+    const PtBaseTriangle t = pt_base_triangle(a, d.geomSlots[k], sh.index);
+    const tfdm::DisplacedPoint sp = tfdm::displaced_point(d.table[k], sh, tfdm::v3(rayOrg.x, rayOrg.y, rayOrg.z), tfdm::v3(rayDir.x, rayDir.y, rayDir.z), t.a, t.b, t.c);
+    const f3 ng(sp.normal.x, sp.normal.y, sp.normal.z), tc0(sp.tangent.x, sp.tangent.y, sp.tangent.z);
+    const gfx_material& mat = a.scene.materials[t.materialSlot];
+    const f3 vOut = unit(-rayDir);
+    const float frontHit = dot(vOut, ng) >= 0.0f ? 1.0f : -1.0f;
+    su.frame = Frame(ng, tc0);
+    path.pos = offset_ray_origin(f3(sp.position.x, sp.position.y, sp.position.z), frontHit * ng);
+    su.vOutLocal = su.frame.to_local(vOut);
+    if (rngBuf) path.rng.state = *rngBuf;
+    // Russian roulette; initImportance = sRGB_calcLuminance(RGB(1))
+    const float continueProb = fminf(luminance_srgb(path.alpha) / luminance_srgb(f3(1.0f)), 1.0f);
+    su.shade = false;
+    if (!(path.rng.uniform() >= continueProb || a.maxLengthTerminate != 0u)) {
+        path.alpha = path.alpha / continueProb;
+        su.bsdf.setup(a.scene, mat, sp.u, sp.v);
+        su.shade = true;
+    }
+    return kPtHitSurface;
+}
+__global__ __launch_bounds__(kPtBlock) void k_pt_bounce_scene(PtArgs a, DisplacedArgs d) {
+    const uint32_t i = blockIdx.x * kPtBlock + threadIdx.x;
+    const uint32_t count = *a.extCountIn;
+    PtPath path;
+    path.alpha = f3(0.0f); path.contribution = f3(0.0f); path.dirPDensity = 0.0f; path.rng.state = 0;
+    uint32_t pixel = 0;
+    gfx_hit h; h.dist = 0.0f; h.bcB = 0.0f; h.bcC = 0.0f; h.triIndex = GFX_INVALID_SLOT;
+    tfdm::SceneHit sh = tfdm::scene_miss(0.0f);
+    f3 rayOrg(0.0f), rayDir(0.0f);
+    const bool active = i < count;
+    if (active) {
+        pixel = a.extOwnerIn[i];
+        const float4 h0 = d.hits[2ull * i], h1 = d.hits[2ull * i + 1];          // a gfx_scene_hit: two 16-byte loads
+        sh.dist = h0.x; sh.bcB = h0.y; sh.bcC = h0.z; sh.index = f2bits(h0.w); sh.normal = tfdm::v3(h1.x, h1.y, h1.z); sh.where = f2bits(h1.w);
+        h.dist = h0.x; h.bcB = h0.y; h.bcC = h0.z; h.triIndex = sh.index;        // a miss carries GFX_INVALID_SLOT there
+        const float4 ro4 = a.extOrgIn[i], rd4 = a.extDirIn[i];
+        rayOrg = f3(ro4.x, ro4.y, ro4.z); rayDir = f3(rd4.x, rd4.y, rd4.z);
+        const float4 s0 = a.state[2ull * pixel], s1 = a.state[2ull * pixel + 1];
+        path.alpha = f3(s0.x, s0.y, s0.z);
+        path.dirPDensity = s0.w;
+        path.contribution = f3(s1.x, s1.y, s1.z);
+    }
+    const uint64_t* rngBuf = static_cast<const uint64_t*>(a.s.rngBuffer) + pixel;
+    PtSetup su;
+    uint32_t what;
+    if (active && sh.where != GFX_INVALID_SLOT && sh.where != GFX_SCENE_PLAIN) what = pt_next_setup_displaced(a, d, sh, rayOrg, rayDir, rngBuf, path, su);
+    else what = pt_next_setup<false>(a, active, h, rayOrg, rayDir, rngBuf, path, su);
+    const EnvMap env = load_env(a.s);
+    const bool envEnabled = env.present() && a.f.enableEnvLight;
+    shade_vertex<false>(a, su.shade, env, envEnabled, path.pos, su.vOutLocal, su.frame, su.bsdf, path.rng, path.alpha, path.contribution, path.dirPDensity, path.o);
     if (what & kPtHitSurface) {
         static_cast<uint64_t*>(a.s.rngBuffer)[pixel] = path.rng.state;
         a.state[2ull * pixel] = make_float4(path.alpha.x, path.alpha.y, path.alpha.z, path.dirPDensity);
@@ -1448,6 +1583,13 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
     }
     const RestirParams& rp = ctx.restir;
     if (!rp.valid) throw HipError("gfx_pt_launch: gfx_restir_set_params has not been called");
+    const bool displaced = ctx.displaced.set != nullptr;
+    if (displaced) {
+        if (pass != GFX_PT_PATH_TRACE_BASELINE)
+            throw HipError("gfx_pt_launch: a displaced instance set is bound (gfx_scene_bind_displaced): only the G-buffer pass and the baseline path tracer "
+                           "render displaced instances; ReGIR / NRC pass " + std::to_string(pass) + " is refused");
+        displaced_check(ctx, "gfx_pt_launch");
+    }
     const bool nrcRegir = pass == GFX_PT_PATH_TRACE_NRC_REGIR, nrcRestir = pass == GFX_PT_PATH_TRACE_NRC_RESTIR;
     const bool regirPass = (pass >= GFX_PT_REGIR_BUILD_CELL_RESERVOIRS && pass <= GFX_PT_REGIR_UPDATE_LAST_ACCESS) || nrcRegir;
     const bool nrcPass = (pass >= GFX_PT_NRC_PREPROCESS && pass <= GFX_PT_NRC_COUNT_QUERIES) || nrcRegir || nrcRestir;
@@ -1528,6 +1670,7 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
     ctx.ptExtOrg.reserve(2 * 16 * bandPixels); ctx.ptExtDir.reserve(2 * 16 * bandPixels); ctx.ptExtOwner.reserve(2 * 4 * bandPixels);
     ctx.ptState.reserve(32 * numPixels);
     if (nrc) { ctx.nrcState.reserve(32 * numPixels); ctx.neeTrainIdx.reserve(4 * numPixels); }
+    if (displaced) { ctx.displaced.ptHits.reserve(sizeof(gfx_scene_hit) * bandPixels); ctx.displaced.ptPlain.reserve(sizeof(gfx_hit) * bandPixels); }
     ctx.smallCounters.reserve(kSmallCountersBytes);
     uint32_t* counters = ctx.smallCounters.as<uint32_t>() + 8;   // [0] nee (even bounces), [1] ext ping, [2] ext pong, [3] nee (odd bounces)
     GFX_HIP(hipMemsetAsync(counters, 0, 5 * sizeof(uint32_t), stream));   // [4]: the slot ticket of k_pt_regen
@@ -1576,6 +1719,18 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
     };
     auto trace = [&](hipStream_t s, bool auxScratch, int mode, const float4* org, const float4* dir, const uint32_t* count, void* out,
                      uint32_t* zero0 = nullptr, uint32_t* zero1 = nullptr) {
+        if (displaced) {
+            // the scene query with a device-side count over the queue capacity; the extension trace's plain phase has a buffer of the
+            // binding's own, the any-hit form writes only its occlusion words: the two may overlap on two streams as the plain ones do
+            SceneTrace t;
+            t.accel = &accel; t.set = ctx.displaced.set; t.mode = mode;
+            t.rayOrgTmin = org; t.rayDirTmax = dir; t.numRays = static_cast<uint32_t>(bandPixels); t.numRaysPtr = count;
+            t.out = out; t.plainHits = ctx.displaced.ptPlain.p;
+            t.zeroWords[0] = zero0; t.zeroWords[1] = zero1;
+            if (auxScratch) { t.spill = &ctx.auxSpill; t.counters = &ctx.auxCounters; }
+            trace_scene_launch(ctx, s, t);
+            return;
+        }
         TraceLaunch t;
         t.accel = accel; t.rayOrgTmin = org; t.rayDirTmax = dir; t.numRays = 0; t.numRaysPtr = count; t.out = out; t.mode = mode;
         t.zeroWords[0] = zero0; t.zeroWords[1] = zero1;
@@ -1595,7 +1750,7 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
         const int spillCap = static_cast<int>(local_spill_depth(ctx.accels[h - 1]->maxDepth));
         const size_t spillBytes = sizeof(uint2) * static_cast<size_t>(a.px.launchBlocks) * kPtBlock * spillCap;
         const bool small = launchWaves <= waveSlots + waveSlots / 2;
-        if (!nrc && !ctx.countersEnabled && spillBytes <= (size_t(1) << 30) && (ctx.tune.fusePasses == 2 || (ctx.tune.fusePasses == 0 && small))) {
+        if (!displaced && !nrc && !ctx.countersEnabled && spillBytes <= (size_t(1) << 30) && (ctx.tune.fusePasses == 2 || (ctx.tune.fusePasses == 0 && small))) {
             ctx.spill.reserve(spillBytes);
             unsigned long long* ptDiag = nullptr;             // "pt_diag": wave iterations / lanes with a ray / traversal steps / waves / refills (gfx_pt_diag_read)
             if (ctx.tune.ptDiag) {
@@ -1628,7 +1783,13 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
             return;
         }
     }
-    if (nrc) launch_pixels("nrc_pt_first", nrcRegir ? k_nrc_pt_first<1> : nrcRestir ? k_nrc_pt_first<2> : k_nrc_pt_first<0>);
+    void* const extHits = displaced ? ctx.displaced.ptHits.p : ctx.rayHits.p;
+    if (displaced) {
+        ScopedKernelTimer timer(ctx, stream, "pt_first_scene");
+        hipLaunchKernelGGL(k_pt_first_scene, dim3(a.px.launchBlocks), dim3(kPtBlock), 0, stream, a, displaced_args(ctx, extHits));
+        GFX_HIP(hipGetLastError());
+    }
+    else if (nrc) launch_pixels("nrc_pt_first", nrcRegir ? k_nrc_pt_first<1> : nrcRestir ? k_nrc_pt_first<2> : k_nrc_pt_first<0>);
     else launch_pixels("pt_first", regir ? k_pt_first<true> : k_pt_first<false>);
     // while (true) { ++pathLength; trace; }.  Baseline: at least one extension even when maxPathLength < 2,
     // the terminal vertex (implicit light only) emits no NEE ray.  ReGIR: the loop head breaks before the
@@ -1655,7 +1816,7 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
         }
         // the extension trace also resets the two queue heads the bounce kernel appends to (the NEE head of the NEXT bounce -- not the
         // one the NEE trace above is reading -- and the other extension queue): no memset between the kernels of a bounce
-        trace(stream, false, GFX_TRACE_CLOSEST, extOrg[cur], extDir[cur], counters + 1 + cur, ctx.rayHits.p, neeCounts[nee ^ 1], counters + 1 + (cur ^ 1));
+        trace(stream, false, GFX_TRACE_CLOSEST, extOrg[cur], extDir[cur], counters + 1 + cur, extHits, neeCounts[nee ^ 1], counters + 1 + (cur ^ 1));
         join();                  // the bounce kernel adds to the contribution after k_pt_apply_nee has, and rewrites the NEE queue
         set_queues(cur, cur ^ 1);
         nee ^= 1;
@@ -1663,7 +1824,12 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
         a.pathLength = pathLength;
         a.maxLengthTerminate = (pathLength >= maxPathLength && (!nrc || maxPathLength > 0)) ? 1u : 0u;
         a.nextMaxLengthTerminate = pathLength + 1 >= maxPathLength ? 1u : 0u;
-        if (nrc) launch(stream, "nrc_pt_bounce", nrcRegir ? k_nrc_pt_bounce<1> : nrcRestir ? k_nrc_pt_bounce<2> : k_nrc_pt_bounce<0>);
+        if (displaced) {
+            ScopedKernelTimer timer(ctx, stream, "pt_bounce_scene");
+            hipLaunchKernelGGL(k_pt_bounce_scene, dim3(grid), dim3(kPtBlock), 0, stream, a, displaced_args(ctx, extHits));
+            GFX_HIP(hipGetLastError());
+        }
+        else if (nrc) launch(stream, "nrc_pt_bounce", nrcRegir ? k_nrc_pt_bounce<1> : nrcRestir ? k_nrc_pt_bounce<2> : k_nrc_pt_bounce<0>);
         else launch(stream, "pt_bounce", regir ? k_pt_bounce<true> : k_pt_bounce<false>);
         cur ^= 1;
         if (!regir && !nrc && a.maxLengthTerminate) break;

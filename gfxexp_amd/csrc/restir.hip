@@ -21,6 +21,8 @@
 #include "coop_fetch.hip.h"
 #include "trace_local.hip.h"
 #include "restir_rearch.hip.h"
+#include "tfdm/tfdm_set.h"
+#include "tfdm/displaced_surface.hip.h"
 
 namespace gfx {
 
@@ -28,6 +30,7 @@ namespace gfx {
 // ray generation of optix_gbuffer_kernels.cu:5-27
 // (org.xyz | tmin, dir.xyz | tmax) of the pixel's primary ray; a launch slot without a pixel holds an empty-interval ray (an immediate miss)
 struct RayPair { float4 org, dir; };
+template <bool WRITE_RNG = true>          // false: gfx_restir_primary_rays, which only looks
 GFX_DEV RayPair primary_ray(const RestirArgs& a, const PixelId& px) {
     RayPair r;
     r.org = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -42,7 +45,7 @@ GFX_DEV RayPair primary_ray(const RestirArgs& a, const PixelId& px) {
         Pcg32 rng; rng.state = rngBuf[p];
         jx = rng.uniform();
         jy = rng.uniform();
-        rngBuf[p] = rng.state;
+        if (WRITE_RNG) rngBuf[p] = rng.state;
     }
     const float fx = (x + jx) / a.s.imageSizeX;
     const float fy = (y + jy) / a.s.imageSizeY;
@@ -59,6 +62,14 @@ __global__ __launch_bounds__(kBlock) void k_primary_rays(RestirArgs a) {
     a.rayOrg[px.slot] = r.org;
     a.rayDir[px.slot] = r.dir;
 }
+// gfx_restir_primary_rays: the same rays, row-major and one per pixel
+__global__ __launch_bounds__(kBlock) void k_primary_rays_inspect(RestirArgs a, float4* __restrict__ org, float4* __restrict__ dir) {
+    const PixelId px = pixel_of_thread(a.px);
+    if (!px.valid) return;
+    const RayPair r = primary_ray<false>(a, px);
+    org[px.p] = r.org;
+    dir[px.p] = r.dir;
+}
 
 // PerspectiveCamera::calcScreenPosition, restir_di_shared.h:51-59
 GFX_DEV void calc_screen_position(const Camera& cam, f3 pw, float& sx, float& sy) {
@@ -71,11 +82,33 @@ GFX_DEV void calc_screen_position(const Camera& cam, f3 pw, float& sx, float& sy
     sy = 1 - (ay + 0.5f * h) / h;
 }
 
+// the four G-buffer elements of a pixel and its albedo / normal accumulation (optix_gbuffer_kernels.cu:113-158)
+GFX_DEV void gbuffer_store(const RestirArgs& a, size_t p, uint4 g0, float2 g1, float4 g2, uint4 g3, f3 albedo, f3 shadingNormalInWorld) {
+    const uint32_t bufIdx = a.f.bufferIndex;
+    static_cast<uint4*>(a.s.gbuffer0[bufIdx])[p] = g0;
+    static_cast<float2*>(a.s.gbuffer1[bufIdx])[p] = g1;
+    static_cast<float4*>(a.s.gbuffer2[bufIdx])[p] = g2;
+    static_cast<uint4*>(a.s.gbuffer3[bufIdx])[p] = g3;
+
+    float4* albedoAcc = static_cast<float4*>(a.s.albedoAccumBuffer) + p;
+    float4* normalAcc = static_cast<float4*>(a.s.normalAccumBuffer) + p;
+    f3 prevAlbedo(0.0f), prevNormal(0.0f);
+    if (a.f.numAccumFrames > 0) {
+        const float4 pa = *albedoAcc, pn = *normalAcc;
+        prevAlbedo = f3(pa.x, pa.y, pa.z);
+        prevNormal = f3(pn.x, pn.y, pn.z);
+    }
+    const float curWeight = 1.0f / (1 + a.f.numAccumFrames);
+    const f3 albedoResult = (1 - curWeight) * prevAlbedo + curWeight * albedo;
+    const f3 normalResult = (1 - curWeight) * prevNormal + curWeight * shadingNormalInWorld;
+    *albedoAcc = make_float4(albedoResult.x, albedoResult.y, albedoResult.z, 1.0f);
+    *normalAcc = make_float4(normalResult.x, normalResult.y, normalResult.z, 1.0f);
+}
+
 // closest-hit / miss programs + the tail of the ray-generation program (optix_gbuffer_kernels.cu:56-243)
 GFX_DEV void gbuffer_resolve(const RestirArgs& a, const PixelId& px, const gfx_hit& h, f3 direction) {
     const size_t p = px.p;
     const int x = px.x, y = px.y;
-    const uint32_t bufIdx = a.f.bufferIndex;
 
     f3 albedo(0.0f);
     const float qnan = bits2f(0x7FC00000u);
@@ -155,30 +188,59 @@ GFX_DEV void gbuffer_resolve(const RestirArgs& a, const PixelId& px, const gfx_h
     float mvy = (y + 0.5f) - sy * a.s.imageSizeY;
     if (a.f.resetFlowBuffer || prevPositionInWorld.x != prevPositionInWorld.x) { mvx = 0.0f; mvy = 0.0f; }
 
-    static_cast<uint4*>(a.s.gbuffer0[bufIdx])[p] = make_uint4(instSlot, geomInstSlot, primIndex, qbcB | (qbcC << 16));
-    static_cast<float2*>(a.s.gbuffer1[bufIdx])[p] = make_float2(mvx, mvy);
-    static_cast<float4*>(a.s.gbuffer2[bufIdx])[p] = make_float4(positionInWorld.x, positionInWorld.y, positionInWorld.z, bits2f(qGeomNormal));
-    static_cast<uint4*>(a.s.gbuffer3[bufIdx])[p] = make_uint4(encode_dir(shadingNormalInWorld), qTangent, qTexCoord, matSlot);
-
-    float4* albedoAcc = static_cast<float4*>(a.s.albedoAccumBuffer) + p;
-    float4* normalAcc = static_cast<float4*>(a.s.normalAccumBuffer) + p;
-    f3 prevAlbedo(0.0f), prevNormal(0.0f);
-    if (a.f.numAccumFrames > 0) {
-        const float4 pa = *albedoAcc, pn = *normalAcc;
-        prevAlbedo = f3(pa.x, pa.y, pa.z);
-        prevNormal = f3(pn.x, pn.y, pn.z);
-    }
-    const float curWeight = 1.0f / (1 + a.f.numAccumFrames);
-    const f3 albedoResult = (1 - curWeight) * prevAlbedo + curWeight * albedo;
-    const f3 normalResult = (1 - curWeight) * prevNormal + curWeight * shadingNormalInWorld;
-    *albedoAcc = make_float4(albedoResult.x, albedoResult.y, albedoResult.z, 1.0f);
-    *normalAcc = make_float4(normalResult.x, normalResult.y, normalResult.z, 1.0f);
+    gbuffer_store(a, p, make_uint4(instSlot, geomInstSlot, primIndex, qbcB | (qbcC << 16)), make_float2(mvx, mvy),
+                  make_float4(positionInWorld.x, positionInWorld.y, positionInWorld.z, bits2f(qGeomNormal)),
+                  make_uint4(encode_dir(shadingNormalInWorld), qTangent, qTexCoord, matSlot), albedo, shadingNormalInWorld);
 }
 __global__ __launch_bounds__(kBlock) void k_gbuffer_resolve(RestirArgs a) {
     const PixelId px = pixel_of_thread(a.px);
     if (!px.valid) return;
     const float4 rd = a.rayDir[px.slot];
     gbuffer_resolve(a, px, a.hits[px.slot], f3(rd.x, rd.y, rd.z));
+}
+
+// The same pass over a scene with displaced instances bound (gfx_scene_bind_displaced): the trace is the scene query
+// (tfdm/tfdm_set.hip) and a pixel's hit a gfx_scene_hit.  A plain hit or a miss is resolved by the code above; a displaced hit by
+// tfdm/displaced_surface.hip.h (the closest-hit program's displaced branch, tfdm/gpu_kernels/optix_gbuffer_kernels.cu:218-271).
+// BSDF textures are read at level 0 (the reference passes the object's targetMipLevel; this library's textures have no mip chain);
+// no bump mapping on a displaced surface, as in the reference.
+GFX_DEV tfdm::V3 to_v3(f3 v) { return tfdm::v3(v.x, v.y, v.z); }
+GFX_DEV f3 to_f3(tfdm::V3 v) { return f3(v.x, v.y, v.z); }
+GFX_DEV tfdm::BaseVertex base_vertex(const DevVertex& v) {
+    tfdm::BaseVertex b;
+    b.texCoord0Dir = tfdm::v3(v.tx, v.ty, v.tz); b.u = v.u; b.v = v.v;
+    return b;
+}
+__global__ __launch_bounds__(kBlock) void k_gbuffer_resolve_scene(RestirArgs a, DisplacedArgs d) {
+    const PixelId px = pixel_of_thread(a.px);
+    if (!px.valid) return;
+    const float4 ro = a.rayOrg[px.slot], rd = a.rayDir[px.slot];
+    const float4 h0 = d.hits[2ull * px.slot], h1 = d.hits[2ull * px.slot + 1];
+    const uint32_t where = f2bits(h1.w);
+    if (where == GFX_INVALID_SLOT || where == GFX_SCENE_PLAIN) {
+        gfx_hit h; h.dist = h0.x; h.bcB = h0.y; h.bcC = h0.z; h.triIndex = f2bits(h0.w);     // a miss carries GFX_INVALID_SLOT there
+        gbuffer_resolve(a, px, h, f3(rd.x, rd.y, rd.z));
+        return;
+    }
+    tfdm::SceneHit sh;
+    sh.dist = h0.x; sh.bcB = h0.y; sh.bcC = h0.z; sh.index = f2bits(h0.w); sh.normal = tfdm::v3(h1.x, h1.y, h1.z); sh.where = where;
+    const uint32_t k = where >> 1;
+    const uint32_t geomInstSlot = d.geomSlots[k];
+    const DevGeomInst g = a.scene.geomInsts[geomInstSlot];
+    const uint32_t* tri = a.scene.triangles + 3ull * (g.triangleOffset + sh.index);
+    const tfdm::BaseVertex vA = base_vertex(load_vertex(a.scene.vertices + g.vertexOffset + tri[0]));
+    const tfdm::BaseVertex vB = base_vertex(load_vertex(a.scene.vertices + g.vertexOffset + tri[1]));
+    const tfdm::BaseVertex vC = base_vertex(load_vertex(a.scene.vertices + g.vertexOffset + tri[2]));
+    const tfdm::DisplacedPoint sp = tfdm::displaced_point(d.table[k], sh, tfdm::v3(ro.x, ro.y, ro.z), tfdm::v3(rd.x, rd.y, rd.z), vA, vB, vC);
+    const tfdm::DisplacedGBuffer gb = tfdm::displaced_gbuffer(sp, sh, geomInstSlot, g.materialSlot, a.f.prevCamera, px.x, px.y, a.s.imageSizeX, a.s.imageSizeY,
+                                                              a.f.resetFlowBuffer != 0);
+    const gfx_material& mat = a.scene.materials[g.materialSlot];
+    Bsdf bsdf; bsdf.setup(a.scene, mat, sp.u, sp.v);
+    const Frame frame(to_f3(sp.normal), to_f3(sp.tangent));
+    const f3 albedo = bsdf.dh_reflectance_estimate(frame.to_local(unit(-f3(rd.x, rd.y, rd.z))));
+    gbuffer_store(a, px.p, make_uint4(gb.g0[0], gb.g0[1], gb.g0[2], gb.g0[3]), make_float2(gb.mv[0], gb.mv[1]),
+                  make_float4(gb.position[0], gb.position[1], gb.position[2], bits2f(gb.qGeometricNormal)), make_uint4(gb.g3[0], gb.g3[1], gb.g3[2], gb.g3[3]),
+                  albedo, to_f3(sp.normal));
 }
 
 // ---------------------------------------------------------------- INITIAL (+ TEMPORAL)
@@ -1202,10 +1264,26 @@ void restir_visualize(Context& ctx, hipStream_t stream, const void* linearBuffer
     GFX_HIP(hipGetLastError());
 }
 
+void restir_primary_rays(Context& ctx, hipStream_t stream, uint32_t width, uint32_t height, void* dRayOrgTmin, void* dRayDirTmax) {
+    if (!dRayOrgTmin || !dRayDirTmax) throw HipError("gfx_restir_primary_rays: null output");
+    if ((reinterpret_cast<uintptr_t>(dRayOrgTmin) | reinterpret_cast<uintptr_t>(dRayDirTmax)) & 15u) throw HipError("gfx_restir_primary_rays: the outputs must be 16-byte aligned");
+    const RestirArgs a = make_args(ctx, width, height, 0, height, false);
+    if (a.px.launchBlocks == 0) return;
+    hipLaunchKernelGGL(k_primary_rays_inspect, dim3(a.px.launchBlocks), dim3(kBlock), 0, stream, a, static_cast<float4*>(dRayOrgTmin), static_cast<float4*>(dRayDirTmax));
+    GFX_HIP(hipGetLastError());
+}
+
 void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, uint32_t height, uint32_t rowBegin, uint32_t rowEnd, uint32_t gapBegin, uint32_t gapEnd) {
     const bool rearch = pass >= GFX_RESTIR_LIGHT_PRESAMPLING && pass <= GFX_RESTIR_SHADE_AND_RESAMPLE_SPATIOTEMPORAL;
     // a gap (gfx_restir_launch_rows_gap) is for the pass a band renderer splits around its exchange: the biased spatial pass, a plain per-pixel kernel
     if (gapEnd > gapBegin && pass != GFX_RESTIR_SPATIAL_BIASED) throw HipError("gfx_restir_launch_rows_gap: only GFX_RESTIR_SPATIAL_BIASED takes a gap");
+    const bool displaced = ctx.displaced.set != nullptr;
+    if (displaced) {
+        if (pass != GFX_RESTIR_SETUP_GBUFFERS)
+            throw HipError("gfx_restir_launch: a displaced instance set is bound (gfx_scene_bind_displaced): only the G-buffer pass and the baseline path tracer "
+                           "render displaced instances; ReSTIR pass " + std::to_string(pass) + " is refused");
+        displaced_check(ctx, "gfx_restir_launch");
+    }
     RestirArgs a = make_args(ctx, width, height, rowBegin, rowEnd, rearch, gapBegin, gapEnd);
     if (rowEnd == rowBegin || a.px.launchBlocks == 0) return;
     auto reset_queue = [&]() { GFX_HIP(hipMemsetAsync(a.rayCount, 0, sizeof(uint32_t), stream)); };
@@ -1249,6 +1327,25 @@ void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, u
         // primary rays are coherent (neighbouring lanes walk nearly the same nodes, the temporal hint ends most of them early): the
         // wave-local traversal loses little to the missing refill and saves the ray queue and two launches at every size (rearchitected
         // ReSTIR at 1920x1080: 2.250 -> 2.115 ms per frame, NRC 3.65 -> 3.53) -- fused unless "fuse_passes" says never
+        if (displaced) {
+            // the wavefront form whatever "fuse_passes" says: the trace is the scene query.  Its plain phase writes gbRayHits, which so
+            // stays the temporal hint store; the instance phase widens into a buffer of the binding's own.
+            ctx.displaced.gbHits.reserve(sizeof(gfx_scene_hit) * frameSlots);
+            launch_pixels(ctx, stream, "primary_rays", k_primary_rays, a);
+            const DevAccel accel = ctx.accels[ctx.restir.f.travHandle - 1]->dev();
+            SceneTrace t;
+            t.accel = &accel; t.set = ctx.displaced.set; t.mode = GFX_TRACE_CLOSEST;
+            t.rayOrgTmin = a.rayOrg; t.rayDirTmax = a.rayDir;
+            t.numRays = numSlots;
+            t.out = ctx.displaced.gbHits.p; t.plainHits = ctx.gbRayHits.p;
+            t.spill = &ctx.gbSpill; t.counters = &ctx.gbCounters;
+            t.hintFromOut = true;
+            trace_scene_launch(ctx, stream, t);
+            ScopedKernelTimer timer(ctx, stream, "gbuffer_resolve_scene");
+            hipLaunchKernelGGL(k_gbuffer_resolve_scene, dim3(a.px.launchBlocks), dim3(kBlock), 0, stream, a, displaced_args(ctx, ctx.displaced.gbHits.p));
+            GFX_HIP(hipGetLastError());
+            break;
+        }
         if (!ctx.countersEnabled && fusedSpillBytes <= (size_t(1) << 30) && ctx.tune.fusePasses != 1) {
             ctx.gbSpill.reserve(fusedSpillBytes);
             const uint32_t* order = nullptr;

@@ -26,6 +26,38 @@ void tfdm_set_transform(TfdmSet& s, uint32_t index, const float objToWorld[12]);
 void tfdm_set_commit(TfdmSet& s, hipStream_t stream);
 void tfdm_set_read(TfdmSet& s, void* hostOut, size_t bytes);
 void tfdm_set_release(TfdmSet& s);
+// The scene query as the passes launch it (restir.hip, pathtrace.hip).  The ray count may be a device word (numRaysPtr; numRays is
+// then the queue capacity: k_scene_instances launches over it and the waves beyond the count leave at once), as TraceLaunch's is for
+// k_trace, so a bounce loop needs no host read-back.  spill / counters / zeroWords / hintFromOut go to the plain phase's TraceLaunch
+// unchanged.  plainHits: gfx_hit[numRays] the plain phase of a closest-hit query writes and the instance phase widens -- the caller's,
+// so that two queries in flight on two streams never share one.
+struct SceneTrace {
+    const DevAccel* accel = nullptr;
+    TfdmSet* set = nullptr;
+    int mode = 0;
+    const float4* rayOrgTmin = nullptr; const float4* rayDirTmax = nullptr;
+    uint32_t numRays = 0; const uint32_t* numRaysPtr = nullptr;
+    void* out = nullptr;
+    void* plainHits = nullptr;
+    void* statCounters = nullptr;       // u64[8] of gfx_trace_scene, optional
+    DevBuf* spill = nullptr; DevBuf* counters = nullptr;
+    uint32_t* zeroWords[2] = { nullptr, nullptr };
+    bool hintFromOut = false;           // plainHits still holds the previous launch's plain hits for the same rays
+};
+void trace_scene_launch(Context& ctx, hipStream_t stream, const SceneTrace& t);
+void trace_scene_check_set(const TfdmSet& set, int device, const char* who);   // throws: foreign device, uncommitted change, stale member
+
+// what the set-bound passes read of a displaced hit: gfx_scene_hit[] as two float4 per entry, the committed instance table and the
+// geometry each instance is shaded with (Context::displaced)
+struct DisplacedArgs { const float4* hits; const tfdm::InstanceRecord* table; const uint32_t* geomSlots; };
+
+// gfx_scene_bind_displaced (set == nullptr: unbind) and the check every set-bound launch repeats: the set as gfx_trace_scene wants
+// it, and no bound geometry's material emitting (a material may have been set after the bind).
+void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint32_t n);
+void displaced_check(Context& ctx, const char* who);
+DisplacedArgs displaced_args(const Context& ctx, const void* hits);
+void restir_primary_rays(Context& ctx, hipStream_t stream, uint32_t width, uint32_t height, void* dRayOrgTmin, void* dRayDirTmax);   // restir.hip
+
 // set == nullptr: no displaced instances; accel == nullptr: no plain geometry.  `fallbackPlain`: the plain-phase buffer of a
 // closest-hit query without a set (the context's).
 void trace_scene(Context& ctx, hipStream_t stream, const DevAccel* accel, TfdmSet* set, DevBuf& fallbackPlain, int mode, const void* dRayOrgTmin,

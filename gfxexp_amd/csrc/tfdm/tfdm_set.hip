@@ -11,6 +11,7 @@
 //                    instance no lane of the wave enters is skipped by ballot.
 //
 // Register count, scratch and occupancy: DESIGN.md section 15.
+#include <algorithm>
 #include <cstring>
 #include "tfdm_set.h"
 #include "tfdm_lds_stack.hip.h"
@@ -26,9 +27,14 @@ using SceneStack = LdsColumnStack<kSceneBlock>;
 
 template <bool ANY_HIT>
 __global__ void __launch_bounds__(kSceneBlock) k_scene_instances(const InstanceRecord* __restrict__ table, uint32_t numInstances, const float4* __restrict__ rayOrgTmin,
-                                                                 const float4* __restrict__ rayDirTmax, uint32_t numRays, const void* plain, void* out,
-                                                                 unsigned long long* __restrict__ counters) {
+                                                                 const float4* __restrict__ rayDirTmax, uint32_t numRays, const uint32_t* __restrict__ numRaysPtr, const void* plain,
+                                                                 void* out, unsigned long long* __restrict__ counters) {
     __shared__ uint2 s_stack[kStackDepth * kSceneBlock];
+    if (numRaysPtr) {                            // a device-side count: the launch covers the queue capacity
+        const uint32_t count = *numRaysPtr;
+        numRays = count < numRays ? count : numRays;
+        if (blockIdx.x * kSceneBlock >= numRays) return;
+    }
     const uint32_t i = blockIdx.x * kSceneBlock + threadIdx.x;
     const bool live = i < numRays;
     TraceStats ts;
@@ -140,16 +146,99 @@ void tfdm_set_read(TfdmSet& s, void* hostOut, size_t bytes) {
 
 void tfdm_set_release(TfdmSet& s) { s.table.release(); s.plain.release(); }
 
+void trace_scene_check_set(const TfdmSet& set, int device, const char* who) {
+    const std::string w(who);
+    if (set.device != device) throw HipError(w + ": the instance set belongs to another device");
+    if (set.dirty) throw HipError(w + ": the instance set has an add or a transform that is not committed (gfx_tfdm_set_commit)");
+    for (size_t k = 0; k < set.members.size(); ++k)
+        if (set.members[k].generation != set.members[k].obj->generation)
+            throw HipError(w + ": instance " + std::to_string(k) + "'s object had gfx_tfdm_set_params after the set was committed; commit the set again");
+}
+
+void trace_scene_launch(Context& ctx, hipStream_t stream, const SceneTrace& s) {
+    if (s.numRays == 0) return;
+    const bool any = s.mode == GFX_TRACE_ANY;
+    const uint32_t numInstances = s.set ? static_cast<uint32_t>(s.set->host.size()) : 0u;
+    // Plain phase.  An any-hit answer has the output's own format: k_trace writes it in place and the instance phase goes over
+    // it.  A closest hit is a 16-byte gfx_hit that the instance phase widens, so it goes through a buffer.
+    const void* plain = nullptr;
+    if (s.accel) {
+        void* dst = any ? s.out : s.plainHits;
+        TraceLaunch t;
+        t.accel = *s.accel;
+        t.rayOrgTmin = s.rayOrgTmin; t.rayDirTmax = s.rayDirTmax;
+        t.numRays = s.numRays; t.numRaysPtr = s.numRaysPtr; t.out = dst; t.mode = s.mode;
+        t.spill = s.spill; t.counters = s.counters;
+        t.zeroWords[0] = s.zeroWords[0]; t.zeroWords[1] = s.zeroWords[1];
+        t.hintFromOut = s.hintFromOut;
+        trace_launch(ctx, stream, t);
+        plain = dst;
+        if (any && numInstances == 0 && !s.statCounters) return;
+    }
+    else {
+        // no plain phase to zero the queue heads a path tracer hands over: stream order does
+        for (uint32_t* w : s.zeroWords) if (w) GFX_HIP(hipMemsetAsync(w, 0, sizeof(uint32_t), stream));
+    }
+    const uint32_t blocks = (s.numRays + kSceneBlock - 1u) / kSceneBlock;
+    const InstanceRecord* table = numInstances ? s.set->table.as<InstanceRecord>() : nullptr;
+    unsigned long long* cnt = static_cast<unsigned long long*>(s.statCounters);
+    ScopedKernelTimer timer(ctx, stream, "k_scene_instances");
+    if (any) k_scene_instances<true><<<blocks, kSceneBlock, 0, stream>>>(table, numInstances, s.rayOrgTmin, s.rayDirTmax, s.numRays, s.numRaysPtr, plain, s.out, cnt);
+    else k_scene_instances<false><<<blocks, kSceneBlock, 0, stream>>>(table, numInstances, s.rayOrgTmin, s.rayDirTmax, s.numRays, s.numRaysPtr, plain, s.out, cnt);
+    GFX_HIP(hipGetLastError());
+}
+
+void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint32_t n) {
+    DisplacedBinding& b = ctx.displaced;
+    if (!set) { b.set = nullptr; b.geomSlots.clear(); return; }
+    if (set->device != ctx.device) throw HipError("gfx_scene_bind_displaced: the instance set belongs to another device");
+    if (n != set->members.size())
+        throw HipError("gfx_scene_bind_displaced: " + std::to_string(n) + " geometry slots for a set of " + std::to_string(set->members.size()) + " instances");
+    if (n && !geomSlots) throw HipError("gfx_scene_bind_displaced: null geometry slots");
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::string who = "gfx_scene_bind_displaced: instance " + std::to_string(k) + ": ";
+        if (geomSlots[k] >= ctx.geoms.size()) throw HipError(who + "unknown geometry slot " + std::to_string(geomSlots[k]));
+        const HostGeom& g = ctx.geoms[geomSlots[k]];
+        if (g.triangles.size() / 3 != set->members[k].obj->numTriangles)
+            throw HipError(who + "geometry slot " + std::to_string(geomSlots[k]) + " has " + std::to_string(g.triangles.size() / 3) + " triangles, the displaced object " +
+                           std::to_string(set->members[k].obj->numTriangles) + " (triangle count mismatch)");
+        if (g.materialSlot < ctx.materials.size() && ctx.materials[g.materialSlot].hasEmittance)
+            throw HipError(who + "the material of geometry slot " + std::to_string(geomSlots[k]) + " has emittance; displaced emitters are not supported");
+    }
+    // (a reserve() that has to grow frees the old table with hipFree, which waits for the passes that read it)
+    std::vector<uint32_t> slots(geomSlots, geomSlots + n);
+    b.dGeomSlots.reserve(std::max<size_t>(sizeof(uint32_t) * n, 16));
+    if (n) GFX_HIP(hipMemcpy(b.dGeomSlots.p, slots.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+    b.geomSlots.swap(slots);
+    b.set = set;
+}
+
+void displaced_check(Context& ctx, const char* who) {
+    const DisplacedBinding& b = ctx.displaced;
+    trace_scene_check_set(*b.set, ctx.device, who);
+    if (b.geomSlots.size() != b.set->members.size())
+        throw HipError(std::string(who) + ": the bound instance set has grown since gfx_scene_bind_displaced; bind it again");
+    for (size_t k = 0; k < b.geomSlots.size(); ++k) {
+        if (b.geomSlots[k] >= ctx.hGeomInsts.size())
+            throw HipError(std::string(who) + ": the geometry of displaced instance " + std::to_string(k) + " is not on the device yet (gfx_accel_build uploads the scene)");
+        const uint32_t m = ctx.geoms[b.geomSlots[k]].materialSlot;
+        if (m < ctx.materials.size() && ctx.materials[m].hasEmittance)
+            throw HipError(std::string(who) + ": the material of displaced instance " + std::to_string(k) + " has emittance; displaced emitters are not supported");
+    }
+}
+
+DisplacedArgs displaced_args(const Context& ctx, const void* hits) {
+    DisplacedArgs d;
+    d.hits = static_cast<const float4*>(hits);
+    d.table = ctx.displaced.set->table.as<InstanceRecord>();
+    d.geomSlots = ctx.displaced.dGeomSlots.as<uint32_t>();
+    return d;
+}
+
 void trace_scene(Context& ctx, hipStream_t stream, const DevAccel* accel, TfdmSet* set, DevBuf& fallbackPlain, int mode, const void* dRayOrgTmin,
                  const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters) {
     if (mode != GFX_TRACE_CLOSEST && mode != GFX_TRACE_ANY) throw HipError("gfx_trace_scene: unknown mode");
-    if (set) {
-        if (set->device != ctx.device) throw HipError("gfx_trace_scene: the instance set belongs to another device");
-        if (set->dirty) throw HipError("gfx_trace_scene: the instance set has an add or a transform that is not committed (gfx_tfdm_set_commit)");
-        for (size_t k = 0; k < set->members.size(); ++k)
-            if (set->members[k].generation != set->members[k].obj->generation)
-                throw HipError("gfx_trace_scene: instance " + std::to_string(k) + "'s object had gfx_tfdm_set_params after the set was committed; commit the set again");
-    }
+    if (set) trace_scene_check_set(*set, ctx.device, "gfx_trace_scene");
     if (numRays == 0) return;
     if (!dRayOrgTmin || !dRayDirTmax || !dOut) throw HipError("gfx_trace_scene: null ray or output buffer");
     // rays are read as float4 and a closest hit is written as two float4; an any-hit answer is one uint32
@@ -158,34 +247,16 @@ void trace_scene(Context& ctx, hipStream_t stream, const DevAccel* accel, TfdmSe
     if ((reinterpret_cast<uintptr_t>(dRayOrgTmin) & 15u) || (reinterpret_cast<uintptr_t>(dRayDirTmax) & 15u) || (reinterpret_cast<uintptr_t>(dOut) & outMask))
         throw HipError("gfx_trace_scene: the ray buffers and a closest-hit output must be 16-byte aligned (an any-hit output 4-byte)");
     if (reinterpret_cast<uintptr_t>(dCounters) & 7u) throw HipError("gfx_trace_scene: the counters must be 8-byte aligned");
-    const uint32_t numInstances = set ? static_cast<uint32_t>(set->host.size()) : 0u;
-    const float4* org = static_cast<const float4*>(dRayOrgTmin);
-    const float4* dir = static_cast<const float4*>(dRayDirTmax);
-    // Plain phase.  An any-hit answer has the output's own format: k_trace writes it in place and the instance phase goes over
-    // it.  A closest hit is a 16-byte gfx_hit that the instance phase widens, so it goes through a buffer.
-    const void* plain = nullptr;
-    if (accel) {
-        void* dst = dOut;
-        if (!any) {
-            DevBuf& buf = set ? set->plain : fallbackPlain;
-            buf.reserve(sizeof(gfx_hit) * static_cast<size_t>(numRays));
-            dst = buf.p;
-        }
-        TraceLaunch t;
-        t.accel = *accel;
-        t.rayOrgTmin = org; t.rayDirTmax = dir;
-        t.numRays = numRays; t.numRaysPtr = nullptr; t.out = dst; t.mode = mode;
-        trace_launch(ctx, stream, t);
-        plain = dst;
-        if (any && numInstances == 0 && !dCounters) return;
+    SceneTrace s;
+    s.accel = accel; s.set = set; s.mode = mode;
+    s.rayOrgTmin = static_cast<const float4*>(dRayOrgTmin); s.rayDirTmax = static_cast<const float4*>(dRayDirTmax);
+    s.numRays = numRays; s.out = dOut; s.statCounters = dCounters;
+    if (accel && !any) {
+        DevBuf& buf = set ? set->plain : fallbackPlain;
+        buf.reserve(sizeof(gfx_hit) * static_cast<size_t>(numRays));
+        s.plainHits = buf.p;
     }
-    const uint32_t blocks = (numRays + kSceneBlock - 1u) / kSceneBlock;
-    const InstanceRecord* table = numInstances ? set->table.as<InstanceRecord>() : nullptr;
-    unsigned long long* cnt = static_cast<unsigned long long*>(dCounters);
-    ScopedKernelTimer timer(ctx, stream, "k_scene_instances");
-    if (any) k_scene_instances<true><<<blocks, kSceneBlock, 0, stream>>>(table, numInstances, org, dir, numRays, plain, dOut, cnt);
-    else k_scene_instances<false><<<blocks, kSceneBlock, 0, stream>>>(table, numInstances, org, dir, numRays, plain, dOut, cnt);
-    GFX_HIP(hipGetLastError());
+    trace_scene_launch(ctx, stream, s);
 }
 
 } // namespace gfx

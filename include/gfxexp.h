@@ -725,8 +725,8 @@ int gfx_bc_expand(gfx_ctx* ctx, void* stream, uint32_t bcFormat, const void* dBl
  * space of the base mesh, in gfx_trace's layout (origin | tmin, direction | tmax), and a ray's tmax lets the caller chain
  * the query behind gfx_trace for a scene that mixes plain and displaced geometry: trace the plain geometry first, hand its
  * hit distance in as tmax, and a displaced hit that comes back is the closer one.  gfx_trace_scene below does that chain in
- * one call, for any number of displaced instances under their own transforms; the G-buffer pass and the renderers do not
- * see displaced geometry. */
+ * one call, for any number of displaced instances under their own transforms; gfx_scene_bind_displaced at the end of this
+ * section makes the G-buffer pass and the baseline path tracer render them. */
 typedef struct gfx_tfdm gfx_tfdm;                       /* opaque; owns heights, pyramid, records, AABBs, tree */
 enum gfx_tfdm_local { GFX_TFDM_BOX = 0, GFX_TFDM_TWO_TRIANGLE = 1 };   /* LocalIntersectionType, tfdm/tfdm_shared.h; Bilinear and BSpline are not built */
 /* DisplacementParameters, tfdm/tfdm_shared.h, with the texture transform as the scale / rotation (degrees) / offset it is made
@@ -806,6 +806,32 @@ typedef struct gfx_scene_hit { float dist, bcB, bcC; uint32_t index; float norma
  * uncommitted add or transform, or with a member whose gfx_tfdm_set_params ran after the commit, is refused with a message. */
 int gfx_trace_scene(gfx_ctx* ctx, void* stream, uint64_t accel, gfx_tfdm_set* set, int mode, const void* dRayOrgTmin, const void* dRayDirTmax,
                     uint32_t numRays, void* dOut, void* dCounters);
+
+/* Displaced instances in the renderer.  While a set is bound, GFX_RESTIR_SETUP_GBUFFERS / GFX_PT_SETUP_GBUFFERS
+ * and GFX_PT_PATH_TRACE_BASELINE trace plain and displaced geometry together (the scene query above, in their wavefront form whatever
+ * "fuse_passes" says); every other renderer pass (ReSTIR, the rearchitected set, ReGIR, NRC) is refused with a message.  Without a
+ * binding every pass does what it always did.
+ *   geomInstSlots[k]  the geometry instance k of the set is shaded with: a gfx_geom_create of the vertex and triangle arrays the
+ *                     instance's gfx_tfdm was created from, put in NO group (so it is not in the BVH8).  Material, texture
+ *                     coordinates and texCoord0Dir come from it, transform and normal matrix from the instance's record.
+ * Refused: n other than the set's instance count, an unknown slot, a slot whose triangle count differs from the object's, a slot
+ * whose material emits (the light distributions do not know displaced emitters).  A set with an uncommitted change is refused at
+ * launch, as gfx_trace_scene refuses it.  set == NULL unbinds; gfx_tfdm_set_destroy of the bound set unbinds too.
+ * A displaced pixel in the G-buffers:
+ *   gbuffer0   instSlot = GFX_GBUFFER_DISPLACED | k (k: the set index; 0xFFFFFFFF stays "no surface"), geomInstSlot = the bound
+ *              geometry, primIndex = the base triangle, qbcB / qbcC = the base barycentrics
+ *   gbuffer1   displaced instances are static for the motion vector: prevPositionInWorld = positionInWorld, only the camera moves
+ *   gbuffer2   positionInWorld = origin + distance * direction of the world ray; qGeometricNormal = the hit's world normal
+ *   gbuffer3   qShadingNormal = the same normal (no bump mapping on a displaced surface, as in the reference), qShadingTangent =
+ *              texCoord0Dir of the base triangle in world space, orthogonal to it; qTexCoord, matSlot from the base triangle
+ * BSDF textures are read at level 0 (this library's textures have no mip chain; the reference passes targetMipLevel).
+ * G-buffers that hold displaced pixels are for the passes above and the output-chain copies; run the G-buffer pass again after
+ * unbinding before any other pass reads them. */
+#define GFX_GBUFFER_DISPLACED 0x80000000u
+int gfx_scene_bind_displaced(gfx_ctx* ctx, gfx_tfdm_set* set, const uint32_t* geomInstSlots, uint32_t n);   /* set == NULL: unbind */
+/* The primary rays the G-buffer pass of the current parameters (gfx_restir_set_params) generates, by the device function the pass
+ * runs: row-major, one ray per pixel, gfx_trace's layout.  With jittering on it reads rngBuffer and does not write it back. */
+int gfx_restir_primary_rays(gfx_ctx* ctx, void* stream, uint32_t width, uint32_t height, void* dRayOrgTmin, void* dRayDirTmax);
 
 #ifdef __cplusplus
 }

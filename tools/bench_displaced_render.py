@@ -1,0 +1,106 @@
+"""Rendering displaced instances against rendering their tessellation, for an MI355X.
+
+    python tools/bench_displaced_render.py [--size 1024] [--frames 20] [--width 1920] [--height 1080] [--max-len 5] [--step-timeout 300]
+
+The scene of tfdm_common.lit_mixed_scene (a plain teapot on a displaced ground quad, a displaced wall behind it, an emissive
+rectangle above, one size x size height map), G-buffer pass + baseline path tracer per frame:
+
+  displaced     the two quads as a bound instance set (gfx_scene_bind_displaced): the scene query in every trace
+  tessellated   the two quads tessellated into the BVH8 (two triangles per texel), rendered by the existing tracer with
+                "fuse_passes" 1, so both sides run the same wavefront form
+
+Per side: milliseconds per frame (HIP events around --frames frames after 3 warm-up frames), the per-kernel times of one more frame
+from the context's timers, and the device bytes of the geometry (displaced: the object and the instance table; tessellated: BVH8
+nodes and triangle records at 64 bytes each, plus the vertex and index pools).  Prints one JSON line.
+
+Every GPU step is a child process of its own under a time limit (--step-timeout seconds); the first step that fails or runs out of
+time ends the run, and nothing more is started on the GPU after it."""
+import json
+import os
+import subprocess
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+
+STEPS = ["displaced", "tessellated"]
+
+
+def _arg(argv, name, default):
+    return type(default)(argv[argv.index(name) + 1]) if name in argv else default
+
+
+def step(name, size, frames, w, h, max_len):
+    import torch
+    from gfxexp_amd import api
+    import tfdm_common as K
+    tess = name == "tessellated"
+    hs, (v, t, heights, gp), instances, slot, pos, target = K.lit_mixed_scene(size, tessellate=tess)
+    ctx = api.Context(0)
+    hs.upload(ctx)
+    accel = ctx.accel_build()
+    ctx.lights_build_static()
+    stats = ctx.accel_stats(accel)
+    out = {"bvh_triangles": stats["triangles"]}
+    if tess:
+        ctx.tunable_set("fuse_passes", 1)
+        # BVH8 items, and one copy of the tessellated quad in the vertex and index pools ((size + 1)^2 vertices, 2 size^2 triangles)
+        out["device_bytes"] = 64 * (stats["nodes"] + stats["triRecords"]) + 44 * (size + 1) ** 2 + 12 * 2 * size * size
+    else:
+        tf = api.Tfdm(ctx, v, t, heights, gp)
+        tset = api.TfdmSet(ctx)
+        for m, uid in instances:
+            tset.add(tf, m, uid)
+        tset.commit()
+        ctx.bind_displaced(tset, [slot] * len(instances))
+        out["device_bytes"] = tf.device_bytes() + api.TFDM_RECORD_BYTES * len(instances)
+    fr = K.PathTraceFrames(ctx, accel, w, h)
+    cam = K.look_at_camera(w, h, pos, target)
+    stream = torch.cuda.current_stream().cuda_stream
+    for k in range(3):
+        fr.frame(k, cam, max_len, stream)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for k in range(frames):
+        fr.frame(3 + k, cam, max_len, stream)
+    b.record()
+    b.synchronize()
+    out["ms_per_frame"] = round(a.elapsed_time(b) / frames, 4)
+    ctx.timing_enable(True)
+    fr.frame(3 + frames, cam, max_len, stream)
+    torch.cuda.synchronize()
+    out["kernel_ms"] = {k: round(ms, 4) for k, (ms, calls) in sorted(ctx.timing_collect().items())}
+    ctx.timing_enable(False)
+    out["mean_radiance"] = round(float(fr.beauty()[:, :3].mean()), 5)
+    if not tess:
+        ctx.bind_displaced(None)
+    return out
+
+
+def main(argv):
+    size, frames, max_len = _arg(argv, "--size", 1024), _arg(argv, "--frames", 20), _arg(argv, "--max-len", 5)
+    w, h = _arg(argv, "--width", 1920), _arg(argv, "--height", 1080)
+    if "--step" in argv:
+        print("STEP_RESULT " + json.dumps(step(argv[argv.index("--step") + 1], size, frames, w, h, max_len)))
+        return 0
+    limit = _arg(argv, "--step-timeout", 300)
+    result = {"metric": "displaced_render", "size": size, "frames": frames, "width": w, "height": h, "max_len": max_len}
+    for name in STEPS:
+        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name, "--size", str(size), "--frames", str(frames),
+               "--width", str(w), "--height", str(h), "--max-len", str(max_len)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("STEP_RESULT ")]
+        if r.returncode != 0 or not line:
+            result["failed_step"] = {"name": name, "exit_status": r.returncode, "stderr_tail": r.stderr[-2000:]}
+            print(json.dumps(result))
+            return 1
+        result[name] = json.loads(line[-1][len("STEP_RESULT "):])
+    result["tessellated_over_displaced_ms"] = round(result["tessellated"]["ms_per_frame"] / result["displaced"]["ms_per_frame"], 3)
+    result["tessellated_over_displaced_bytes"] = round(result["tessellated"]["device_bytes"] / result["displaced"]["device_bytes"], 1)
+    print(json.dumps(result))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))

@@ -119,3 +119,69 @@ def mixed_scene(map_size):
     ground = affine(np.diag([4.0, 4.0, 4.0]), (-2.0, -2.0, 0.0))
     wall = affine(rotation_x(70.0) @ np.diag([4.0, 2.5, 4.0]), (-2.0, 2.0, 0.0))
     return s, (v, t, procedural_map(map_size), gp), [(ground, 1), (wall, 2)], (0.6, -4.2, 2.2), (0.0, 0.3, 0.6)
+
+
+# ---------------------------------------------------------------- the mixed scene, lit and path traced (tools/tfdm_view.py --render, tools/bench_displaced_render.py)
+def lit_mixed_scene(map_size, tessellate=False):
+    """mixed_scene() with an emissive rectangle above it and a constant grey Lambert material for the two displaced quads.
+    tessellate=False: the quads' shading geometry is added in NO group (gfx_scene_bind_displaced wants it so) and its slot returned.
+    tessellate=True: the quads stand in the BVH8 as tessellated_quad() meshes, two triangles per texel, under the same transforms.
+    Returns (HostScene, (vertices, triangles, heights, params), instances, shading geometry slot or None, camera position, target)."""
+    s, (v, t, heights, gp), instances, pos, target = mixed_scene(map_size)
+    grey = api.GfxMaterial()
+    grey.bsdfType = 0                                       # GFX_BSDF_LAMBERT
+    grey.a = (C.c_float * 3)(0.7, 0.7, 0.7)
+    grey_slot = s.add_material(grey)
+    lamp = s.add_material_traditional((0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 0.0, emittance=(40.0, 38.0, 34.0))
+    lv = np.zeros(4, api.VERTEX_DTYPE)
+    lv["position"] = [(-1.5, -1.5, 4.5), (1.5, -1.5, 4.5), (1.5, 1.5, 4.5), (-1.5, 1.5, 4.5)]
+    lv["normal"] = (0, 0, -1)
+    lv["texCoord0Dir"] = (1, 0, 0)
+    s.add_instance(s.add_group([s.add_geom(lv, np.array([[0, 2, 1], [0, 3, 2]], np.uint32), lamp)]), affine(np.eye(3), (0, 0, 0)))
+    slot = None
+    if tessellate:
+        mv, mt = tessellated_quad(heights, gp.hScale)
+        group = s.add_group([s.add_geom(mv, mt, grey_slot)])
+        for m, _ in instances:
+            s.add_instance(group, m)
+    else:
+        slot = s.add_geom(v, t, grey_slot)
+    return s, (v, t, heights, gp), instances, slot, pos, target
+
+
+class PathTraceFrames:
+    """The per-pixel buffers of the G-buffer pass + baseline path tracer on the device (torch), and one frame of the two passes."""
+
+    def __init__(self, ctx, accel, width, height, seed=591842031321323413):
+        import torch
+        self.ctx, self.accel, self.w, self.h = ctx, accel, width, height
+        n = width * height
+        z = lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        self.t = {"rng": torch.from_numpy(api.seed_rng_states(n, seed).view(np.uint8)).cuda(), "beauty": z(16 * n), "albedo": z(16 * n), "normal": z(16 * n)}
+        for i in range(2):
+            self.t.update({"gb0_%d" % i: z(16 * n), "gb1_%d" % i: z(8 * n), "gb2_%d" % i: z(16 * n), "gb3_%d" % i: z(16 * n)})
+        s = api.GfxRestirStaticParams()
+        s.imageSizeX, s.imageSizeY = width, height
+        s.rngBuffer = self.t["rng"].data_ptr()
+        for i in range(2):
+            s.gbuffer0[i], s.gbuffer1[i] = self.t["gb0_%d" % i].data_ptr(), self.t["gb1_%d" % i].data_ptr()
+            s.gbuffer2[i], s.gbuffer3[i] = self.t["gb2_%d" % i].data_ptr(), self.t["gb3_%d" % i].data_ptr()
+        s.beautyAccumBuffer, s.albedoAccumBuffer, s.normalAccumBuffer = self.t["beauty"].data_ptr(), self.t["albedo"].data_ptr(), self.t["normal"].data_ptr()
+        s.numTilesX, s.numTilesY = (width + 7) // 8, (height + 7) // 8
+        self.s = s
+
+    def frame(self, index, cam, max_len=5, stream=0):
+        f = api.GfxRestirFrameParams()
+        C.memmove(C.byref(f.camera), C.byref(cam), C.sizeof(cam))
+        C.memmove(C.byref(f.prevCamera), C.byref(cam), C.sizeof(cam))
+        f.travHandle, f.numAccumFrames, f.frameIndex, f.bufferIndex = self.accel, index, index, index % 2
+        f.resetFlowBuffer, f.enableJittering, f.envLightPowerCoeff = int(index == 0), 1, 1.0
+        self.ctx.lights_build_instances(stream)
+        self.ctx.restir_set_params(self.s, f, 0, 0, stream)
+        self.ctx.pt_launch(api.PT_SETUP_GBUFFERS, self.w, self.h, max_len, 0, 0, stream)
+        self.ctx.pt_launch(api.PT_PATH_TRACE_BASELINE, self.w, self.h, max_len, 0, 0, stream)
+
+    def beauty(self):
+        import torch
+        torch.cuda.synchronize()
+        return self.t["beauty"].cpu().numpy().view(np.float32).reshape(-1, 4)

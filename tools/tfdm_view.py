@@ -11,7 +11,12 @@ prints the hit share and the traversal counters per ray.
 
 --scene: a plain teapot on a displaced ground quad with a second displaced quad as a tilted wall (tfdm_common.mixed_scene), through
 ONE gfx_trace_scene call.  Writes <out>_normal.png (world-space normals of the displaced hits; plain hits grey), <out>_depth.png
-and <out>_instance.png (plain geometry grey, every displaced instance a colour of its own, misses black)."""
+and <out>_instance.png (plain geometry grey, every displaced instance a colour of its own, misses black).
+
+    python tools/tfdm_view.py --scene --render [--frames 64] [--size 256] [--width 960] [--height-px 540] [--out tfdm_view]
+
+--render: the same scene under an emissive rectangle, path traced through the bound instance set (gfx_scene_bind_displaced: the
+G-buffer pass and the baseline path tracer), --frames accumulated frames, written tone-mapped as <out>_render.png."""
 import argparse
 import json
 import os
@@ -33,6 +38,34 @@ def _depth_image(dist, hit, n):
         d = dist[hit]
         depth[hit, :3] = (1.0 - 0.9 * (d - d.min()) / max(float(d.max() - d.min()), 1e-30))[:, None]
     return depth
+
+
+def scene_render(a):
+    hs, (v, t, heights, gp), instances, slot, pos, target = K.lit_mixed_scene(a.size)
+    ctx = api.Context(0)
+    hs.upload(ctx)
+    accel = ctx.accel_build()
+    ctx.lights_build_static()
+    tf = api.Tfdm(ctx, v, t, heights, gp)
+    tset = api.TfdmSet(ctx)
+    for m, uid in instances:
+        tset.add(tf, m, uid)
+    tset.commit()
+    ctx.bind_displaced(tset, [slot] * len(instances))
+    w, h = a.width, a.height_px
+    frames = K.PathTraceFrames(ctx, accel, w, h)
+    cam = K.look_at_camera(w, h, pos, target)
+    stream = torch.cuda.current_stream().cuda_stream
+    for k in range(a.frames):
+        frames.frame(k, cam, stream=stream)
+    beauty = frames.beauty()
+    ctx.bind_displaced(None)
+    api.save_image_sdr(a.out + "_render.png", beauty, w, h, api.sdr_config(brightness=1.0, tone_map=True, gamma=True))
+    g0 = frames.t["gb0_%d" % ((a.frames - 1) % 2)].cpu().numpy().view(np.uint32).reshape(-1, 4)[:, 0]
+    print(json.dumps({"scene": "teapot on displaced ground, displaced wall, emissive rectangle", "size": int(heights.shape[0]), "frames": a.frames,
+                      "displaced_pixel_share": round(float(((g0 != api.GFX_INVALID_SLOT) & (g0 >= api.GBUFFER_DISPLACED)).mean()), 4),
+                      "mean_radiance": round(float(beauty[:, :3].mean()), 5), "images": [a.out + "_render.png"]}))
+    return 0
 
 
 def scene_view(a):
@@ -95,7 +128,11 @@ def main():
     ap.add_argument("--height-px", type=int, default=540)
     ap.add_argument("--out", default="tfdm_view")
     ap.add_argument("--scene", action="store_true")
+    ap.add_argument("--render", action="store_true")
+    ap.add_argument("--frames", type=int, default=64)
     a = ap.parse_args()
+    if a.render:
+        return scene_render(a)
     if a.scene:
         return scene_view(a)
     heights = api.tfdm_load_height(a.height) if a.height else K.procedural_map(a.size)
