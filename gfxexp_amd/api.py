@@ -329,7 +329,7 @@ C_ABI_SYMBOLS = [
     "gfx_tunable_set", "gfx_stream_copy", "gfx_bc_expand",
     "gfx_tfdm_default_params", "gfx_tfdm_create", "gfx_tfdm_set_params", "gfx_tfdm_destroy", "gfx_tfdm_trace", "gfx_tfdm_read", "gfx_tfdm_size",
     "gfx_tfdm_set_create", "gfx_tfdm_set_add", "gfx_tfdm_set_transform", "gfx_tfdm_set_commit", "gfx_tfdm_set_read", "gfx_tfdm_set_destroy", "gfx_trace_scene",
-    "gfx_scene_bind_displaced", "gfx_restir_primary_rays",
+    "gfx_scene_bind_displaced", "gfx_restir_primary_rays", "gfx_scene_bind_displaced_passes", "gfx_restir_last_rays",
 ]
 HOST_ABI_SYMBOLS = [
     "gfxh_scene_create", "gfxh_scene_destroy", "gfxh_last_error", "gfxh_scene_add_material_traditional",
@@ -912,17 +912,31 @@ class Context:
         reads rngBuffer when jittering is on and leaves it as it is."""
         self._check(self.L.gfx_restir_primary_rays(self.h, C.c_void_p(stream), C.c_uint32(width), C.c_uint32(height), C.c_void_p(d_ray_org), C.c_void_p(d_ray_dir)))
 
-    def bind_displaced(self, tfdm_set, geom_slots=()):
+    def bind_displaced(self, tfdm_set, geom_slots=(), restir=False, pass_mask=None):
         """gfx_scene_bind_displaced: the G-buffer pass and the baseline path tracer render the displaced instances of `tfdm_set`
-        (None: unbind); geom_slots[k] is the ungrouped geometry instance k is shaded with.  Every other renderer pass is refused
-        while a set is bound."""
+        (None: unbind); geom_slots[k] is the ungrouped geometry instance k is shaded with.  restir=True binds through
+        gfx_scene_bind_displaced_passes with DISPLACED_RESTIR, so the ReSTIR passes run over the set too (their shadow rays become the
+        scene query); every pass the binding does not carry is refused while a set is bound.  pass_mask: the mask as given."""
         if tfdm_set is None:
             self._check(self.L.gfx_scene_bind_displaced(self.h, None, None, C.c_uint32(0)))
             self._displaced = None
             return
         slots = np.ascontiguousarray(geom_slots, np.uint32).reshape(-1)
-        self._check(self.L.gfx_scene_bind_displaced(self.h, tfdm_set.h, _p(slots), C.c_uint32(len(slots))))
+        if restir or pass_mask is not None:
+            mask = pass_mask if pass_mask is not None else DISPLACED_GBUFFER_PT | DISPLACED_RESTIR
+            self._check(self.L.gfx_scene_bind_displaced_passes(self.h, tfdm_set.h, _p(slots), C.c_uint32(len(slots)), C.c_uint32(mask)))
+        else:
+            self._check(self.L.gfx_scene_bind_displaced(self.h, tfdm_set.h, _p(slots), C.c_uint32(len(slots))))
         self._displaced = tfdm_set          # the binding does not own the set: keep it alive
+
+    def restir_last_rays(self, d_ray_org, d_ray_dir, d_occluded, capacity, stream=0):
+        """gfx_restir_last_rays: the ray queue (float4 pairs, gfx_trace's layout) and the occlusion words (uint32) of the most recent
+        ReSTIR ray pass that ran in its three-kernel form, copied into device buffers of `capacity` entries; returns the number of
+        queue entries that pass traced."""
+        n = C.c_uint32(0)
+        self._check(self.L.gfx_restir_last_rays(self.h, C.c_void_p(stream), C.c_void_p(d_ray_org), C.c_void_p(d_ray_dir), C.c_void_p(d_occluded),
+                                                C.c_uint32(capacity), C.byref(n)))
+        return n.value
 
     def nrc_inference_image(self, net, which):
         """(device pointer, bytes) of the packed inference image gfx_nrc_infer reads: 0 = MLP fragments, 1 = hash grid."""
@@ -1332,6 +1346,7 @@ class Tfdm:
 
 
 SCENE_PLAIN = 0x80000000
+DISPLACED_GBUFFER_PT, DISPLACED_RESTIR = 1, 2      # GFX_DISPLACED_*: the pass mask of gfx_scene_bind_displaced_passes
 GBUFFER_DISPLACED = 0x80000000       # GFX_GBUFFER_DISPLACED: gbuffer0.instSlot of a displaced pixel = GBUFFER_DISPLACED | set index
 SCENE_HIT_DTYPE = np.dtype([("dist", "<f4"), ("bcB", "<f4"), ("bcC", "<f4"), ("index", "<u4"), ("normal", "<f4", 3), ("where", "<u4")])
 TFDM_INSTANCE_DTYPE = np.dtype([("objToWorld", "<f4", 12), ("worldToObj", "<f4", 12), ("boxLo", "<f4", 3), ("userId", "<u4"), ("boxHi", "<f4", 3), ("pad0", "<u4"),

@@ -815,7 +815,7 @@ int gfx_tfdm_set_destroy(gfx_tfdm_set* set) {
     int prev = -1;
     const bool switched = hipGetDevice(&prev) == hipSuccess && prev != set->s.device && hipSetDevice(set->s.device) == hipSuccess;
     (void)hipDeviceSynchronize();
-    if (set->ctx && set->ctx->c.displaced.set == &set->s) displaced_bind(set->ctx->c, nullptr, nullptr, 0);
+    if (set->ctx && set->ctx->c.displaced.set == &set->s) displaced_bind(set->ctx->c, nullptr, nullptr, 0, 0);
     tfdm_set_release(set->s);
     if (switched) (void)hipSetDevice(prev);
     delete set;
@@ -833,7 +833,17 @@ int gfx_trace_scene(gfx_ctx* ctx, void* stream, uint64_t accel, gfx_tfdm_set* se
 
 int gfx_scene_bind_displaced(gfx_ctx* ctx, gfx_tfdm_set* set, const uint32_t* geomInstSlots, uint32_t n) {
     GFX_TRY(ctx)
-    displaced_bind(ctx->c, set ? &set->s : nullptr, geomInstSlots, n);
+    displaced_bind(ctx->c, set ? &set->s : nullptr, geomInstSlots, n, GFX_DISPLACED_GBUFFER_PT);
+    GFX_CATCH(ctx)
+}
+int gfx_scene_bind_displaced_passes(gfx_ctx* ctx, gfx_tfdm_set* set, const uint32_t* geomInstSlots, uint32_t n, uint32_t passMask) {
+    GFX_TRY(ctx)
+    displaced_bind(ctx->c, set ? &set->s : nullptr, geomInstSlots, n, passMask);
+    GFX_CATCH(ctx)
+}
+int gfx_restir_last_rays(gfx_ctx* ctx, void* stream, void* dRayOrgTmin, void* dRayDirTmax, void* dOccluded, uint32_t capacity, uint32_t* count) {
+    GFX_TRY(ctx)
+    restir_last_rays(ctx->c, static_cast<hipStream_t>(stream), dRayOrgTmin, dRayDirTmax, dOccluded, capacity, count);
     GFX_CATCH(ctx)
 }
 int gfx_restir_primary_rays(gfx_ctx* ctx, void* stream, uint32_t width, uint32_t height, void* dRayOrgTmin, void* dRayDirTmax) {

@@ -90,6 +90,7 @@ struct TfdmSet;
 // set's or its own) never shares one with a frame.
 struct DisplacedBinding {
     TfdmSet* set = nullptr;          // not owned
+    uint32_t passMask = 0;           // GFX_DISPLACED_*: the passes that render the set (gfx_scene_bind_displaced_passes)
     std::vector<uint32_t> geomSlots;
     DevBuf dGeomSlots;               // uint32[instances]
     DevBuf gbHits;                   // gfx_scene_hit per launch slot of the G-buffer pass (Context::gbRayHits stays its plain phase and hint store)
@@ -194,6 +195,8 @@ struct Context {
     DevBuf ptPending, ptExtOrg, ptExtDir, ptExtOwner, ptState;
     DevBuf rearchSlots;
     DisplacedBinding displaced;
+    // the queue of the last ReSTIR ray pass (gfx_restir_last_rays): state 0 none yet, 1 three-kernel form, 2 fused (no queue)
+    struct LastRays { int state = 0; const void* org = nullptr; const void* dir = nullptr; const void* out = nullptr; uint32_t fixedCount = 0; const uint32_t* countPtr = nullptr; } lastRays;
     DevBuf nrcState, neeTrainIdx;
     DevBuf nrcQueryCount;            // u32: inference batch size of the NRC frame (GFX_PT_NRC_COUNT_QUERIES)
     // build scratch

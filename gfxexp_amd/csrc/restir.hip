@@ -1199,7 +1199,23 @@ static void launch_pixels(Context& ctx, hipStream_t stream, const char* name, K 
     GFX_HIP(hipGetLastError());
 }
 
-static void trace_queue(Context& ctx, hipStream_t stream, const RestirArgs& a, int mode, uint32_t fixedCount, bool useCounter, void* out) {
+// The shadow rays of a ray pass.  fixedCount: one entry per launch slot; useCounter: the device count a.rayCount, of at most `capacity`
+// entries.  Under a binding that carries GFX_DISPLACED_RESTIR this is the scene any-hit query: k_trace writes `out` in place and the
+// instance phase goes over it (tfdm/tfdm_set.hip).  What it traced is remembered for gfx_restir_last_rays.
+static void trace_queue(Context& ctx, hipStream_t stream, const RestirArgs& a, int mode, uint32_t fixedCount, bool useCounter, void* out, uint32_t capacity = 0) {
+    Context::LastRays& last = ctx.lastRays;
+    last.state = 1; last.org = a.rayOrg; last.dir = a.rayDir; last.out = out;
+    last.fixedCount = fixedCount; last.countPtr = useCounter ? a.rayCount : nullptr;
+    if (ctx.displaced.set && (ctx.displaced.passMask & GFX_DISPLACED_RESTIR)) {
+        const DevAccel accel = ctx.accels[ctx.restir.f.travHandle - 1]->dev();
+        SceneTrace t;
+        t.accel = &accel; t.set = ctx.displaced.set; t.mode = mode;
+        t.rayOrgTmin = a.rayOrg; t.rayDirTmax = a.rayDir;
+        t.numRays = useCounter ? capacity : fixedCount; t.numRaysPtr = useCounter ? a.rayCount : nullptr;
+        t.out = out;
+        trace_scene_launch(ctx, stream, t);
+        return;
+    }
     TraceLaunch t;
     t.accel = ctx.accels[ctx.restir.f.travHandle - 1]->dev();
     t.rayOrgTmin = a.rayOrg; t.rayDirTmax = a.rayDir;
@@ -1273,19 +1289,46 @@ void restir_primary_rays(Context& ctx, hipStream_t stream, uint32_t width, uint3
     GFX_HIP(hipGetLastError());
 }
 
+void restir_last_rays(Context& ctx, hipStream_t stream, void* dRayOrgTmin, void* dRayDirTmax, void* dOccluded, uint32_t capacity, uint32_t* count) {
+    const Context::LastRays& last = ctx.lastRays;
+    if (!count) throw HipError("gfx_restir_last_rays: null count");
+    if (last.state == 0) throw HipError("gfx_restir_last_rays: no ray pass has run yet");
+    if (last.state == 2) throw HipError("gfx_restir_last_rays: the last ray pass ran fused (one kernel, no ray queue); \"fuse_passes\" 1 keeps the three-kernel form");
+    if ((reinterpret_cast<uintptr_t>(dRayOrgTmin) | reinterpret_cast<uintptr_t>(dRayDirTmax)) & 15u) throw HipError("gfx_restir_last_rays: the ray outputs must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(dOccluded) & 3u) throw HipError("gfx_restir_last_rays: the occlusion output must be 4-byte aligned");
+    if (last.org != ctx.rayOrg.p || last.dir != ctx.rayDir.p || last.out != ctx.rayOut.p)
+        throw HipError("gfx_restir_last_rays: the ray queue was reallocated for a larger launch since the last ray pass");
+    uint32_t n = last.fixedCount;
+    if (last.countPtr) {                         // a counted pass: the device count, once the pass is through
+        GFX_HIP(hipMemcpyAsync(&n, last.countPtr, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        GFX_HIP(hipStreamSynchronize(stream));
+    }
+    *count = n;
+    if (n > capacity) throw HipError("gfx_restir_last_rays: the pass traced " + std::to_string(n) + " queue entries, capacity is " + std::to_string(capacity));
+    if (n == 0) return;
+    if (!dRayOrgTmin || !dRayDirTmax || !dOccluded) throw HipError("gfx_restir_last_rays: null output");
+    GFX_HIP(hipMemcpyAsync(dRayOrgTmin, last.org, 16 * static_cast<size_t>(n), hipMemcpyDeviceToDevice, stream));
+    GFX_HIP(hipMemcpyAsync(dRayDirTmax, last.dir, 16 * static_cast<size_t>(n), hipMemcpyDeviceToDevice, stream));
+    GFX_HIP(hipMemcpyAsync(dOccluded, last.out, 4 * static_cast<size_t>(n), hipMemcpyDeviceToDevice, stream));
+}
+
 void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, uint32_t height, uint32_t rowBegin, uint32_t rowEnd, uint32_t gapBegin, uint32_t gapEnd) {
     const bool rearch = pass >= GFX_RESTIR_LIGHT_PRESAMPLING && pass <= GFX_RESTIR_SHADE_AND_RESAMPLE_SPATIOTEMPORAL;
     // a gap (gfx_restir_launch_rows_gap) is for the pass a band renderer splits around its exchange: the biased spatial pass, a plain per-pixel kernel
     if (gapEnd > gapBegin && pass != GFX_RESTIR_SPATIAL_BIASED) throw HipError("gfx_restir_launch_rows_gap: only GFX_RESTIR_SPATIAL_BIASED takes a gap");
     const bool displaced = ctx.displaced.set != nullptr;
     if (displaced) {
-        if (pass != GFX_RESTIR_SETUP_GBUFFERS)
+        if (pass != GFX_RESTIR_SETUP_GBUFFERS && !(ctx.displaced.passMask & GFX_DISPLACED_RESTIR))
             throw HipError("gfx_restir_launch: a displaced instance set is bound (gfx_scene_bind_displaced): only the G-buffer pass and the baseline path tracer "
                            "render displaced instances; ReSTIR pass " + std::to_string(pass) + " is refused");
         displaced_check(ctx, "gfx_restir_launch");
     }
     RestirArgs a = make_args(ctx, width, height, rowBegin, rowEnd, rearch, gapBegin, gapEnd);
     if (rowEnd == rowBegin || a.px.launchBlocks == 0) return;
+    // a counted queue holds at most this many entries: the launch's slots times the rays a pixel may emit, within what make_args reserved
+    const uint32_t raysPerPixel = rearch ? kRearchRayKinds : 1u + a.f.numSpatialNeighbors;
+    const uint32_t queueCapacity = static_cast<uint32_t>(std::min<size_t>(static_cast<size_t>(a.px.launchBlocks) * kBlock * raysPerPixel,
+                                                                         std::min(std::min(ctx.rayOrg.bytes, ctx.rayDir.bytes) / 16, ctx.rayOut.bytes / 4)));
     auto reset_queue = [&]() { GFX_HIP(hipMemsetAsync(a.rayCount, 0, sizeof(uint32_t), stream)); };
     // A launch of up to about half a full-HD frame (a row band of a multi-GPU frame) runs each of the three ray passes as ONE kernel
     // (k_*_fused above); a larger one keeps the persistent k_trace with its refill between two per-pixel kernels (band of 8 / 4 / 2 /
@@ -1297,7 +1340,8 @@ void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, u
     const bool fusableLaunch = 2u * launchWaves <= 9u * waveSlots;
     const int spillCap = static_cast<int>(local_spill_depth(ctx.accels[ctx.restir.f.travHandle - 1]->maxDepth));   // stack entries per thread behind the LDS part
     const size_t fusedSpillBytes = sizeof(uint2) * static_cast<size_t>(a.px.launchBlocks) * kBlock * spillCap;
-    const bool fused = !ctx.countersEnabled && fusedSpillBytes <= (size_t(1) << 30) && (ctx.tune.fusePasses == 2 || (ctx.tune.fusePasses == 0 && fusableLaunch));
+    // (a bound set: the three-kernel form whatever "fuse_passes" says -- the fused kernels trace through trace_local and cannot see it)
+    const bool fused = !displaced && !ctx.countersEnabled && fusedSpillBytes <= (size_t(1) << 30) && (ctx.tune.fusePasses == 2 || (ctx.tune.fusePasses == 0 && fusableLaunch));
     // Cost-ordered block start (block_order_begin / _end below) for the kernels whose launch is several rounds of blocks.
     const uint64_t orderKey = (static_cast<uint64_t>(rowBegin) << 44) ^ (static_cast<uint64_t>(rowEnd) << 24) ^ (static_cast<uint64_t>(width) << 4);
     const uint32_t orderMinBlocks = 8u * static_cast<uint32_t>(ctx.numCUs);     // up to about one round: they all start together
@@ -1399,6 +1443,7 @@ void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, u
                 uint32_t* cost = nullptr;
                 block_order_begin(0, grid, split, order, cost);
                 {
+                    ctx.lastRays.state = 2;
                     ScopedKernelTimer timer(ctx, stream, "initial_fused");
                     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, a, accel, ctx.spill.as<uint2>(), spillCap, cost);
                     GFX_HIP(hipGetLastError());
@@ -1437,12 +1482,13 @@ void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, u
         // slower at every band size: up to four rays per pixel are what k_trace's refill is good at; profiles/r05_experiments.txt 9)
         reset_queue();
         launch_pixels(ctx, stream, "spatial_unbiased_select", k_spatial<true>, a);
-        trace_queue(ctx, stream, a, GFX_TRACE_ANY, 0, true, ctx.rayOut.p);
+        trace_queue(ctx, stream, a, GFX_TRACE_ANY, 0, true, ctx.rayOut.p, queueCapacity);
         launch_pixels(ctx, stream, "spatial_unbiased_finish", k_spatial_mis_finish, a);
         break;
     case GFX_RESTIR_SPATIAL_BIASED_AND_SHADING:
     case GFX_RESTIR_SHADING:
         if (fused) {
+            ctx.lastRays.state = 2;
             ctx.spill.reserve(fusedSpillBytes);
             const bool both = pass == GFX_RESTIR_SPATIAL_BIASED_AND_SHADING;
             const uint32_t* order = nullptr;
@@ -1499,7 +1545,7 @@ void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, u
 #undef GFX_REARCH_CASE
         }
         launch_pixels(ctx, stream, "rearch_emit", emit, a);
-        trace_queue(ctx, stream, a, GFX_TRACE_ANY, 0, true, ctx.rayOut.p);
+        trace_queue(ctx, stream, a, GFX_TRACE_ANY, 0, true, ctx.rayOut.p, queueCapacity);
         launch_pixels(ctx, stream, "rearch_vis_finish", finish, a);
         break;
     }

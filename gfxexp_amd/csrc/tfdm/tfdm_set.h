@@ -51,12 +51,15 @@ void trace_scene_check_set(const TfdmSet& set, int device, const char* who);   /
 // geometry each instance is shaded with (Context::displaced)
 struct DisplacedArgs { const float4* hits; const tfdm::InstanceRecord* table; const uint32_t* geomSlots; };
 
-// gfx_scene_bind_displaced (set == nullptr: unbind) and the check every set-bound launch repeats: the set as gfx_trace_scene wants
-// it, and no bound geometry's material emitting (a material may have been set after the bind).
-void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint32_t n);
+// gfx_scene_bind_displaced_passes (set == nullptr: unbind; passMask: GFX_DISPLACED_*, the G-buffer pass and the path tracer are
+// always in it) and the check every set-bound launch repeats: the set as gfx_trace_scene wants it, and no bound geometry's material
+// emitting (a material may have been set after the bind).
+void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint32_t n, uint32_t passMask);
 void displaced_check(Context& ctx, const char* who);
 DisplacedArgs displaced_args(const Context& ctx, const void* hits);
 void restir_primary_rays(Context& ctx, hipStream_t stream, uint32_t width, uint32_t height, void* dRayOrgTmin, void* dRayDirTmax);   // restir.hip
+// gfx_restir_last_rays: the queue and the occlusion words of the last ray pass that ran in its three-kernel form (restir.hip)
+void restir_last_rays(Context& ctx, hipStream_t stream, void* dRayOrgTmin, void* dRayDirTmax, void* dOccluded, uint32_t capacity, uint32_t* count);
 
 // set == nullptr: no displaced instances; accel == nullptr: no plain geometry.  `fallbackPlain`: the plain-phase buffer of a
 // closest-hit query without a set (the context's).

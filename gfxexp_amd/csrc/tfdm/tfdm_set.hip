@@ -60,7 +60,9 @@ __global__ void __launch_bounds__(kSceneBlock) k_scene_instances(const InstanceR
     SceneStack stack;
     stack.col = s_stack + threadIdx.x;
     stack.sp = 0;
-    bool open = live && !occluded;               // the lane still looks for a hit
+    // the lane still looks for a hit; a shadow-ray slot without a ray (tmax = -1, zero direction: restir_common.hip.h emit_ray_at_slot)
+    // enters no instance and keeps the 0 k_trace wrote
+    bool open = live && !occluded && (!ANY_HIT || best.dist > tmin);
     for (uint32_t k = 0; k < numInstances; ++k) {
         const InstanceRecord& r = table[k];
         bool enter = false;
@@ -188,9 +190,11 @@ void trace_scene_launch(Context& ctx, hipStream_t stream, const SceneTrace& s) {
     GFX_HIP(hipGetLastError());
 }
 
-void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint32_t n) {
+void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint32_t n, uint32_t passMask) {
     DisplacedBinding& b = ctx.displaced;
-    if (!set) { b.set = nullptr; b.geomSlots.clear(); return; }
+    if (passMask & ~(GFX_DISPLACED_GBUFFER_PT | GFX_DISPLACED_RESTIR))
+        throw HipError("gfx_scene_bind_displaced_passes: unknown bit in the pass mask " + std::to_string(passMask));
+    if (!set) { b.set = nullptr; b.geomSlots.clear(); b.passMask = 0u; return; }
     if (set->device != ctx.device) throw HipError("gfx_scene_bind_displaced: the instance set belongs to another device");
     if (n != set->members.size())
         throw HipError("gfx_scene_bind_displaced: " + std::to_string(n) + " geometry slots for a set of " + std::to_string(set->members.size()) + " instances");
@@ -211,6 +215,7 @@ void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint3
     if (n) GFX_HIP(hipMemcpy(b.dGeomSlots.p, slots.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
     b.geomSlots.swap(slots);
     b.set = set;
+    b.passMask = passMask | GFX_DISPLACED_GBUFFER_PT;
 }
 
 void displaced_check(Context& ctx, const char* who) {

@@ -807,10 +807,12 @@ typedef struct gfx_scene_hit { float dist, bcB, bcC; uint32_t index; float norma
 int gfx_trace_scene(gfx_ctx* ctx, void* stream, uint64_t accel, gfx_tfdm_set* set, int mode, const void* dRayOrgTmin, const void* dRayDirTmax,
                     uint32_t numRays, void* dOut, void* dCounters);
 
-/* Displaced instances in the renderer.  While a set is bound, GFX_RESTIR_SETUP_GBUFFERS / GFX_PT_SETUP_GBUFFERS
- * and GFX_PT_PATH_TRACE_BASELINE trace plain and displaced geometry together (the scene query above, in their wavefront form whatever
- * "fuse_passes" says); every other renderer pass (ReSTIR, the rearchitected set, ReGIR, NRC) is refused with a message.  Without a
- * binding every pass does what it always did.
+/* Displaced instances in the renderer (DESIGN.md sections 16 and 17).  While a set is bound, GFX_RESTIR_SETUP_GBUFFERS /
+ * GFX_PT_SETUP_GBUFFERS and GFX_PT_PATH_TRACE_BASELINE trace plain and displaced geometry together (the scene query above, in their
+ * wavefront form whatever "fuse_passes" says).  A binding made with GFX_DISPLACED_RESTIR in its pass mask (gfx_scene_bind_displaced_passes)
+ * also runs the ReSTIR passes and the rearchitected set over it: their shadow rays become the scene's any-hit query, and they too run in
+ * their three-kernel form whatever "fuse_passes" says.  Every pass the binding does not carry (ReSTIR without that bit; ReGIR and NRC
+ * with any binding) is refused with a message.  Without a binding every pass does what it always did.
  *   geomInstSlots[k]  the geometry instance k of the set is shaded with: a gfx_geom_create of the vertex and triangle arrays the
  *                     instance's gfx_tfdm was created from, put in NO group (so it is not in the BVH8).  Material, texture
  *                     coordinates and texCoord0Dir come from it, transform and normal matrix from the instance's record.
@@ -825,13 +827,26 @@ int gfx_trace_scene(gfx_ctx* ctx, void* stream, uint64_t accel, gfx_tfdm_set* se
  *   gbuffer3   qShadingNormal = the same normal (no bump mapping on a displaced surface, as in the reference), qShadingTangent =
  *              texCoord0Dir of the base triangle in world space, orthogonal to it; qTexCoord, matSlot from the base triangle
  * BSDF textures are read at level 0 (this library's textures have no mip chain; the reference passes targetMipLevel).
- * G-buffers that hold displaced pixels are for the passes above and the output-chain copies; run the G-buffer pass again after
- * unbinding before any other pass reads them. */
+ * G-buffers that hold displaced pixels are for the passes above, the ReSTIR passes of a binding that carries GFX_DISPLACED_RESTIR
+ * (no ReSTIR kernel looks an instance, a geometry or a triangle up by a G-buffer id: DESIGN.md section 17) and the output-chain
+ * copies; run the G-buffer pass again after unbinding before any other pass reads them. */
 #define GFX_GBUFFER_DISPLACED 0x80000000u
 int gfx_scene_bind_displaced(gfx_ctx* ctx, gfx_tfdm_set* set, const uint32_t* geomInstSlots, uint32_t n);   /* set == NULL: unbind */
+/* The same binding with the passes it serves: gfx_scene_bind_displaced is this call with GFX_DISPLACED_GBUFFER_PT, which every
+ * binding carries.  Checks and refusals are those above; an unknown bit in passMask is refused.  Displaced emitters stay refused. */
+#define GFX_DISPLACED_GBUFFER_PT 1u   /* the G-buffer passes and the baseline path tracer */
+#define GFX_DISPLACED_RESTIR 2u       /* ... and the ReSTIR passes, the rearchitected set included */
+int gfx_scene_bind_displaced_passes(gfx_ctx* ctx, gfx_tfdm_set* set, const uint32_t* geomInstSlots, uint32_t n, uint32_t passMask);
 /* The primary rays the G-buffer pass of the current parameters (gfx_restir_set_params) generates, by the device function the pass
  * runs: row-major, one ray per pixel, gfx_trace's layout.  With jittering on it reads rngBuffer and does not write it back. */
 int gfx_restir_primary_rays(gfx_ctx* ctx, void* stream, uint32_t width, uint32_t height, void* dRayOrgTmin, void* dRayDirTmax);
+/* The ray queue (gfx_trace's layout) and the occlusion words (uint32, 1 = occluded) of the most recent ray pass gfx_restir_launch*
+ * ran in its three-kernel form, copied into buffers of `capacity` entries, with or without a binding; *count = the queue entries that
+ * pass traced: its launch slots, slots without a ray included (tmax = -1, word 0), for a pass with one entry per slot, the device
+ * count for a pass that compacts its rays (the unbiased spatial pass, the rearchitected set; this waits for `stream`).  Refused with
+ * a message: no ray pass yet, the last one ran fused (no queue exists), capacity < *count (which is still set), rays not 16-byte or
+ * words not 4-byte aligned.  `stream` is a hipStream_t passed as void*, as everywhere in this header. */
+int gfx_restir_last_rays(gfx_ctx* ctx, void* stream, void* dRayOrgTmin, void* dRayDirTmax, void* dOccluded, uint32_t capacity, uint32_t* count);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,110 @@
+"""ReSTIR DI over a bound set of displaced instances, for an MI355X.
+
+    python tools/bench_displaced_restir.py [--size 1024] [--frames 20] [--width 1920] [--height 1080] [--step-timeout 300]
+
+The scene of tfdm_common.lit_mixed_scene (tools/tfdm_view.py --scene under its emissive rectangle).  A frame is the G-buffer pass,
+INITIAL_AND_TEMPORAL_BIASED (INITIAL_RIS in frame 0), two SPATIAL_BIASED passes and SHADING.
+
+  displaced     the two quads as an instance set bound with GFX_DISPLACED_RESTIR: every shadow ray is the scene's any-hit query
+  tessellated   the two quads tessellated into the BVH8 (two triangles per texel), "fuse_passes" 1: the same three-kernel form
+
+displaced / tessellated: milliseconds per frame (HIP events around --frames frames after 3 warm-up frames), per-kernel times of one
+more frame from the context's timers, device bytes of the geometry (as tools/bench_displaced_render.py counts them).  Prints one JSON line.
+
+Every GPU step is a child process of its own under a time limit (--step-timeout seconds); the first step that fails or runs out of
+time ends the run, and nothing more is started on the GPU after it."""
+import json
+import os
+import subprocess
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+
+STEPS = ["displaced", "tessellated"]
+
+
+def _arg(argv, name, default):
+    return type(default)(argv[argv.index(name) + 1]) if name in argv else default
+
+
+def _setup(size, tess):
+    from gfxexp_amd import api
+    import tfdm_common as K
+    hs, (v, t, heights, gp), instances, slot, pos, target = K.lit_mixed_scene(size, tessellate=tess)
+    ctx = api.Context(0)
+    hs.upload(ctx)
+    accel = ctx.accel_build()
+    ctx.lights_build_static()
+    stats = ctx.accel_stats(accel)
+    out = {"bvh_triangles": stats["triangles"]}
+    keep = None
+    if tess:
+        ctx.tunable_set("fuse_passes", 1)
+        out["device_bytes"] = 64 * (stats["nodes"] + stats["triRecords"]) + 44 * (size + 1) ** 2 + 12 * 2 * size * size
+    else:
+        tf = api.Tfdm(ctx, v, t, heights, gp)
+        tset = api.TfdmSet(ctx)
+        for m, uid in instances:
+            tset.add(tf, m, uid)
+        tset.commit()
+        ctx.bind_displaced(tset, [slot] * len(instances), restir=True)
+        out["device_bytes"] = tf.device_bytes() + api.TFDM_RECORD_BYTES * len(instances)
+        keep = (tf, tset)
+    return ctx, accel, keep, pos, target, out
+
+
+def step_frames(name, size, frames, w, h):
+    import torch
+    import tfdm_common as K
+    ctx, accel, keep, pos, target, out = _setup(size, name == "tessellated")
+    fr = K.RestirFrames(ctx, accel, w, h)
+    cam = K.look_at_camera(w, h, pos, target)
+    stream = torch.cuda.current_stream().cuda_stream
+    for k in range(3):
+        fr.frame(k, cam, stream=stream)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for k in range(frames):
+        fr.frame(3 + k, cam, stream=stream)
+    b.record()
+    b.synchronize()
+    out["ms_per_frame"] = round(a.elapsed_time(b) / frames, 4)
+    ctx.timing_enable(True)
+    fr.frame(3 + frames, cam, stream=stream)
+    torch.cuda.synchronize()
+    out["kernel_ms"] = {k: round(ms, 4) for k, (ms, calls) in sorted(ctx.timing_collect().items())}
+    ctx.timing_enable(False)
+    out["mean_radiance"] = round(float(fr.beauty()[:, :3].mean()), 5)
+    ctx.bind_displaced(None)
+    return out
+
+
+def main(argv):
+    size, frames = _arg(argv, "--size", 1024), _arg(argv, "--frames", 20)
+    w, h = _arg(argv, "--width", 1920), _arg(argv, "--height", 1080)
+    if "--step" in argv:
+        name = argv[argv.index("--step") + 1]
+        print("STEP_RESULT " + json.dumps(step_frames(name, size, frames, w, h)))
+        return 0
+    limit = _arg(argv, "--step-timeout", 300)
+    result = {"metric": "displaced_restir", "size": size, "frames": frames, "width": w, "height": h}
+    for name in STEPS:
+        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name, "--size", str(size), "--frames", str(frames),
+               "--width", str(w), "--height", str(h)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("STEP_RESULT ")]
+        if r.returncode != 0 or not line:
+            result["failed_step"] = {"name": name, "exit_status": r.returncode, "stderr_tail": r.stderr[-2000:]}
+            print(json.dumps(result))
+            return 1
+        result[name] = json.loads(line[-1][len("STEP_RESULT "):])
+    result["tessellated_over_displaced_ms"] = round(result["tessellated"]["ms_per_frame"] / result["displaced"]["ms_per_frame"], 3)
+    result["tessellated_over_displaced_bytes"] = round(result["tessellated"]["device_bytes"] / result["displaced"]["device_bytes"], 1)
+    print(json.dumps(result))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))

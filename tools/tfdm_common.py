@@ -185,3 +185,48 @@ class PathTraceFrames:
         import torch
         torch.cuda.synchronize()
         return self.t["beauty"].cpu().numpy().view(np.float32).reshape(-1, 4)
+
+
+class RestirFrames(PathTraceFrames):
+    """... and the buffers of the ReSTIR DI passes (reservoirs, reservoir info, sample visibility, neighbour deltas) with one frame of
+    G-buffer, initial + temporal (biased), `spatial` biased spatial passes and shading, sequenced as restir_di_main.cpp does."""
+    NUM_NEIGHBORS = 5
+
+    def __init__(self, ctx, accel, width, height, seed=591842031321323413):
+        import torch
+        super().__init__(ctx, accel, width, height, seed)
+        n = width * height
+        z = lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        self.t["deltas"] = torch.from_numpy(api.spatial_neighbor_deltas().view(np.uint8).reshape(-1)).cuda()
+        for i in range(2):
+            self.t.update({"res_%d" % i: z(48 * n), "info_%d" % i: z(8 * n), "vis_%d" % i: z(4 * n)})
+            self.s.reservoirBuffer[i], self.s.reservoirInfoBuffer[i] = self.t["res_%d" % i].data_ptr(), self.t["info_%d" % i].data_ptr()
+            self.s.sampleVisibilityBuffer[i] = self.t["vis_%d" % i].data_ptr()
+        self.s.spatialNeighborDeltas = self.t["deltas"].data_ptr()
+        self.last_res, self.last_base = 1, 0
+
+    def frame(self, index, cam, spatial=2, stream=0, accumulate=True):
+        f = api.GfxRestirFrameParams()
+        C.memmove(C.byref(f.camera), C.byref(cam), C.sizeof(cam))
+        C.memmove(C.byref(f.prevCamera), C.byref(cam), C.sizeof(cam))
+        f.travHandle, f.numAccumFrames, f.frameIndex, f.bufferIndex = self.accel, index if accumulate else 0, index, index % 2
+        f.resetFlowBuffer, f.enableJittering, f.envLightPowerCoeff = int(index == 0), 1, 1.0
+        f.spatialNeighborRadius, f.radiusThresholdForSpatialVisReuse = 20.0, 10.0
+        f.log2NumCandidateSamples, f.numSpatialNeighbors, f.useLowDiscrepancyNeighbors = 5, self.NUM_NEIGHBORS, 1
+        f.reuseVisibility, f.reuseVisibilityForTemporal, f.enableTemporalReuse, f.enableSpatialReuse = 1, 1, 1, 1
+        ctx, w, h = self.ctx, self.w, self.h
+        ctx.lights_build_instances(stream)
+        cur = (self.last_res + 1) % 2
+
+        def launch(pass_id, cur_res, base):
+            ctx.restir_set_params(self.s, f, cur_res, base, stream)
+            ctx.restir_launch(pass_id, w, h, stream)
+
+        launch(api.PASS_SETUP_GBUFFERS, cur, self.last_base)
+        launch(api.PASS_INITIAL_RIS if index == 0 else api.PASS_INITIAL_TEMPORAL_BIASED, cur, self.last_base)
+        for i in range(spatial):
+            launch(api.PASS_SPATIAL_BIASED, cur, self.last_base + self.NUM_NEIGHBORS * i)
+            cur = (cur + 1) % 2
+        self.last_base += self.NUM_NEIGHBORS * spatial
+        launch(api.PASS_SHADING, cur, self.last_base)
+        self.last_res = cur

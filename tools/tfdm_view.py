@@ -16,7 +16,13 @@ and <out>_instance.png (plain geometry grey, every displaced instance a colour o
     python tools/tfdm_view.py --scene --render [--frames 64] [--size 256] [--width 960] [--height-px 540] [--out tfdm_view]
 
 --render: the same scene under an emissive rectangle, path traced through the bound instance set (gfx_scene_bind_displaced: the
-G-buffer pass and the baseline path tracer), --frames accumulated frames, written tone-mapped as <out>_render.png."""
+G-buffer pass and the baseline path tracer), --frames accumulated frames, written tone-mapped as <out>_render.png.
+
+    python tools/tfdm_view.py --scene --restir [--frames 64] [--size 256] [--width 960] [--height-px 540] [--out tfdm_view]
+
+--restir: the scene of --render by ReSTIR DI under a binding that carries GFX_DISPLACED_RESTIR (G-buffer, initial + temporal, two
+spatial passes, shading; the shadow rays are the scene's any-hit query), --frames accumulated frames, written tone-mapped as
+<out>_restir.png."""
 import argparse
 import json
 import os
@@ -51,20 +57,21 @@ def scene_render(a):
     for m, uid in instances:
         tset.add(tf, m, uid)
     tset.commit()
-    ctx.bind_displaced(tset, [slot] * len(instances))
+    ctx.bind_displaced(tset, [slot] * len(instances), restir=a.restir)
     w, h = a.width, a.height_px
-    frames = K.PathTraceFrames(ctx, accel, w, h)
+    frames = K.RestirFrames(ctx, accel, w, h) if a.restir else K.PathTraceFrames(ctx, accel, w, h)
     cam = K.look_at_camera(w, h, pos, target)
     stream = torch.cuda.current_stream().cuda_stream
     for k in range(a.frames):
         frames.frame(k, cam, stream=stream)
     beauty = frames.beauty()
     ctx.bind_displaced(None)
-    api.save_image_sdr(a.out + "_render.png", beauty, w, h, api.sdr_config(brightness=1.0, tone_map=True, gamma=True))
+    image = a.out + ("_restir.png" if a.restir else "_render.png")
+    api.save_image_sdr(image, beauty, w, h, api.sdr_config(brightness=1.0, tone_map=True, gamma=True))
     g0 = frames.t["gb0_%d" % ((a.frames - 1) % 2)].cpu().numpy().view(np.uint32).reshape(-1, 4)[:, 0]
     print(json.dumps({"scene": "teapot on displaced ground, displaced wall, emissive rectangle", "size": int(heights.shape[0]), "frames": a.frames,
                       "displaced_pixel_share": round(float(((g0 != api.GFX_INVALID_SLOT) & (g0 >= api.GBUFFER_DISPLACED)).mean()), 4),
-                      "mean_radiance": round(float(beauty[:, :3].mean()), 5), "images": [a.out + "_render.png"]}))
+                      "renderer": "restir_di" if a.restir else "path_tracer", "mean_radiance": round(float(beauty[:, :3].mean()), 5), "images": [image]}))
     return 0
 
 
@@ -129,9 +136,10 @@ def main():
     ap.add_argument("--out", default="tfdm_view")
     ap.add_argument("--scene", action="store_true")
     ap.add_argument("--render", action="store_true")
+    ap.add_argument("--restir", action="store_true")
     ap.add_argument("--frames", type=int, default=64)
     a = ap.parse_args()
-    if a.render:
+    if a.render or a.restir:
         return scene_render(a)
     if a.scene:
         return scene_view(a)
