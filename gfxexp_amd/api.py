@@ -313,13 +313,17 @@ GBUFFER2_DTYPE = np.dtype([("positionInWorld", "<f4", 3), ("qGeometricNormal", "
 GBUFFER3_DTYPE = np.dtype([("qShadingNormal", "<u4"), ("qShadingTangent", "<u4"), ("qTexCoord", "<u4"),
                            ("matSlot", "<u4")])
 
+LIGHTS_SAMPLE, LIGHTS_SAMPLE_SEARCH, LIGHTS_SAMPLE_SOLID_ANGLE = 0, 1, 2      # gfx_lights_sample_mode
+LIGHT_SAMPLE_DTYPE = np.dtype([("emittance", "<f4", 3), ("areaPDensity", "<f4"), ("position", "<f4", 3), ("atInfinity", "<u4"),
+                               ("normal", "<f4", 3), ("record", "<u4"), ("instSlot", "<u4"), ("tableUsed", "<u4"), ("pad", "<u4", 2)])
+
 # every symbol include/gfxexp.h and include/gfxexp_host.h declare
 C_ABI_SYMBOLS = [
     "gfx_ctx_create", "gfx_ctx_destroy", "gfx_last_error", "gfx_version", "gfx_material_set", "gfx_texture_set", "gfx_texture_sample", "gfx_texture_set_bc", "gfx_texture_read", "gfx_geom_create",
     "gfx_group_create", "gfx_instance_create", "gfx_instance_set_transform", "gfx_instance_set_transform_and_normal_matrix", "gfx_instance_set_dynamic",
     "gfx_accel_build",
     "gfx_accel_set_max_leaf", "gfx_accel_stats", "gfx_accel_tri_ids", "gfx_lights_build_static",
-    "gfx_lights_build_instances", "gfx_lights_read", "gfx_lights_table_info", "gfx_trace", "gfx_trace_counted", "gfx_restir_set_params", "gfx_restir_copy_to_linear", "gfx_visualize", "gfx_restir_launch",
+    "gfx_lights_build_instances", "gfx_lights_read", "gfx_lights_table_info", "gfx_lights_sample", "gfx_trace", "gfx_trace_counted", "gfx_restir_set_params", "gfx_restir_copy_to_linear", "gfx_visualize", "gfx_restir_launch",
     "gfx_restir_copy_depth_to_linear", "gfx_restir_copy_emissive_to_linear", "gfx_denoiser_default_settings", "gfx_denoiser_create", "gfx_denoiser_destroy", "gfx_denoise",
     "gfx_denoiser_history", "gfx_restir_copy_taa_flow_to_linear", "gfx_taa_create", "gfx_taa_destroy", "gfx_taa_set_history_length", "gfx_taa_apply", "gfx_taa_history",
     "gfx_restir_launch_rows", "gfx_restir_launch_rows_gap", "gfx_pt_launch", "gfx_regir_set_params",
@@ -860,6 +864,12 @@ class Context:
         self._check(self.L.gfx_lights_table_info(self.h, info))
         return {"usable": int(info[0]), "verified": int(info[1]), "records": int(info[2]), "cells": int(info[3]),
                 "matrices": int(info[4]), "interior_cells": int(info[5])}
+
+    def lights_sample(self, mode, d_u, n, d_out, shading_point=(0.0, 0.0, 0.0), stream=0):
+        """gfx_lights_sample: n light samples from d_u (float4 (ul, u0, u1, unused) each) into d_out (LIGHT_SAMPLE_DTYPE each) with the
+        sampler of the passes; mode LIGHTS_SAMPLE / LIGHTS_SAMPLE_SEARCH / LIGHTS_SAMPLE_SOLID_ANGLE (from shading_point)."""
+        self._check(self.L.gfx_lights_sample(self.h, C.c_void_p(stream), C.c_int(mode), _f3(shading_point), C.c_void_p(d_u), C.c_uint32(n),
+                                             C.c_void_p(d_out)))
 
     def trace(self, accel, mode, d_ray_org, d_ray_dir, num_rays, d_out, d_counters=0, stream=0, d_per_ray_items=0):
         if d_per_ray_items:

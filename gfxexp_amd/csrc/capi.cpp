@@ -336,6 +336,12 @@ int gfx_lights_read(gfx_ctx* ctx, uint32_t level, uint32_t index, float* weights
     GFX_CATCH(ctx)
 }
 
+int gfx_lights_sample(gfx_ctx* ctx, void* stream, int mode, const float shadingPoint[3], const void* dU, uint32_t n, void* dOut) {
+    GFX_TRY(ctx)
+    lights_sample(ctx->c, static_cast<hipStream_t>(stream), mode, shadingPoint, dU, n, dOut);
+    GFX_CATCH(ctx)
+}
+
 int gfx_lights_table_info(gfx_ctx* ctx, uint32_t info[8]) {
     GFX_TRY(ctx)
     Context& c = ctx->c;

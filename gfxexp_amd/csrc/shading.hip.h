@@ -672,7 +672,8 @@ GFX_DEV bool light_locate_3level(const DevScene& sc, const InstDist& instDist, f
     float instProb, uGeomInst;
     instSlot = discrete_sample_guided(instDist, *sc.lightInstIntegral, sc.numInsts, ul, instProb, &uGeomInst);
     lightProb *= instProb;
-    if (instProb == 0.0f) return false;
+    // zero, or 0 / 0 where no emitter of the scene has any weight (the reference continues with a NaN density there)
+    if (!(instProb > 0.0f)) return false;
     const DevInstance* inst = sc.insts + instSlot;
     // (distOffset, numGeomInsts, distIntegral, slotsOffset) in one 16-byte load
     const uint4 ih = *reinterpret_cast<const uint4*>(&inst->distOffset);
@@ -811,6 +812,9 @@ GFX_DEV void light_from_record(const DevScene& sc, const LightPick& pk, float4 r
         const f3 gn = unit(cross(pB - pA, pC - pA));
         const float lpCos = -dot(dir, gn);
         areaPDensity = (lpCos > 0 && is_finite(dirPDF)) ? lightProb * (dirPDF * lpCos / sq(dist)) : 0.0f;
+        // a triangle seen edge-on or from behind, or from a point in its own plane (no solid angle: the direction above is 0 / 0): no
+        // sample -- like the early outs of the selection, the caller's default-constructed one stays (the reference writes NaNs into it)
+        if (!(areaPDensity > 0.0f)) { areaPDensity = 0.0f; return; }
     }
     else {
         bcA = 0.5f * u0;

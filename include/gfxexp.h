@@ -217,6 +217,22 @@ int gfx_lights_read(gfx_ctx* ctx, uint32_t level, uint32_t index, float* weights
  * one load), 0, 0 }. */
 int gfx_lights_table_info(gfx_ctx* ctx, uint32_t info[8]);
 
+/* Inspection / test entry of the light sampler: one light sample per (ul, u0, u1, unused) of dU (float4[n]) with the device
+ * functions the passes call, no environment light.  GFX_LIGHTS_SAMPLE: sampleLight<false> as the kernels run it (the interval
+ * table when the build verified it, else the three searches); GFX_LIGHTS_SAMPLE_SEARCH: the three searches whatever the
+ * table's state; GFX_LIGHTS_SAMPLE_SOLID_ANGLE: sampleLight<true> from shadingPoint (may be NULL in the other modes).
+ * dOut = gfx_light_sample_record[n].  Both buffers 16-byte aligned; needs gfx_lights_build_static and
+ * gfx_lights_build_instances since the last change of the scene. */
+enum gfx_lights_sample_mode { GFX_LIGHTS_SAMPLE = 0, GFX_LIGHTS_SAMPLE_SEARCH = 1, GFX_LIGHTS_SAMPLE_SOLID_ANGLE = 2 };
+typedef struct gfx_light_sample_record {
+    float emittance[3]; float areaPDensity;
+    float position[3]; uint32_t atInfinity;
+    float normal[3]; uint32_t record;          /* emitter record index; 0xFFFFFFFF: the pick returned early, density 0 */
+    uint32_t instSlot; uint32_t tableUsed;     /* instSlot 0xFFFFFFFF with record */
+    uint32_t pad[2];
+} gfx_light_sample_record;
+int gfx_lights_sample(gfx_ctx* ctx, void* stream, int mode, const float shadingPoint[3], const void* dU, uint32_t n, void* dOut);
+
 /* ---------------------------------------------------------------- ray queries ---------------- */
 
 /* Replaces optixTrace (utils/optix_util.h:557-603) for wavefront ray queues and the scalar

@@ -304,6 +304,17 @@ class OracleScene:
         self.L.orc_sample_light(self.h, _p(sp), _p(u), C.c_uint32(len(u)), _p(ls), _p(pd))
         return ls, pd
 
+    def sample_light_ids(self, shading_point, u3, solid_angle=False):
+        """sample_light plus the pick: (light samples (n, 10), densities (n,), ids (n, 3) uint32 = instance slot, geometry-instance index
+        inside the instance, primitive index; 0xFFFFFFFF each where sampleLight returned early).  solid_angle: sampleLight<true>."""
+        u = np.ascontiguousarray(u3, dtype=np.float32).reshape(-1, 3)
+        sp = np.ascontiguousarray(shading_point, dtype=np.float32)
+        ls = np.zeros((len(u), 10), np.float32)
+        pd = np.zeros(len(u), np.float32)
+        ids = np.zeros((len(u), 3), np.uint32)
+        self.L.orc_sample_light_ids(self.h, _p(sp), C.c_int(1 if solid_angle else 0), _p(u), C.c_uint32(len(u)), _p(ls), _p(pd), _p(ids))
+        return ls, pd, ids
+
 
 def seed_rngs(count, seed):
     out = np.zeros(count, np.uint64)

@@ -549,7 +549,24 @@ void orc_sample_light(orc_scene* s, const float* shadingPoint3, const float* u3,
         areaPDensity[i] = pd;
     }
 }
-
+// The same with the pick reported: ids3 = (instance slot, geomInst index inside the instance, primitive index) per sample,
+// 0xFFFFFFFF each where sampleLight returned early.  solidAngle != 0: sampleLight<true> from the shading point.
+void orc_sample_light_ids(orc_scene* s, const float* shadingPoint3, int solidAngle, const float* u3, uint32_t n,
+                          float* lightSample10, float* areaPDensity, uint32_t* ids3) {
+    const V3 sp(shadingPoint3[0], shadingPoint3[1], shadingPoint3[2]);
+#pragma omp parallel for schedule(static) num_threads(s->numThreads)
+    for (int64_t i = 0; i < static_cast<int64_t>(n); ++i) {
+        LightSample ls; float pd = 0;
+        uint32_t* ids = ids3 + 3 * i;
+        ids[0] = ids[1] = ids[2] = 0xFFFFFFFFu;
+        sampleLight(s->scene, 0.0f, 0.0f, sp, u3[3 * i], false, u3[3 * i + 1], u3[3 * i + 2], &ls, &pd, solidAngle != 0, ids);
+        float* o = lightSample10 + 10 * i;
+        o[0] = ls.emittance.x; o[1] = ls.emittance.y; o[2] = ls.emittance.z;
+        o[3] = ls.position.x; o[4] = ls.position.y; o[5] = ls.position.z;
+        o[6] = ls.normal.x; o[7] = ls.normal.y; o[8] = ls.normal.z; o[9] = static_cast<float>(ls.atInfinity);
+        areaPDensity[i] = pd;
+    }
+}
 
 // Streaming weighted-reservoir selection (Reservoir::update, restir_di_shared.h:118-125) over K
 // independent streams of M candidates: weights[M*K] and us[M*K] are (M, K) row-major.

@@ -179,7 +179,8 @@ static inline SphericalTriangle sphericalTriangle(V3 pA, V3 pB, V3 pC, V3 refPoi
 static inline void sampleLight(
     const Scene& scene, float envLightRotation, float envLightPowerCoeff,
     V3 shadingPoint, float ul, bool sampleEnvLight, float u0, float u1,
-    LightSample* lightSample, float* areaPDensity, bool useSolidAngleSampling = false)
+    LightSample* lightSample, float* areaPDensity, bool useSolidAngleSampling = false,
+    uint32_t* pickedIds = nullptr /* out, optional: (instance slot, geomInst index inside the instance, primitive index) */)
 {
     bool hasTexEmittance = false;
     RGB texValue(0.0f);
@@ -209,7 +210,8 @@ static inline void sampleLight(
         const uint32_t instSlot = scene.lightInstDist.sample(ul, &instProb, &uGeomInst);
         lightProb *= instProb;
         const InstanceData& inst = scene.insts[instSlot];
-        if (instProb == 0.0f) { *areaPDensity = 0.0f; return; }
+        // zero, or 0 / 0 where no emitter of the scene has any weight (the reference continues with a NaN density there)
+        if (!(instProb > 0.0f)) { *areaPDensity = 0.0f; return; }
 
         float geomInstProb, uPrim;
         const uint32_t geomInstIndexInInst = inst.lightGeomInstDist.sample(uGeomInst, &geomInstProb, &uPrim);
@@ -221,6 +223,7 @@ static inline void sampleLight(
         float primProb;
         const uint32_t primIndex = geomInst.emitterPrimDist.sample(uPrim, &primProb);
         lightProb *= primProb;
+        if (pickedIds) { pickedIds[0] = instSlot; pickedIds[1] = geomInstIndexInInst; pickedIds[2] = primIndex; }
 
         const MaterialData& mat = scene.materials[geomInst.materialSlot];
         const Triangle& tri = geomInst.triangleBuffer[primIndex];
@@ -264,6 +267,9 @@ static inline void sampleLight(
             const float lpCos = -dot(dir, gn);
             if (lpCos > 0 && finitef(dirPDF)) *areaPDensity = lightProb * (dirPDF * lpCos / pow2(dist));
             else *areaPDensity = 0.0f;
+            // edge-on, from behind or from a point in the triangle's own plane (no solid angle: dir is 0 / 0): no sample, the
+            // caller's default-constructed one stays (the reference writes NaNs into it)
+            if (!(*areaPDensity > 0.0f)) { *areaPDensity = 0.0f; return; }
         }
         else {
             // A Low-Distortion Map Between Triangle and Square (:485-498)

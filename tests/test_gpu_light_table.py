@@ -6,14 +6,15 @@ import numpy as np
 import pytest
 
 from gfxexp_amd import api
-from tests import util
+from tests import light_scenes, util
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("scene", ["bunny", "small_street", "pathological"])
+@pytest.mark.parametrize("scene", ["bunny", "small_street", "pathological", "count_8193"])
 def test_table_is_usable_and_fully_verified(built_lib, scene):
-    hs = {"bunny": util.bunny_scene, "small_street": util.small_street, "pathological": util.pathological_light_scene}[scene]()
+    hs = {"bunny": util.bunny_scene, "small_street": util.small_street, "pathological": util.pathological_light_scene,
+          "count_8193": light_scenes.SCENES["count_8193"]}[scene]()      # more instances than one chunk of the instance-level scan
     ctx = api.Context(0)
     hs.upload(ctx)
     ctx.lights_build_static()
