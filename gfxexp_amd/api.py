@@ -1244,7 +1244,7 @@ class TemporalAA:
             pass
 
 
-TFDM_BOX, TFDM_TWO_TRIANGLE = 0, 1
+TFDM_BOX, TFDM_TWO_TRIANGLE, TFDM_BILINEAR = 0, 1, 4
 TFDM_READ_PYRAMID, TFDM_READ_AABBS, TFDM_READ_RECORDS, TFDM_READ_NODES, TFDM_READ_HEIGHTS = range(5)
 TFDM_HIT_DTYPE = np.dtype([("dist", "<f4"), ("bcB", "<f4"), ("bcC", "<f4"), ("primIndex", "<u4"), ("normal", "<f4", 3), ("frontFace", "<u4")])
 TFDM_NODE_DTYPE = np.dtype([("lo", "<f4", 3), ("first", "<u4"), ("hi", "<f4", 3), ("count", "<u4")])

@@ -5,9 +5,11 @@
 //   k_tfdm_minmax_first / k_tfdm_minmax_level   generateFirstMinMaxMipMap / generateMinMaxMipMap (tfdm_preprocess_kernels.cu:46-131),
 //                                               launched level after level as tfdm_main.cpp:2492-2545 does
 //   k_tfdm_prim_aabbs                           computeAABBs (:159-363)
-//   k_tfdm_trace<ANY_HIT>                       the custom-primitive GAS + intersection program (tfdm_intersection_kernels.h): one
+//   k_tfdm_trace<ANY_HIT, BILINEAR>             the custom-primitive GAS + intersection program (tfdm_intersection_kernels.h): one
 //                                               ray per lane through a binary tree over the per-triangle boxes, tfdm::intersect at
-//                                               the leaves
+//                                               the leaves.  BILINEAR: the instantiation for an object of GFX_TFDM_BILINEAR; the
+//                                               Newton loop is kept out of the other one, whose registers Box and TwoTriangle
+//                                               users pay for
 //
 // Launch shape of k_tfdm_trace (cdna_hip_programming guidelines 5-7).  A lane's work is a data-dependent descent whose length
 // differs by orders of magnitude between neighbouring rays, so the unit that retires together is chosen as small as the hardware
@@ -56,7 +58,7 @@ __global__ void __launch_bounds__(64) k_tfdm_prim_aabbs(const TriRecord* __restr
 
 using LdsStack = LdsColumnStack<kTraceBlock>;      // tfdm_lds_stack.hip.h
 
-template <bool ANY_HIT>
+template <bool ANY_HIT, bool BILINEAR>
 __global__ void __launch_bounds__(kTraceBlock) k_tfdm_trace(const Node* __restrict__ nodes, const TriRecord* __restrict__ records, const float* __restrict__ heights,
                                                             const F2* __restrict__ pyramid, Params p, const float4* __restrict__ rayOrgTmin,
                                                             const float4* __restrict__ rayDirTmax, uint32_t numRays, void* __restrict__ out,
@@ -74,7 +76,7 @@ __global__ void __launch_bounds__(kTraceBlock) k_tfdm_trace(const Node* __restri
         Map map;
         map.heights = heights; map.pyramid = pyramid;
         TraceHit best;
-        const bool hit = trace_ray<ANY_HIT>(nodes, records, map, p, v3(o.x, o.y, o.z), v3(d.x, d.y, d.z), o.w, d.w, stack, best, ts);
+        const bool hit = trace_ray_local<ANY_HIT, BILINEAR>(nodes, records, map, p, v3(o.x, o.y, o.z), v3(d.x, d.y, d.z), o.w, d.w, stack, best, ts);
         if (ANY_HIT) static_cast<uint32_t*>(out)[i] = hit ? 1u : 0u;
         else {
             float4* h = static_cast<float4*>(out) + 2u * i;
@@ -90,8 +92,8 @@ __global__ void __launch_bounds__(kTraceBlock) k_tfdm_trace(const Node* __restri
 
 void check_params(const gfx_tfdm_params& g, uint32_t size) {
     const int maxDepth = floor_log2(size);
-    if (g.localIntersection != kBox && g.localIntersection != kTwoTriangle)
-        throw HipError("gfx_tfdm: localIntersection must be GFX_TFDM_BOX or GFX_TFDM_TWO_TRIANGLE (Bilinear and BSpline are not built)");
+    if (g.localIntersection != kBox && g.localIntersection != kTwoTriangle && g.localIntersection != kBilinear)
+        throw HipError("gfx_tfdm: localIntersection must be GFX_TFDM_BOX, GFX_TFDM_TWO_TRIANGLE or GFX_TFDM_BILINEAR (the reference's BSpline is not built)");
     if (g.targetMipLevel > static_cast<uint32_t>(maxDepth)) throw HipError("gfx_tfdm: targetMipLevel lies beyond the pyramid (log2(size) is its last level)");
     const float fields[] = { g.hOffset, g.hScale, g.hBias, g.texScale[0], g.texScale[1], g.texRotation, g.texOffset[0], g.texOffset[1] };
     for (float f : fields) if (!std::isfinite(f)) throw HipError("gfx_tfdm: a parameter is not finite");
@@ -206,10 +208,13 @@ void tfdm_trace(TfdmObject& o, hipStream_t stream, int mode, const void* dRayOrg
     const float4* org = static_cast<const float4*>(dRayOrgTmin);
     const float4* dir = static_cast<const float4*>(dRayDirTmax);
     unsigned long long* cnt = static_cast<unsigned long long*>(dCounters);
-    if (mode == GFX_TRACE_ANY)
-        k_tfdm_trace<true><<<blocks, kTraceBlock, 0, stream>>>(o.nodes.as<Node>(), o.records.as<TriRecord>(), o.heights.as<float>(), o.pyramid.as<F2>(), o.params, org, dir, numRays, dOut, cnt);
-    else
-        k_tfdm_trace<false><<<blocks, kTraceBlock, 0, stream>>>(o.nodes.as<Node>(), o.records.as<TriRecord>(), o.heights.as<float>(), o.pyramid.as<F2>(), o.params, org, dir, numRays, dOut, cnt);
+    auto launch = [&](auto kernel) {
+        kernel<<<blocks, kTraceBlock, 0, stream>>>(o.nodes.as<Node>(), o.records.as<TriRecord>(), o.heights.as<float>(), o.pyramid.as<F2>(), o.params, org, dir, numRays, dOut, cnt);
+    };
+    const bool any = mode == GFX_TRACE_ANY;
+    // (named in this order so that the instantiations without the Newton loop keep their place at the front of the code object)
+    if (o.params.local != kBilinear) launch(any ? k_tfdm_trace<true, false> : k_tfdm_trace<false, false>);
+    else launch(any ? k_tfdm_trace<true, true> : k_tfdm_trace<false, true>);
     GFX_HIP(hipGetLastError());
 }
 

@@ -6,7 +6,8 @@
 // Restated from the reference in this project's own types:
 //     tfdm/affine_arithmetic.h:631-1279            AAFloatOn2D and its 3-vector forms             -> AA, AA3
 //     tfdm/tfdm_shared.h:736-897                    Texel, up / down / next, the triangle / square test, findRoots
-//     tfdm/gpu_kernels/tfdm_intersection_kernels.h  displacedSurface_generic (Box, TwoTriangle)      -> intersect()
+//     tfdm/gpu_kernels/tfdm_intersection_kernels.h  displacedSurface_generic (Box, TwoTriangle, Bilinear) -> intersect()
+//     common/basic_types.h:2602-2609               makeCoordinateSystem                             -> ray_frame()
 //     tfdm/gpu_kernels/tfdm_preprocess_kernels.cu   computeTexelMinMax, computeAABBs                 -> texel_min_max(), prim_aabb()
 // Where this differs from the reference, on purpose:
 //   * ray-independent terms (the inverted texture transform, the composed matrices, the transformed texture coordinates, the
@@ -20,6 +21,24 @@
 //   * a ray that starts inside a Box-mode texel box leaves through the face of its smallest far distance (the reference reports
 //     the face of the largest near distance there);
 //   * texel indices are int32 (int16 in the reference).
+// ... and in the Bilinear (Newton) local intersection, newton_bilinear() (kernels.h:362-528):
+//   * the distance of a hit is the ray's parameter (the reference returns the length |S - org|, the parameter only for a unit
+//     direction; an object-space direction under a scaled instance is not unit);
+//   * delta = S - (org + max(t0, tmin) dir), from the ray point at the texel box's entry and not from the origin: F is the same in
+//     exact arithmetic, in fp32 its cancellation scales with the texel and not with the ray's length (an absolute 1e-5 criterion
+//     against a delta of length 50 would never be met).  The hit's parameter is the entry parameter plus the projected rest.
+//     "Behind" stays what it is in the reference, a guess that projects behind the ray's ORIGIN (parameter < 0): the first
+//     guesses of a ray that enters the box late project before the box entry although the root lies after it;
+//   * a hit counts only with tmin < t < tmax, as in the other modes (the reference checks tMax alone);
+//   * bcB, bcC come from the final guess on every path (the reference reads them uninitialised when it converges at iteration 0);
+//   * a hit outside the base triangle is rejected by the test of the TwoTriangle branch;
+//   * frontFace = dot(dir, normal) <= 0 with both in object space (the reference dots a tangent-space direction with an
+//     object-space normal);
+//   * the normal is normalize(cross(dS/du, dS/dv)), negated for a record with `flipped` set, so that it lies on the side of +N
+//     wherever the height gradient vanishes, as in the other two modes (the reference's cross(dS/dv, dS/du) lies on the side of
+//     -N for a footprint of positive area);
+//   * a singular 2 x 2 system, or any NaN, ends in "no hit" after at most 10 iterations; nothing that is not finite is written
+//     to a hit.
 //
 // Plain C++17 under the project's math contract: no contraction unless written fmaf (none here), IEEE division and sqrt, from
 // libm only sqrtf / fabsf / floorf; min and max are written as selects so that signed zeros and NaNs fall the same way on both
@@ -43,7 +62,7 @@ constexpr int kStackDepth = 24;            // base-tree stack entries per ray (t
 constexpr uint32_t kMaxTriangles = 1u << 20;
 static_assert((1u << (kStackDepth - 4)) >= kMaxTriangles, "a balanced tree over kMaxTriangles leaves is 20 deep: trace_ray pushes at most one entry per level, and a push beyond kStackDepth would be dropped");
 constexpr float kMaxTexelCoord = 16777216.0f;   // |texture coordinate| x map size stays below 2^24: int32 texel indices, exact as floats
-enum Local : uint32_t { kBox = 0, kTwoTriangle = 1 };
+enum Local : uint32_t { kBox = 0, kTwoTriangle = 1, kBilinear = 4 };   // gfx_tfdm_local; 2 and 3 are refused at the boundary
 
 // ---------------------------------------------------------------- scalars
 GFX_TFDM_FN uint32_t f2b(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
@@ -336,8 +355,89 @@ GFX_TFDM_FN bool ray_triangle(V3 org, V3 dir, float distMin, float distMax, V3 p
     return (t < distMax) && (t > distMin) && (bcB >= 0.0f) && (bcC >= 0.0f) && (bcB + bcC <= 1.0f);
 }
 
+// makeCoordinateSystem (common/basic_types.h:2602-2609) of the normalised direction: d1, d2 span the plane across the ray
+struct RayFrame { V3 d1, d2; float dirSq; };
+GFX_TFDM_FN RayFrame ray_frame(V3 dir) {
+    RayFrame f;
+    f.dirSq = dot(dir, dir);
+    const V3 d = normalize(dir);
+    const float sign = d.z >= 0.0f ? 1.0f : -1.0f;
+    const float a = -1.0f / (sign + d.z);
+    const float b = d.x * d.y * a;
+    f.d1 = v3(1.0f + sign * d.x * d.x * a, sign * b, -sign * d.x);
+    f.d2 = v3(b, sign + d.y * d.y * a, -d.y);
+    return f;
+}
+
+// The Bilinear local intersection (kernels.h:402-511): Newton's iteration in texture space for the point of
+//     S(u, v) = P(u, v) + h(u, v) N(u, v) / |N(u, v)|,   h bilinear over the texel's four corner heights,
+// on the ray's line, F(u, v) = ((S - entry) . d1, (S - entry) . d2) = 0, from the texel's centre.  `entry` is the ray point
+// org + tEntry dir at the texel box's entry (the header's list of departures).  `res` is the number of texels per unit at the
+// texel's level, (cx, cy) its index, lo / hi its corners.  Everything is in named scalars: nothing here is indexed at run time.
+GFX_TFDM_FN bool newton_bilinear(const TriRecord& r, V2 tcA, V2 tcB, V2 tcC, V2 lo, V2 hi, float res, float cx, float cy, float hTL, float hTR, float hBL, float hBR,
+                                 V3 entry, float tEntry, V3 dir, const RayFrame& fr, float tmin, float tmax, float& tOut, float& bcBOut, float& bcCOut, V3& nOut) {
+    const V3 pu = v3(r.tcToP[0], r.tcToP[3], r.tcToP[6]), pv = v3(r.tcToP[1], r.tcToP[4], r.tcToP[7]);     // the Jacobians of P and N
+    const V3 nu = v3(r.tcToN[0], r.tcToN[3], r.tcToN[6]), nv = v3(r.tcToN[1], r.tcToN[4], r.tcToN[7]);
+    V2 g = v2(0.5f * lo.x + 0.5f * hi.x, 0.5f * lo.y + 0.5f * hi.y);
+    const float behindAt = -(tEntry * fr.dirSq);          // along < behindAt: the guess projects behind the ray's origin
+    float prevErr = inf();
+    int errStreak = 0, behindStreak = 0, outsideStreak = 0;
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+    for (int itr = 0; itr < 10; ++itr) {
+        const V3 gp = v3(g.x, g.y, 1.0f);
+        V3 n = mul3(r.tcToN, 3, gp);
+        const float recLen = 1.0f / sqrtf(dot(n, n));
+        n = recLen * n;
+        const float ut = res * g.x - cx, vt = res * g.y - cy;
+        const float h = (((1.0f - ut) * (1.0f - vt)) * hTL + (ut * (1.0f - vt)) * hTR) + (((1.0f - ut) * vt) * hBL + (ut * vt) * hBR);
+        const V3 S = mul3(r.tcToP, 3, gp) + h * n;
+        const V3 delta = S - entry;
+        const float fx = dot(delta, fr.d1), fy = dot(delta, fr.d2);
+        const float err = fx * fx + fy * fy;
+        const float along = dot(dir, delta);
+        errStreak = err > prevErr ? errStreak + 1 : 0;
+        behindStreak = along < behindAt ? behindStreak + 1 : 0;
+        if (errStreak >= 2 || behindStreak >= 2) return false;
+        prevErr = err;
+        const float hu = res * (((1.0f - vt) * hTR - (1.0f - vt) * hTL) + (vt * hBR - vt * hBL));
+        const float hv = res * (((1.0f - ut) * hBL - (1.0f - ut) * hTL) + (ut * hBR - ut * hTR));
+        // dS = dP + dh n + h d(N / |N|), d(N / |N|) = (dN - (dN . n) n) / |N|
+        const float k = h * recLen;
+        const V3 su = (pu + hu * n) + k * (nu - dot(nu, n) * n);
+        const V3 sv = (pv + hv * n) + k * (nv - dot(nv, n) * n);
+        if (err < 1e-5f * 1e-5f) {
+            const float bcB = cross2(tcC - g, tcA - g) * r.recArea, bcC = cross2(tcA - g, tcB - g) * r.recArea;
+            const float t = tEntry + along / fr.dirSq;
+            V3 c = cross(su, sv);
+            if (r.flipped != 0u) c = v3(-c.x, -c.y, -c.z);
+            const float len2 = dot(c, c);
+            if (!(bcB >= 0.0f && bcC >= 0.0f && bcB + bcC <= 1.0f) || !(along >= behindAt) || !(t > tmin && t < tmax) || !(len2 > 0.0f && len2 < inf())) return false;
+            tOut = t; bcBOut = bcB; bcCOut = bcC;
+            nOut = (1.0f / sqrtf(len2)) * c;
+            return true;
+        }
+        if (itr + 1 < 10) {
+            // dF / d(u, v) = ((d1 . su, d1 . sv), (d2 . su, d2 . sv)); a singular system gives a guess that is not a number,
+            // which no comparison below accepts
+            const float a = dot(fr.d1, su), b = dot(fr.d1, sv), c = dot(fr.d2, su), d = dot(fr.d2, sv);
+            const float recDet = 1.0f / (a * d - b * c);
+            g = v2(g.x - recDet * (d * fx - b * fy), g.y - recDet * (a * fy - c * fx));
+            const float bcB = cross2(tcC - g, tcA - g) * r.recArea, bcC = cross2(tcA - g, tcB - g) * r.recArea, bcA = 1.0f - (bcB + bcC);
+            const bool outside = g.x < lo.x || g.y < lo.y || g.x > hi.x || g.y > hi.y || bcA < 0.0f || bcB < 0.0f || bcC < 0.0f || bcA > 1.0f || bcB > 1.0f || bcC > 1.0f;
+            outsideStreak = outside ? outsideStreak + 1 : 0;
+            if (outsideStreak >= 3) return false;
+            if (outside) g = v2(fmin_(fmax_(g.x, lo.x), hi.x), fmin_(fmax_(g.y, lo.y), hi.y));
+        }
+    }
+    return false;
+}
+
 // The displaced surface of one base triangle against the ray (org, dir) of the base mesh's object space, inside (tmin, tmax).
-// Returns whether a hit closer than tmax was found; `hit` is written only then.
+// Returns whether a hit closer than tmax was found; `hit` is written only then.  kWithBilinear: the instantiation can run
+// p.local == kBilinear; without it that branch is not compiled (an object of that mode never reaches such an instantiation).
+template <bool kWithBilinear>
 GFX_TFDM_FN bool intersect(const TriRecord& r, const Map& map, const Params& p, V3 org, V3 dir, float tmin, float tmax, Hit& hit, Stats& stats) {
     const Footprint f = footprint(r);
     const V3 orgT = mul3(r.objToTang, 4, org) + v3(r.objToTang[3], r.objToTang[7], r.objToTang[11]);
@@ -347,6 +447,8 @@ GFX_TFDM_FN bool intersect(const TriRecord& r, const Map& map, const Params& p, 
     const int maxDepth = p.maxDepth;
     bool found = false;
     V3 hitNormal = v3(0.0f, 0.0f, 1.0f);
+    const bool bilinear = kWithBilinear && p.local == kBilinear;
+    const RayFrame fr = bilinear ? ray_frame(dir) : RayFrame();
     for (uint32_t rootIdx = 0; rootIdx < r.numRoots; ++rootIdx) {
         Texel cur = root_texel(r, rootIdx);
         Texel end = cur;
@@ -394,6 +496,18 @@ GFX_TFDM_FN bool intersect(const TriRecord& r, const Map& map, const Params& p, 
                 const float hTR = p.baseHeight + p.heightScale * corner_height(map.heights, maxDepth, cur.lod, cur.x + 1, cur.y);
                 const float hBL = p.baseHeight + p.heightScale * corner_height(map.heights, maxDepth, cur.lod, cur.x, cur.y + 1);
                 const float hBR = p.baseHeight + p.heightScale * corner_height(map.heights, maxDepth, cur.lod, cur.x + 1, cur.y + 1);
+                if (bilinear) {
+                    const float tEntry = fmax_(t0, tmin);
+                    V3 n;
+                    float t, bcB, bcC;
+                    if (newton_bilinear(r, tcA, tcB, tcC, v2(centre.x + scale * -0.5f, centre.y + scale * -0.5f), v2(centre.x + scale * 0.5f, centre.y + scale * 0.5f),
+                                        pow2i(maxDepth - cur.lod), static_cast<float>(cur.x), static_cast<float>(cur.y), hTL, hTR, hBL, hBR, org + tEntry * dir, tEntry, dir,
+                                        fr, tmin, tmax, t, bcB, bcC, n)) {
+                        tmax = t; found = true; hit.bcB = bcB; hit.bcC = bcC; hitNormal = n;
+                    }
+                    next(cur, signX, signY, initialLod);
+                    continue;
+                }
                 const V2 tcTL = v2(centre.x + scale * -0.5f, centre.y + scale * -0.5f), tcTR = v2(centre.x + scale * 0.5f, centre.y + scale * -0.5f);
                 const V2 tcBL = v2(centre.x + scale * -0.5f, centre.y + scale * 0.5f), tcBR = v2(centre.x + scale * 0.5f, centre.y + scale * 0.5f);
                 // normals are normalised in object space, then taken to tangent space with the corner's height
@@ -422,6 +536,11 @@ GFX_TFDM_FN bool intersect(const TriRecord& r, const Map& map, const Params& p, 
     // the tangent-space normal goes back with the transpose of the upper-left 3 x 3 (the inverse transpose of tangent -> object)
     const float* m = r.objToTang;
     hit.t = tmax;
+    if (bilinear) {                          // the normal of the smooth surface is in object space already
+        hit.normal = hitNormal;
+        hit.frontFace = dot(dir, hitNormal) <= 0.0f ? 1u : 0u;
+        return true;
+    }
     hit.normal = normalize(v3(m[0] * hitNormal.x + m[4] * hitNormal.y + m[8] * hitNormal.z, m[1] * hitNormal.x + m[5] * hitNormal.y + m[9] * hitNormal.z,
                               m[2] * hitNormal.x + m[6] * hitNormal.y + m[10] * hitNormal.z));
     hit.frontFace = dot(dirT, hitNormal) <= 0.0f ? 1u : 0u;
@@ -491,8 +610,8 @@ GFX_TFDM_FN Box node_box(const Node& n) { Box b; b.lo = v3(n.lo[0], n.lo[1], n.l
 // One ray, closest hit (kAny: any hit).  `Stack` has push(uint32 node, float entry), pop(uint32&, float&), empty(): the device
 // keeps it in an LDS column per lane, the host in an array.  A triangle is tested when the ray enters its box no later than the
 // current hit distance; equal distances go to the lower primitive index, so the result does not depend on the order of the walk.
-template <bool kAny, class Stack>
-GFX_TFDM_FN bool trace_ray(const Node* nodes, const TriRecord* records, const Map& map, const Params& p, V3 org, V3 dir, float tmin, float tmax,
+template <bool kAny, bool kWithBilinear, class Stack>
+GFX_TFDM_FN bool trace_ray_local(const Node* nodes, const TriRecord* records, const Map& map, const Params& p, V3 org, V3 dir, float tmin, float tmax,
                            Stack& stack, TraceHit& best, TraceStats& ts) {
     best.t = tmax; best.bcB = 0.0f; best.bcC = 0.0f; best.prim = kInvalid; best.normal = v3(0.0f, 0.0f, 0.0f); best.frontFace = 0u;
     const V3 inv = v3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
@@ -511,7 +630,7 @@ GFX_TFDM_FN bool trace_ray(const Node* nodes, const TriRecord* records, const Ma
             Stats s;
             s.aabbTests = 0u; s.leafTests = 0u;
             ++ts.primTests;
-            const bool got = intersect(records[prim], map, p, org, dir, tmin, bound, h, s);
+            const bool got = intersect<kWithBilinear>(records[prim], map, p, org, dir, tmin, bound, h, s);
             ts.aabbTests += s.aabbTests; ts.leafTests += s.leafTests;
             if (got) {
                 best.t = h.t; best.bcB = h.bcB; best.bcC = h.bcC; best.prim = prim; best.normal = h.normal; best.frontFace = h.frontFace;
@@ -541,6 +660,13 @@ GFX_TFDM_FN bool trace_ray(const Node* nodes, const TriRecord* records, const Ma
         }
     }
     return best.prim != kInvalid;
+}
+// ... with the instantiation chosen by the object's mode (the host; a kernel names its own)
+template <bool kAny, class Stack>
+GFX_TFDM_FN bool trace_ray(const Node* nodes, const TriRecord* records, const Map& map, const Params& p, V3 org, V3 dir, float tmin, float tmax,
+                           Stack& stack, TraceHit& best, TraceStats& ts) {
+    if (p.local == kBilinear) return trace_ray_local<kAny, true>(nodes, records, map, p, org, dir, tmin, tmax, stack, best, ts);
+    return trace_ray_local<kAny, false>(nodes, records, map, p, org, dir, tmin, tmax, stack, best, ts);
 }
 
 } // namespace tfdm

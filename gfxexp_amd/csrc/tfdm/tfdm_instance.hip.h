@@ -81,21 +81,27 @@ GFX_TFDM_FN bool world_box_hit(const InstanceRecord& r, V3 org, V3 inv, float tm
 
 // One step of the merge rule: instance `index` against the world ray, accepted only where closer than `best`.  kAny: returns at
 // the first hit and leaves `best` alone.  `stack` is emptied first (an any-hit return leaves entries behind).
-template <bool kAny, class Stack>
-GFX_TFDM_FN bool scene_instance(const InstanceRecord& r, uint32_t index, V3 org, V3 dir, float tmin, Stack& stack, SceneHit& best, TraceStats& ts) {
+template <bool kAny, bool kWithBilinear, class Stack>
+GFX_TFDM_FN bool scene_instance_local(const InstanceRecord& r, uint32_t index, V3 org, V3 dir, float tmin, Stack& stack, SceneHit& best, TraceStats& ts) {
     V3 objOrg, objDir;
     to_object_ray(r, org, dir, objOrg, objDir);
     Map map;
     map.heights = r.heights; map.pyramid = r.pyramid;
     TraceHit h;
     stack.sp = 0;
-    if (!trace_ray<kAny>(r.nodes, r.records, map, r.params, objOrg, objDir, tmin, best.dist, stack, h, ts)) return false;
+    if (!trace_ray_local<kAny, kWithBilinear>(r.nodes, r.records, map, r.params, objOrg, objDir, tmin, best.dist, stack, h, ts)) return false;
     if (!kAny) {
         best.dist = h.t; best.bcB = h.bcB; best.bcC = h.bcC; best.index = h.prim;
         best.normal = normal_to_world(r, h.normal);
         best.where = (index << 1) | h.frontFace;
     }
     return true;
+}
+// ... with the instantiation chosen by the instance's mode (the host; k_scene_instances names its own)
+template <bool kAny, class Stack>
+GFX_TFDM_FN bool scene_instance(const InstanceRecord& r, uint32_t index, V3 org, V3 dir, float tmin, Stack& stack, SceneHit& best, TraceStats& ts) {
+    if (r.params.local == kBilinear) return scene_instance_local<kAny, true>(r, index, org, dir, tmin, stack, best, ts);
+    return scene_instance_local<kAny, false>(r, index, org, dir, tmin, stack, best, ts);
 }
 
 // ---------------------------------------------------------------- host: a record from a transform and an object

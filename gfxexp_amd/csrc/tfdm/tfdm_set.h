@@ -17,6 +17,7 @@ struct TfdmSet {
     std::vector<Member> members;
     bool dirty = false;             // an add or a transform since the last commit
     std::vector<tfdm::InstanceRecord> host;   // the committed table
+    bool anyBilinear = false;       // ... has a member of GFX_TFDM_BILINEAR: the instance phase launches the instantiation that can run it
     DevBuf table;                   // InstanceRecord[members]
     DevBuf plain;                   // gfx_hit[numRays] of the plain phase of a closest-hit query; grows on demand
 };

@@ -3,14 +3,16 @@
 //
 //   plain phase      the scene BVH8 through the persistent k_trace (trace_launch), unchanged: its refill keeps the lanes of a
 //                    wave busy, which a one-wave block beside a TFDM descent could not
-//   instance phase   k_scene_instances<ANY_HIT>: one ray per lane, one wave per block (the launch shape of k_tfdm_trace and for
+//   instance phase   k_scene_instances<ANY_HIT, BILINEAR>: one ray per lane, one wave per block (the launch shape of k_tfdm_trace and for
 //                    its reason, tfdm.hip).  A lane starts from the plain result and walks the instance table in index order; the
 //                    record is read through the wave-uniform loop index, so the matrices, Params and pointers live in scalar
 //                    registers.  A lane whose ray passes the instance's padded world box takes the ray to object space and runs
 //                    tfdm::trace_ray with tmax = its best distance so far (tfdm_instance.hip.h: that is the merge rule); an
-//                    instance no lane of the wave enters is skipped by ballot.
+//                    instance no lane of the wave enters is skipped by ballot.  BILINEAR: the instantiation that can run a member of
+//                    GFX_TFDM_BILINEAR (its mode is read through the same wave-uniform record); launched only for a set that has
+//                    one, so a set of Box and TwoTriangle members runs the code it ran before that mode existed.
 //
-// Register count, scratch and occupancy: DESIGN.md section 15.
+// Register count, scratch and occupancy: DESIGN.md sections 15 and 18.
 #include <algorithm>
 #include <cstring>
 #include "tfdm_set.h"
@@ -25,7 +27,7 @@ namespace {
 constexpr int kSceneBlock = 64;
 using SceneStack = LdsColumnStack<kSceneBlock>;
 
-template <bool ANY_HIT>
+template <bool ANY_HIT, bool BILINEAR>
 __global__ void __launch_bounds__(kSceneBlock) k_scene_instances(const InstanceRecord* __restrict__ table, uint32_t numInstances, const float4* __restrict__ rayOrgTmin,
                                                                  const float4* __restrict__ rayDirTmax, uint32_t numRays, const uint32_t* __restrict__ numRaysPtr, const void* plain,
                                                                  void* out, unsigned long long* __restrict__ counters) {
@@ -70,7 +72,7 @@ __global__ void __launch_bounds__(kSceneBlock) k_scene_instances(const InstanceR
         if (__ballot(enter) == 0ull) continue;
         if (enter) {
             ++traversals;
-            if (scene_instance<ANY_HIT>(r, k, org, dir, tmin, stack, best, ts) && ANY_HIT) { occluded = true; open = false; }
+            if (scene_instance_local<ANY_HIT, BILINEAR>(r, k, org, dir, tmin, stack, best, ts) && ANY_HIT) { occluded = true; open = false; }
         }
     }
     if (live) {
@@ -133,6 +135,8 @@ void tfdm_set_commit(TfdmSet& s, hipStream_t stream) {
         GFX_HIP(hipStreamSynchronize(stream));       // `recs` is pageable memory
     }
     s.host.swap(recs);
+    s.anyBilinear = false;
+    for (const InstanceRecord& r : s.host) s.anyBilinear = s.anyBilinear || r.params.local == kBilinear;
     for (TfdmSet::Member& m : s.members) m.generation = m.obj->generation;
     s.dirty = false;
 }
@@ -185,8 +189,11 @@ void trace_scene_launch(Context& ctx, hipStream_t stream, const SceneTrace& s) {
     const InstanceRecord* table = numInstances ? s.set->table.as<InstanceRecord>() : nullptr;
     unsigned long long* cnt = static_cast<unsigned long long*>(s.statCounters);
     ScopedKernelTimer timer(ctx, stream, "k_scene_instances");
-    if (any) k_scene_instances<true><<<blocks, kSceneBlock, 0, stream>>>(table, numInstances, s.rayOrgTmin, s.rayDirTmax, s.numRays, s.numRaysPtr, plain, s.out, cnt);
-    else k_scene_instances<false><<<blocks, kSceneBlock, 0, stream>>>(table, numInstances, s.rayOrgTmin, s.rayDirTmax, s.numRays, s.numRaysPtr, plain, s.out, cnt);
+    auto launch = [&](auto kernel) {
+        kernel<<<blocks, kSceneBlock, 0, stream>>>(table, numInstances, s.rayOrgTmin, s.rayDirTmax, s.numRays, s.numRaysPtr, plain, s.out, cnt);
+    };
+    if (!(numInstances && s.set->anyBilinear)) launch(any ? k_scene_instances<true, false> : k_scene_instances<false, false>);
+    else launch(any ? k_scene_instances<true, true> : k_scene_instances<false, true>);
     GFX_HIP(hipGetLastError());
 }
 

@@ -744,7 +744,12 @@ int gfx_bc_expand(gfx_ctx* ctx, void* stream, uint32_t bcFormat, const void* dBl
  * one call, for any number of displaced instances under their own transforms; gfx_scene_bind_displaced at the end of this
  * section makes the G-buffer pass and the baseline path tracer render them. */
 typedef struct gfx_tfdm gfx_tfdm;                       /* opaque; owns heights, pyramid, records, AABBs, tree */
-enum gfx_tfdm_local { GFX_TFDM_BOX = 0, GFX_TFDM_TWO_TRIANGLE = 1 };   /* LocalIntersectionType, tfdm/tfdm_shared.h; Bilinear and BSpline are not built */
+/* How a texel of the target level is intersected (the modes of LocalIntersectionType, tfdm/tfdm_shared.h; the values are this
+ * library's own): its bounding box, two flat triangles over its four corners, or -- 4 -- the displaced surface itself,
+ * S(u, v) = P(u, v) + h(u, v) N(u, v) / |N(u, v)| with h bilinear over the texel's corner heights, by Newton's iteration (the
+ * reference's Bilinear).  Only this last mode has a normal that is continuous inside a texel.  2 and 3
+ * are refused (the reference's BSpline is not implemented there either). */
+enum gfx_tfdm_local { GFX_TFDM_BOX = 0, GFX_TFDM_TWO_TRIANGLE = 1, GFX_TFDM_BILINEAR = 4 };
 /* DisplacementParameters, tfdm/tfdm_shared.h, with the texture transform as the scale / rotation (degrees) / offset it is made
  * from (tfdm_main.cpp:2580-2588).  The height of a map value h is hOffset + preScale * hScale * (h - hBias) with preScale =
  * 1 / sqrt(texScale[0] * texScale[1]) (tfdm_intersection_kernels.h:54-59).  targetMipLevel: the map level whose texels are
@@ -754,7 +759,8 @@ enum gfx_tfdm_local { GFX_TFDM_BOX = 0, GFX_TFDM_TWO_TRIANGLE = 1 };   /* LocalI
 typedef struct gfx_tfdm_params { float hOffset, hScale, hBias; float texScale[2], texRotation, texOffset[2];
                                  uint32_t targetMipLevel, localIntersection; } gfx_tfdm_params;
 /* closest-hit record of gfx_tfdm_trace (DisplacedSurfaceAttributes + the hit kind, tfdm_intersection_kernels.h:537-561), 32 B.
- * bcB / bcC are barycentrics on the BASE triangle primIndex; normal is the unit normal of the displaced surface in object space.
+ * bcB / bcC are barycentrics on the BASE triangle primIndex; normal is the unit normal of the displaced surface in object space:
+ * of the box face or the flat triangle that was hit, or with GFX_TFDM_BILINEAR the normal of the smooth surface at the hit.
  * Miss: dist = the ray's tmax, primIndex = GFX_INVALID_SLOT, the rest zero. */
 typedef struct gfx_tfdm_hit { float dist, bcB, bcC; uint32_t primIndex; float normal[3]; uint32_t frontFace; } gfx_tfdm_hit;
 /* hOffset 0, hScale 1, hBias 0, unit texture transform, level 0, two triangles per texel. */
@@ -770,7 +776,8 @@ int gfx_tfdm_create(gfx_ctx* ctx, void* stream, const void* vertices, uint32_t s
                     const float* const* heightLevels, uint32_t numLevels, uint32_t size,
                     const gfx_tfdm_params* params, gfx_tfdm** out);
 /* New parameters for an object (the GUI edits of tfdm_main.cpp:2576-2600): records, AABBs and the tree are made again, the
- * pyramid is kept.  A refused call leaves the object as it was. */
+ * pyramid is kept.  localIntersection may change between all three modes (records, boxes and the tree do not depend on it).  A
+ * refused call leaves the object as it was. */
 int gfx_tfdm_set_params(gfx_ctx* ctx, void* stream, gfx_tfdm* obj, const gfx_tfdm_params* params);
 int gfx_tfdm_destroy(gfx_tfdm* obj);
 /* One ray per entry, optixTrace against the custom-primitive GAS of the reference (tfdm_intersection_kernels.h:16-35 for the
@@ -810,7 +817,8 @@ int gfx_tfdm_set_destroy(gfx_tfdm_set* set);
  *   miss                       dist = the ray's tmax, where = index = GFX_INVALID_SLOT, the rest zero
  *   plain hit                  where = GFX_SCENE_PLAIN, dist / bcB / bcC / index as gfx_hit (index = triIndex), normal zero
  *   displaced hit, instance k  where = k << 1 | frontFace, index = the base primIndex, bcB / bcC on the base triangle, normal =
- *                              the unit WORLD-space normal (the object-space normal through the instance's normal matrix) */
+ *                              the unit WORLD-space normal (the object-space normal through the instance's normal matrix; for
+ *                              an instance of GFX_TFDM_BILINEAR that of the smooth surface at the hit) */
 typedef struct gfx_scene_hit { float dist, bcB, bcC; uint32_t index; float normal[3]; uint32_t where; } gfx_scene_hit;
 #define GFX_SCENE_PLAIN 0x80000000u
 /* One optixTrace on an instance AS that mixes triangle GASes and custom-primitive GASes (tfdm/tfdm_main.cpp:2620-2640): world

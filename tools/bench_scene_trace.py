@@ -6,6 +6,8 @@
 it, one size x size height map):
 
   call    one gfx_trace_scene
+  call_bilinear   the same call with the wall an instance of a GFX_TFDM_BILINEAR object of the same mesh and map (the ground stays
+          TwoTriangle): the set then runs the Bilinear-capable instance phase
   chain   gfx_trace, then per instance a ray transform on the user's side (torch), gfx_tfdm_trace with tmax = the best distance so
           far, and a merge (torch): what a caller had to do before
 
@@ -29,7 +31,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
-STEPS = ["call", "chain"]
+STEPS = ["call", "call_bilinear", "chain"]
 
 
 def _arg(argv, name, default):
@@ -59,8 +61,12 @@ def step(name, size, iters, w, h):
     accel = ctx.accel_build()
     tf = api.Tfdm(ctx, v, t, heights, gp)
     tset = api.TfdmSet(ctx)
-    for m, uid in instances:
-        tset.add(tf, m, uid)
+    smooth = None
+    if name == "call_bilinear":
+        gp_smooth = api.tfdm_params(h_scale=gp.hScale, tex_scale=(gp.texScale[0], gp.texScale[1]), local_intersection=api.TFDM_BILINEAR)
+        smooth = api.Tfdm(ctx, v, t, heights, gp_smooth)
+    for k, (m, uid) in enumerate(instances):
+        tset.add(smooth if smooth is not None and k == len(instances) - 1 else tf, m, uid)
     tset.commit()
     n = w * h
     org, dirs = api.camera_rays(K.look_at_camera(w, h, pos, target), w, h)
@@ -72,7 +78,7 @@ def step(name, size, iters, w, h):
     def call():
         api.trace_scene(ctx, accel, tset, api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_scene.data_ptr(), stream=stream)
 
-    if name == "call":
+    if name in ("call", "call_bilinear"):
         secs = timed(call, iters)
         d_cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
         api.trace_scene(ctx, accel, tset, api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_scene.data_ptr(), d_cnt.data_ptr(), stream=stream)

@@ -1,12 +1,13 @@
 """gfx_tfdm_trace against the only other way to trace a height-mapped surface, the tessellated mesh in the scene BVH8.
 
-    python tools/bench_tfdm.py [--size 1024] [--iters 20] [--width 1920] [--height 1080] [--step-timeout 300]
+    python tools/bench_tfdm.py [--size 1024] [--iters 20] [--width 1920] [--height 1080] [--step-timeout 300] [--variants a,b,...]
 
 1920 x 1080 primary rays on a procedural size x size height map: on the unit quad and on the teapot (15 704 base triangles), for
-the Box and the TwoTriangle local intersection at map levels 0 and 2; and the same quad rays through gfx_trace on the quad
+the Box, the TwoTriangle and the Bilinear (Newton) local intersection at map levels 0 and 2; and the same quad rays through gfx_trace on the quad
 tessellated to 2 x size x size triangles.  Per variant: microseconds per launch (HIP events around --iters launches after a
 warm-up), Mrays/s, texel AABB tests / leaf tests / base triangles per ray from a counting launch of its own, and the device bytes
-of either representation.  Prints one JSON line.
+of either representation.  --variants: only these (two_triangle_l0, box_l2, bilinear_l0, ...), for a library that lacks one.  Prints
+one JSON line.
 
 Every GPU step is a child process of its own under a time limit (--step-timeout seconds); the first step that fails or runs out of
 time ends the run, and nothing more is started on the GPU after it."""
@@ -22,7 +23,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
 STEPS = ["tfdm_quad", "tfdm_teapot", "mesh_quad"]
-VARIANTS = [("two_triangle_l0", 1, 0), ("two_triangle_l2", 1, 2), ("box_l0", 0, 0), ("box_l2", 0, 2)]
+VARIANTS = [("two_triangle_l0", 1, 0), ("two_triangle_l2", 1, 2), ("box_l0", 0, 0), ("box_l2", 0, 2), ("bilinear_l0", 4, 0), ("bilinear_l2", 4, 2)]
 
 
 def _arg(argv, name, default):
@@ -42,7 +43,7 @@ def timed(fn, iters, warmup=3):
     return a.elapsed_time(b) * 1e-3 / iters
 
 
-def step(name, size, iters, w, h):
+def step(name, size, iters, w, h, only=None):
     import torch
     from gfxexp_amd import api
     import tfdm_common as K
@@ -80,6 +81,8 @@ def step(name, size, iters, w, h):
     out["variants"] = {}
     tf = None
     for vname, local, level in VARIANTS:
+        if only and vname not in only:
+            continue
         gp = api.tfdm_params(h_scale=h_scale, target_mip_level=level, local_intersection=local)
         if tf is None:
             tf = api.Tfdm(ctx, v, t, heights, gp)
@@ -103,14 +106,15 @@ def step(name, size, iters, w, h):
 def main(argv):
     size, iters = _arg(argv, "--size", 1024), _arg(argv, "--iters", 20)
     w, h = _arg(argv, "--width", 1920), _arg(argv, "--height", 1080)
+    only = _arg(argv, "--variants", "")
     if "--step" in argv:
-        print("STEP_RESULT " + json.dumps(step(argv[argv.index("--step") + 1], size, iters, w, h)))
+        print("STEP_RESULT " + json.dumps(step(argv[argv.index("--step") + 1], size, iters, w, h, only.split(",") if only else None)))
         return 0
     limit = _arg(argv, "--step-timeout", 300)
     result = {"metric": "tfdm_trace", "size": size, "iters": iters, "width": w, "height": h}
     for name in STEPS:
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name, "--size", str(size), "--iters", str(iters),
-               "--width", str(w), "--height", str(h)]
+               "--width", str(w), "--height", str(h)] + (["--variants", only] if only else [])
         r = subprocess.run(cmd, capture_output=True, text=True)
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("STEP_RESULT ")]
         if r.returncode != 0 or not line:

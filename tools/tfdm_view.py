@@ -1,10 +1,12 @@
 """Look at a displaced surface: pinhole primary rays through gfx_tfdm_trace, the normals and the depth written as images.
 
-    python tools/tfdm_view.py [--mesh quad|bunny|teapot] [--height FILE] [--size 256] [--scale 0.05] [--level 0] [--box]
+    python tools/tfdm_view.py [--mesh quad|bunny|teapot] [--height FILE] [--size 256] [--scale 0.05] [--level 0] [--box | --bilinear]
                               [--tex-scale 1] [--rotation 0] [--width 960] [--height-px 540] [--out tfdm_view]
 
 --height: a .png / .jpg / .tga / .dds height map (gfxh_tfdm_load_height); without it a procedural map of --size.  --scale is
-relative to the mesh's extent.  Writes <out>_normal.png (n * 0.5 + 0.5 in object space) and <out>_depth.png (near = bright), and
+relative to the mesh's extent.  --box / --bilinear: the local intersection, GFX_TFDM_BOX / GFX_TFDM_BILINEAR (the smooth surface by
+Newton's iteration) instead of two triangles per texel; with --scene, --render and --restir they set the mode of the scene's
+displaced object.  Writes <out>_normal.png (n * 0.5 + 0.5 in object space) and <out>_depth.png (near = bright), and
 prints the hit share and the traversal counters per ray.
 
     python tools/tfdm_view.py --scene [--size 256] [--width 960] [--height-px 540] [--out tfdm_view]
@@ -37,6 +39,10 @@ from gfxexp_amd import api  # noqa: E402
 import tfdm_common as K  # noqa: E402
 
 
+def _local(a):
+    return api.TFDM_BOX if a.box else api.TFDM_BILINEAR if a.bilinear else api.TFDM_TWO_TRIANGLE
+
+
 def _depth_image(dist, hit, n):
     depth = np.zeros((n, 4), np.float32)
     depth[:, 3] = 1
@@ -48,6 +54,7 @@ def _depth_image(dist, hit, n):
 
 def scene_render(a):
     hs, (v, t, heights, gp), instances, slot, pos, target = K.lit_mixed_scene(a.size)
+    gp.localIntersection = _local(a)
     ctx = api.Context(0)
     hs.upload(ctx)
     accel = ctx.accel_build()
@@ -77,6 +84,7 @@ def scene_render(a):
 
 def scene_view(a):
     plain, (v, t, heights, gp), instances, pos, target = K.mixed_scene(a.size)
+    gp.localIntersection = _local(a)
     ctx = api.Context(0)
     plain.upload(ctx)
     accel = ctx.accel_build()
@@ -128,7 +136,9 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--scale", type=float, default=0.05)
     ap.add_argument("--level", type=int, default=0)
-    ap.add_argument("--box", action="store_true")
+    mode = ap.add_mutually_exclusive_group()
+    mode.add_argument("--box", action="store_true")
+    mode.add_argument("--bilinear", action="store_true")
     ap.add_argument("--tex-scale", type=float, default=1.0)
     ap.add_argument("--rotation", type=float, default=0.0)
     ap.add_argument("--width", type=int, default=960)
@@ -146,7 +156,7 @@ def main():
     heights = api.tfdm_load_height(a.height) if a.height else K.procedural_map(a.size)
     v, t, pos, target, up = K.base_mesh(a.mesh)
     gp = api.tfdm_params(h_scale=a.scale * K.extent(v), tex_scale=(a.tex_scale, a.tex_scale), tex_rotation=a.rotation, target_mip_level=a.level,
-                         local_intersection=api.TFDM_BOX if a.box else api.TFDM_TWO_TRIANGLE)
+                         local_intersection=_local(a))
     ctx = api.Context(0)
     tf = api.Tfdm(ctx, v, t, heights, gp)
     w, h = a.width, a.height_px
