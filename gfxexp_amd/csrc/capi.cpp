@@ -342,6 +342,12 @@ int gfx_lights_sample(gfx_ctx* ctx, void* stream, int mode, const float shadingP
     GFX_CATCH(ctx)
 }
 
+int gfx_math_eval(gfx_ctx* ctx, void* stream, int fn, const void* dA, const void* dB, uint32_t n, void* dOut) {
+    GFX_TRY(ctx)
+    math_eval(ctx->c, static_cast<hipStream_t>(stream), fn, dA, dB, n, dOut);
+    GFX_CATCH(ctx)
+}
+
 int gfx_lights_table_info(gfx_ctx* ctx, uint32_t info[8]) {
     GFX_TRY(ctx)
     Context& c = ctx->c;

@@ -56,6 +56,35 @@ GFX_DEV float pow5(float x) { const float x2 = x * x; return x * (x2 * x2); }
 GFX_DEV float mixf(float v0, float v1, float t) { return (1 - t) * v0 + t * v1; }
 GFX_DEV bool is_finite(float x) { return (f2bits(x) & 0x7F800000u) != 0x7F800000u; }
 
+// ---------------------------------------------------------------- the contract's domains (version 1)
+// Stated here and in oracle/orc_math.h; tests/test_math_contract_cpu.py holds the oracle copy to the bounds against float64,
+// tests/test_gpu_math_contract.py holds the device copy to the oracle bit for bit (lists: tests/math_cases.py; figures: DESIGN.md 4).
+//   gm_sincos / gm_sin / gm_cos   |x| <= 1e6: absolute error <= 1.25e-7.  |x| <= 2 pi: sin <= 1.5 ulp, cos <= 6 ulp (the float next to
+//                                 3 pi/2).  |x| <= 1e4: <= 622 ulp, reached only on the floats next to a multiple of pi/2.  Beyond 1e6 the
+//                                 error grows (9.3e-5 at 2.8e6), unspecified; defined for every input (f2i_sat), NaN for +-inf and NaN.
+//                                 sincos(+-0) = (+0, 1).
+//   gm_tan                        |x| <= 1.5: <= 3 ulp; s / c of gm_sincos elsewhere.
+//   gm_exp                        kExpMin <= x <= kExpMax, kExpMin = -87.68312 (0xC2AF5DC2), kExpMax = 88.37626 (0x42B0C0A5): the x
+//                                 whose scale factor 2^n, n = floor(x log2(e) + 1/2), is 2^-126 .. 2^127.  <= 1.25 ulp where the result
+//                                 is normal (x >= kExpNormalMin = -87.33654, 0xC2AEAC4F), within one subnormal spacing below.  One float
+//                                 outside the result is 0 / +inf; further out it is garbage of either sign (gm_exp(-100) = -4.3e33),
+//                                 NaN at +-inf and NaN.  NOT total: callers guard (the denoiser with !(a >= -80)).  exp(+-0) = 1.
+//   gm_acos                       -1 <= x <= 1: <= 1.5 ulp; acos(1) = +0, acos(-1) = kPi.  NaN from the first float outside: callers
+//                                 clamp (to_polar_yup does).
+//   gm_atan                       every finite x and +-inf: <= 3 ulp; atan(+-inf) = +-kHalfPi, atan(+-0) = +0.
+//   gm_atan2                      every finite pair: <= 3.25 ulp, a zero counting as +0.  Special values (part of the contract --
+//                                 to_polar_yup at the phi seam rests on them -- and NOT those of IEEE atan2 where marked *):
+//                                   (+-0, +-0)            +0        * IEEE: (+-0, -0) = +-pi, (-0, +0) = -0
+//                                   (+-0, x > 0)          +0        * IEEE: -0 for y = -0
+//                                   (+-0, x < 0)          +pi       * IEEE: -pi for y = -0
+//                                   (y != 0, +-0)         +-pi/2 by the sign of y; (NaN, +-0) = +pi/2   * IEEE: NaN
+//                                   (+-inf, finite)       +-pi/2
+//                                   (finite y, +inf)      +-0 by y < 0;   (finite y, -inf)   +-pi by y < 0
+//                                   (+-inf, +-inf)        NaN       * IEEE: +-pi/4, +-3 pi/4
+//                                   NaN in x, or NaN in y with x != 0:  NaN
+//                                 A quotient |y| / |x| that underflows gives +-0 or +-pi, one that overflows +-pi/2.
+//   f2i_sat / f2u_sat             total: NaN -> 0, saturating at the ends of the integer type, truncation inside.
+
 // Saturating conversions: defined for every input so host and device agree.
 GFX_DEV uint32_t f2u_sat(float x) {
     if (!(x > 0.0f)) return 0u;
@@ -91,7 +120,7 @@ GFX_DEV float gm_sin(float x) { float s, c; gm_sincos(x, s, c); return s; }
 GFX_DEV float gm_cos(float x) { float s, c; gm_sincos(x, s, c); return c; }
 GFX_DEV float gm_tan(float x) { float s, c; gm_sincos(x, s, c); return s / c; }
 
-// exp(x), |x| < 80: Cody-Waite ln2 split + degree-6 polynomial + exponent insertion
+// exp(x), kExpMin <= x <= kExpMax (above): Cody-Waite ln2 split + degree-6 polynomial + exponent insertion
 GFX_DEV float gm_exp(float x) {
     const float n = floorf(x * 1.44269504088896341f + 0.5f);
     float r = fmaf(n, -0.693359375f, x);

@@ -233,6 +233,26 @@ typedef struct gfx_light_sample_record {
 } gfx_light_sample_record;
 int gfx_lights_sample(gfx_ctx* ctx, void* stream, int mode, const float shadingPoint[3], const void* dU, uint32_t n, void* dOut);
 
+/* Inspection / test entry of the deterministic math contract (csrc/gm_math.hip.h, contract version 1) and of the 16-bit
+ * quantisers on top of it (csrc/shading.hip.h): function `fn` on n arguments with the device functions the passes call.
+ * dA, dB = device float4[n] (dB may be NULL unless fn reads it); dOut = device uint32_t[4][n]: result word k of element i at
+ * dOut[k * n + i], floats as their bits, unused words 0.  All buffers 16-byte aligned.
+ *   GFX_MATH_SINCOS             A.x              -> gm_sincos s, c; gm_tan; gm_sin
+ *   GFX_MATH_EXP / ACOS / ATAN  A.x              -> gm_exp / gm_acos / gm_atan
+ *   GFX_MATH_ATAN2              y = A.x, x = A.y -> gm_atan2
+ *   GFX_MATH_SAT                A.x              -> f2i_sat, f2u_sat, q16
+ *   GFX_MATH_TO_POLAR           A.xyz            -> to_polar_yup phi, theta; encode_dir
+ *   GFX_MATH_DECODE_DIR         bits of A.x      -> decode_dir x, y, z
+ *   GFX_MATH_ENCODE_UV          u = A.x, v = A.y -> encode_uv
+ *   GFX_MATH_DECODE_UV          bits of A.x      -> decode_uv u, v
+ *   GFX_MATH_ENCODE_BC          A.x              -> encode_bc
+ *   GFX_MATH_DECODE_BC          low 16 bits of A.x -> decode_bc
+ *   GFX_MATH_OFFSET_RAY_ORIGIN  p = A.xyz, n = B.xyz -> offset_ray_origin x, y, z */
+enum gfx_math_fn { GFX_MATH_SINCOS = 0, GFX_MATH_EXP = 1, GFX_MATH_ACOS = 2, GFX_MATH_ATAN = 3, GFX_MATH_ATAN2 = 4, GFX_MATH_SAT = 5,
+                   GFX_MATH_TO_POLAR = 6, GFX_MATH_DECODE_DIR = 7, GFX_MATH_ENCODE_UV = 8, GFX_MATH_DECODE_UV = 9, GFX_MATH_ENCODE_BC = 10,
+                   GFX_MATH_DECODE_BC = 11, GFX_MATH_OFFSET_RAY_ORIGIN = 12 };
+int gfx_math_eval(gfx_ctx* ctx, void* stream, int fn, const void* dA, const void* dB, uint32_t n, void* dOut);
+
 /* ---------------------------------------------------------------- ray queries ---------------- */
 
 /* Replaces optixTrace (utils/optix_util.h:557-603) for wavefront ray queues and the scalar

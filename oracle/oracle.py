@@ -365,6 +365,74 @@ def math_atan2(y, x):
     return r
 
 
+def _unary(name, x):
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.zeros_like(x)
+    getattr(lib(), name)(_p(x), _p(y), C.c_uint32(x.size))
+    return y
+
+
+def math_tan(x):
+    return _unary("orc_math_tan", x)
+
+
+def math_sin(x):
+    """gm_sin, the wrapper of gm_sincos that returns the sine alone."""
+    return _unary("orc_math_sin", x)
+
+
+def math_exp(x):
+    return _unary("orc_math_exp", x)
+
+
+def math_atan(x):
+    return _unary("orc_math_atan", x)
+
+
+def math_sat(x):
+    """(f2i, f2u, q16) of x: the saturating conversions and the 16-bit unorm quantiser."""
+    x = np.ascontiguousarray(x, np.float32)
+    i32, u32, q = np.zeros(x.size, np.int32), np.zeros(x.size, np.uint32), np.zeros(x.size, np.uint32)
+    lib().orc_math_sat(_p(x), _p(i32), _p(u32), _p(q), C.c_uint32(x.size))
+    return i32, u32, q
+
+
+def to_polar(v):
+    """(phi, theta) of toPolarYUp."""
+    v = np.ascontiguousarray(v, np.float32).reshape(-1, 3)
+    phi, theta = np.zeros(len(v), np.float32), np.zeros(len(v), np.float32)
+    lib().orc_to_polar(_p(v), _p(phi), _p(theta), C.c_uint32(len(v)))
+    return phi, theta
+
+
+def encode_uv(uv):
+    uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    q = np.zeros(len(uv), np.uint32)
+    lib().orc_encode_uv(_p(uv), _p(q), C.c_uint32(len(uv)))
+    return q
+
+
+def decode_uv(q):
+    q = np.ascontiguousarray(q, np.uint32)
+    uv = np.zeros((len(q), 2), np.float32)
+    lib().orc_decode_uv(_p(q), _p(uv), C.c_uint32(len(q)))
+    return uv
+
+
+def encode_bc(x):
+    x = np.ascontiguousarray(x, np.float32)
+    q = np.zeros(x.size, np.uint32)
+    lib().orc_encode_bc(_p(x), _p(q), C.c_uint32(x.size))
+    return q
+
+
+def decode_bc(q):
+    q = np.ascontiguousarray(q, np.uint32)
+    x = np.zeros(q.size, np.float32)
+    lib().orc_decode_bc(_p(q), _p(x), C.c_uint32(q.size))
+    return x
+
+
 def encode_normal(v):
     v = np.ascontiguousarray(v, np.float32).reshape(-1, 3)
     q = np.zeros(len(v), np.uint32)

@@ -494,6 +494,23 @@ void orc_pcg32_uints(uint64_t* state, uint32_t* out, uint32_t n) {
 void orc_math_sincos(const float* x, float* s, float* c, uint32_t n) { for (uint32_t i = 0; i < n; ++i) gm_sincos(x[i], &s[i], &c[i]); }
 void orc_math_acos(const float* x, float* y, uint32_t n) { for (uint32_t i = 0; i < n; ++i) y[i] = gm_acos(x[i]); }
 void orc_math_atan2(const float* y, const float* x, float* r, uint32_t n) { for (uint32_t i = 0; i < n; ++i) r[i] = gm_atan2(y[i], x[i]); }
+void orc_math_tan(const float* x, float* y, uint32_t n) { for (uint32_t i = 0; i < n; ++i) y[i] = gm_tan(x[i]); }
+void orc_math_sin(const float* x, float* y, uint32_t n) { for (uint32_t i = 0; i < n; ++i) y[i] = gm_sin(x[i]); }
+void orc_math_exp(const float* x, float* y, uint32_t n) { for (uint32_t i = 0; i < n; ++i) y[i] = gm_exp(x[i]); }
+void orc_math_atan(const float* x, float* y, uint32_t n) { for (uint32_t i = 0; i < n; ++i) y[i] = gm_atan(x[i]); }
+// the saturating conversions and the 16-bit unorm quantiser (encodeBarycentric is q16 of shading.hip.h)
+void orc_math_sat(const float* x, int32_t* i32, uint32_t* u32, uint32_t* q16, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) { i32[i] = f2i(x[i]); u32[i] = f2u(x[i]); q16[i] = encodeBarycentric(x[i]); }
+}
+void orc_to_polar(const float* v3, float* phi, float* theta, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) toPolarYUp(V3(v3[3 * i], v3[3 * i + 1], v3[3 * i + 2]), &phi[i], &theta[i]);
+}
+void orc_encode_uv(const float* uv2, uint32_t* q, uint32_t n) { for (uint32_t i = 0; i < n; ++i) q[i] = encodeTexCoords(V2{ uv2[2 * i], uv2[2 * i + 1] }); }
+void orc_decode_uv(const uint32_t* q, float* uv2, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) { const V2 t = decodeTexCoords(q[i]); uv2[2 * i] = t.x; uv2[2 * i + 1] = t.y; }
+}
+void orc_encode_bc(const float* x, uint32_t* q, uint32_t n) { for (uint32_t i = 0; i < n; ++i) q[i] = encodeBarycentric(x[i]); }
+void orc_decode_bc(const uint32_t* q, float* x, uint32_t n) { for (uint32_t i = 0; i < n; ++i) x[i] = decodeBarycentric(static_cast<uint16_t>(q[i])); }
 void orc_encode_normal(const float* v3, uint32_t* q, uint32_t n) { for (uint32_t i = 0; i < n; ++i) q[i] = encodeNormal(V3(v3[3 * i], v3[3 * i + 1], v3[3 * i + 2])); }
 void orc_decode_normal(const uint32_t* q, float* v3, uint32_t n) {
     for (uint32_t i = 0; i < n; ++i) { const V3 v = decodeNormal(q[i]); v3[3 * i] = v.x; v3[3 * i + 1] = v.y; v3[3 * i + 2] = v.z; }

@@ -35,6 +35,35 @@ static inline float pow5(float x) { return x * pow4(x); }                 // bas
 static inline float lerpf(float v0, float v1, float t) { return (1 - t) * v0 + t * v1; }
 static inline bool finitef(float x) { return (f2bits(x) & 0x7F800000u) != 0x7F800000u; }
 
+// ---------------------------------------------------------------- the contract's domains (version 1)
+// Stated here and in gfxexp_amd/csrc/gm_math.hip.h; tests/test_math_contract_cpu.py holds the oracle copy to the bounds against float64,
+// tests/test_gpu_math_contract.py holds the device copy to the oracle bit for bit (lists: tests/math_cases.py; figures: DESIGN.md 4).
+//   gm_sincos / gm_sin / gm_cos   |x| <= 1e6: absolute error <= 1.25e-7.  |x| <= 2 pi: sin <= 1.5 ulp, cos <= 6 ulp (the float next to
+//                                 3 pi/2).  |x| <= 1e4: <= 622 ulp, reached only on the floats next to a multiple of pi/2.  Beyond 1e6 the
+//                                 error grows (9.3e-5 at 2.8e6), unspecified; defined for every input (f2i), NaN for +-inf and NaN.
+//                                 sincos(+-0) = (+0, 1).
+//   gm_tan                        |x| <= 1.5: <= 3 ulp; s / c of gm_sincos elsewhere.
+//   gm_exp                        kExpMin <= x <= kExpMax, kExpMin = -87.68312 (0xC2AF5DC2), kExpMax = 88.37626 (0x42B0C0A5): the x
+//                                 whose scale factor 2^n, n = floor(x log2(e) + 1/2), is 2^-126 .. 2^127.  <= 1.25 ulp where the result
+//                                 is normal (x >= kExpNormalMin = -87.33654, 0xC2AEAC4F), within one subnormal spacing below.  One float
+//                                 outside the result is 0 / +inf; further out it is garbage of either sign (gm_exp(-100) = -4.3e33),
+//                                 NaN at +-inf and NaN.  NOT total: callers guard (the denoiser with !(a >= -80)).  exp(+-0) = 1.
+//   gm_acos                       -1 <= x <= 1: <= 1.5 ulp; acos(1) = +0, acos(-1) = kPi.  NaN from the first float outside: callers
+//                                 clamp (to_polar_yup does).
+//   gm_atan                       every finite x and +-inf: <= 3 ulp; atan(+-inf) = +-kHalfPi, atan(+-0) = +0.
+//   gm_atan2                      every finite pair: <= 3.25 ulp, a zero counting as +0.  Special values (part of the contract --
+//                                 to_polar_yup at the phi seam rests on them -- and NOT those of IEEE atan2 where marked *):
+//                                   (+-0, +-0)            +0        * IEEE: (+-0, -0) = +-pi, (-0, +0) = -0
+//                                   (+-0, x > 0)          +0        * IEEE: -0 for y = -0
+//                                   (+-0, x < 0)          +pi       * IEEE: -pi for y = -0
+//                                   (y != 0, +-0)         +-pi/2 by the sign of y; (NaN, +-0) = +pi/2   * IEEE: NaN
+//                                   (+-inf, finite)       +-pi/2
+//                                   (finite y, +inf)      +-0 by y < 0;   (finite y, -inf)   +-pi by y < 0
+//                                   (+-inf, +-inf)        NaN       * IEEE: +-pi/4, +-3 pi/4
+//                                   NaN in x, or NaN in y with x != 0:  NaN
+//                                 A quotient |y| / |x| that underflows gives +-0 or +-pi, one that overflows +-pi/2.
+//   f2i / f2u                     total: NaN -> 0, saturating at the ends of the integer type, truncation inside.
+
 // saturating float -> integer conversions (the reference relies on in-range values;
 // the contract makes the out-of-range behaviour explicit so CPU and GPU agree).
 static inline uint32_t f2u(float x) {
@@ -75,7 +104,7 @@ static inline float gm_sin(float x) { float s, c; gm_sincos(x, &s, &c); return s
 static inline float gm_cos(float x) { float s, c; gm_sincos(x, &s, &c); return c; }
 static inline float gm_tan(float x) { float s, c; gm_sincos(x, &s, &c); return s / c; }
 
-// exp(x) for |x| < 80: n = round(x / ln2), Cody-Waite r = x - n ln2 (hi + lo), degree-6 kernel, 2^n by bits
+// exp(x) for kExpMin <= x <= kExpMax (above): n = round(x / ln2), Cody-Waite r = x - n ln2 (hi + lo), degree-6 kernel, 2^n by bits
 static inline float gm_exp(float x) {
     const float n = std::floor(x * 1.44269504088896341f + 0.5f);
     float r = std::fma(n, -0.693359375f, x);
@@ -98,7 +127,7 @@ static inline float gm_asin_kernel(float x) { // |x| <= 0.5
     p = std::fma(p, z, 1.6666752422e-1f);
     return std::fma(p * z, x, x);
 }
-static inline float gm_acos(float x) { // x in [-1, 1]
+static inline float gm_acos(float x) { // x in [-1, 1]; NaN outside
     if (x > 0.5f) {
         const float t = std::sqrt(0.5f * (1.0f - x));
         return 2.0f * gm_asin_kernel(t);
