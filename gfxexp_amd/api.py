@@ -316,6 +316,9 @@ GBUFFER3_DTYPE = np.dtype([("qShadingNormal", "<u4"), ("qShadingTangent", "<u4")
 LIGHTS_SAMPLE, LIGHTS_SAMPLE_SEARCH, LIGHTS_SAMPLE_SOLID_ANGLE = 0, 1, 2      # gfx_lights_sample_mode
 (MATH_SINCOS, MATH_EXP, MATH_ACOS, MATH_ATAN, MATH_ATAN2, MATH_SAT, MATH_TO_POLAR, MATH_DECODE_DIR, MATH_ENCODE_UV, MATH_DECODE_UV,
  MATH_ENCODE_BC, MATH_DECODE_BC, MATH_OFFSET_RAY_ORIGIN) = range(13)                                       # gfx_math_fn
+(BSDF_SETUP, BSDF_EVALUATE, BSDF_PDF, BSDF_SAMPLE, BSDF_DHR, BSDF_COSINE_HEMISPHERE, BSDF_COORDINATE_SYSTEM, BSDF_BUMP_FRAME,
+ BSDF_DIRECT_LIGHTING) = range(9)                                                                           # gfx_bsdf_fn
+BSDF_EVAL_WORDS = (8, 4, 4, 8, 4, 8, 8, 16, 12)                                                             # gfx_bsdf_eval_words
 LIGHT_SAMPLE_DTYPE = np.dtype([("emittance", "<f4", 3), ("areaPDensity", "<f4"), ("position", "<f4", 3), ("atInfinity", "<u4"),
                                ("normal", "<f4", 3), ("record", "<u4"), ("instSlot", "<u4"), ("tableUsed", "<u4"), ("pad", "<u4", 2)])
 
@@ -325,7 +328,7 @@ C_ABI_SYMBOLS = [
     "gfx_group_create", "gfx_instance_create", "gfx_instance_set_transform", "gfx_instance_set_transform_and_normal_matrix", "gfx_instance_set_dynamic",
     "gfx_accel_build",
     "gfx_accel_set_max_leaf", "gfx_accel_stats", "gfx_accel_tri_ids", "gfx_lights_build_static",
-    "gfx_lights_build_instances", "gfx_lights_read", "gfx_lights_table_info", "gfx_lights_sample", "gfx_math_eval", "gfx_trace", "gfx_trace_counted", "gfx_restir_set_params", "gfx_restir_copy_to_linear", "gfx_visualize", "gfx_restir_launch",
+    "gfx_lights_build_instances", "gfx_lights_read", "gfx_lights_table_info", "gfx_lights_sample", "gfx_math_eval", "gfx_bsdf_eval", "gfx_bsdf_eval_words", "gfx_trace", "gfx_trace_counted", "gfx_restir_set_params", "gfx_restir_copy_to_linear", "gfx_visualize", "gfx_restir_launch",
     "gfx_restir_copy_depth_to_linear", "gfx_restir_copy_emissive_to_linear", "gfx_denoiser_default_settings", "gfx_denoiser_create", "gfx_denoiser_destroy", "gfx_denoise",
     "gfx_denoiser_history", "gfx_restir_copy_taa_flow_to_linear", "gfx_taa_create", "gfx_taa_destroy", "gfx_taa_set_history_length", "gfx_taa_apply", "gfx_taa_history",
     "gfx_restir_launch_rows", "gfx_restir_launch_rows_gap", "gfx_pt_launch", "gfx_regir_set_params",
@@ -877,6 +880,13 @@ class Context:
         """gfx_math_eval: function MATH_* of the math contract or the quantisers on n arguments d_a (float4 each; d_b likewise, for
         MATH_OFFSET_RAY_ORIGIN) into d_out (uint32 [4][n]: up to four result words per element as bits, plane by plane)."""
         self._check(self.L.gfx_math_eval(self.h, C.c_void_p(stream), C.c_int(fn), C.c_void_p(d_a), C.c_void_p(d_b), C.c_uint32(n), C.c_void_p(d_out)))
+
+    def bsdf_eval(self, fn, n, d_out, d_mat=0, d_a=0, d_b=0, d_c=0, stream=0):
+        """gfx_bsdf_eval: function BSDF_* of the shading layer on n elements: d_mat (float4 [2 n]: (bits of bsdfType, a), (b, smoothness)
+        per element), d_a, d_b (float4 [n]) and d_c (float4 [4 n]) as the function reads them (include/gfxexp.h), into d_out
+        (uint32 [BSDF_EVAL_WORDS[fn]][n]: result words as bits, plane by plane)."""
+        self._check(self.L.gfx_bsdf_eval(self.h, C.c_void_p(stream), C.c_int(fn), C.c_void_p(d_mat), C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_c),
+                                         C.c_uint32(n), C.c_void_p(d_out)))
 
     def trace(self, accel, mode, d_ray_org, d_ray_dir, num_rays, d_out, d_counters=0, stream=0, d_per_ray_items=0):
         if d_per_ray_items:

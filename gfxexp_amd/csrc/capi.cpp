@@ -348,6 +348,16 @@ int gfx_math_eval(gfx_ctx* ctx, void* stream, int fn, const void* dA, const void
     GFX_CATCH(ctx)
 }
 
+int gfx_bsdf_eval(gfx_ctx* ctx, void* stream, int fn, const void* dMat, const void* dA, const void* dB, const void* dC, uint32_t n, void* dOut) {
+    GFX_TRY(ctx)
+    bsdf_eval(ctx->c, static_cast<hipStream_t>(stream), fn, dMat, dA, dB, dC, n, dOut);
+    GFX_CATCH(ctx)
+}
+
+uint32_t gfx_bsdf_eval_words(int fn) {
+    try { return bsdf_eval_words(fn); } catch (...) { return 0; }
+}
+
 int gfx_lights_table_info(gfx_ctx* ctx, uint32_t info[8]) {
     GFX_TRY(ctx)
     Context& c = ctx->c;

@@ -277,6 +277,9 @@ void lights_build_instances(Context& ctx, hipStream_t stream, uint32_t bufferInd
 void lights_sample(Context& ctx, hipStream_t stream, int mode, const float shadingPoint[3], const void* dU, uint32_t n, void* dOut);
 // ---- math_eval.hip
 void math_eval(Context& ctx, hipStream_t stream, int fn, const void* dA, const void* dB, uint32_t n, void* dOut);
+// ---- bsdf_eval.hip
+void bsdf_eval(Context& ctx, hipStream_t stream, int fn, const void* dMat, const void* dA, const void* dB, const void* dC, uint32_t n, void* dOut);
+uint32_t bsdf_eval_words(int fn);   // throws on an unknown fn
 // ---- restir.hip
 void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, uint32_t height, uint32_t rowBegin, uint32_t rowEnd, uint32_t gapBegin = 0, uint32_t gapEnd = 0);
 void restir_copy_to_linear(Context& ctx, hipStream_t stream, void* color, void* albedo, void* normal, void* motion);

@@ -303,7 +303,11 @@ struct Bsdf {
         gm_sincos(phi, sp, cp);
         const float P1 = r * cp;
         const float P2 = r * sp * ((u1 < a) ? 1.0f : sv.z);
-        m = P1 * T1 + P2 * T2 + sqrtf(1.0f - P1 * P1 - P2 * P2) * sv;
+        // sqrt(u0) rounds to 1 or 1 - 2^-24 for u0 >= 1 - 2^-23 (the generator's largest value) and the radicand then comes out as
+        // low as -2^-23: clamped like cosine_hemisphere's (the reference takes the square root of the negative number and returns NaN
+        // throughput, direction and density).  A radicand >= 0 passes unchanged -- a zero one is +0, never -0: x - y rounds to -0 only
+        // for x = -0 -- so no result that was finite changes.
+        m = P1 * T1 + P2 * T2 + sqrtf(fmax2(0.0f, 1.0f - P1 * P1 - P2 * P2)) * sv;
         m = unit(f3(ag * m.x, ag * m.y, m.z));
         const float D = ggx_d(ag, m);
         mPdf = ggx_g1(ag, v, m) * fabsf(dot(v, m)) * D / fabsf(v.z);
@@ -393,6 +397,10 @@ struct Bsdf {
         f3 ret = lobes(dirL, dirV, m, dotLH, D, oneMinusDotVN5);
         vSampled = entering ? dirL : -dirL;
         pdf = (pdfDiff * wDiff + pdfSpec * wSpec) / sumW;
+        // A sample of density exactly 0 (a direction in the horizon from u0 = 0 with no specular weight; a visible normal perpendicular to
+        // the view from the clamped radicand above with no diffuse weight) is one the callers drop (they extend only for density > 0): its
+        // throughput is 0, not the reference's f * (z / 0).  z / 0 is +-inf or NaN and no product with it is finite, so no finite result changes.
+        if (pdf == 0.0f) return f3(0.0f);
         ret = ret * (dirL.z / pdf);
         return ret;
     }

@@ -253,6 +253,32 @@ enum gfx_math_fn { GFX_MATH_SINCOS = 0, GFX_MATH_EXP = 1, GFX_MATH_ACOS = 2, GFX
                    GFX_MATH_DECODE_BC = 11, GFX_MATH_OFFSET_RAY_ORIGIN = 12 };
 int gfx_math_eval(gfx_ctx* ctx, void* stream, int fn, const void* dA, const void* dB, uint32_t n, void* dOut);
 
+/* Inspection / test entry of the shading layer (csrc/shading.hip.h): the BSDFs, the hemisphere sampler, the shading frame with its
+ * bump mapping and the unshadowed direct-lighting term, on n elements with the device functions the passes call.
+ * The material is given per element as constants: dMat = device float4[2 n], element i = (bits of bsdfType, a.rgb), (b.rgb, smoothness);
+ * every texture slot is 0 and Bsdf::setup runs on the device.  dA, dB = device float4[n]; dC = device float4[4 n] (four per element).
+ * A list a function does not read may be NULL; one it reads must not.  dOut = device uint32_t[words][n] with
+ * words = gfx_bsdf_eval_words(fn): result word k of element i at dOut[k * n + i], floats as their bits, unused words 0.  All buffers
+ * 16-byte aligned; n == 0 touches nothing.
+ *   GFX_BSDF_SETUP (8 words)             mat                                   -> diffuse rgb, specularF0 rgb, roughness
+ *   GFX_BSDF_EVALUATE (4)                mat, vGiven = A.xyz, vSampled = B.xyz -> evaluate rgb
+ *   GFX_BSDF_PDF (4)                     mat, vGiven = A.xyz, vSampled = B.xyz -> evaluate_pdf
+ *   GFX_BSDF_SAMPLE (8)                  mat, vGiven = A.xyz, u0 = B.x, u1 = B.y -> sample_throughput rgb, direction xyz, density
+ *                                        (the direction is 0 where sample_throughput returns before writing it)
+ *   GFX_BSDF_DHR (4)                     mat, vGiven = A.xyz                   -> dh_reflectance_estimate rgb
+ *   GFX_BSDF_COSINE_HEMISPHERE (8)       u0 = A.x, u1 = A.y                    -> concentric_disk dx, dy; cosine_hemisphere xyz
+ *   GFX_BSDF_COORDINATE_SYSTEM (8)       n = A.xyz                             -> make_coordinate_system tangent xyz, bitangent xyz
+ *   GFX_BSDF_BUMP_FRAME (16)             n = A.xyz, t = B.xyz, modNormal = C[0].xyz, probe = C[1].xyz
+ *                                        -> Frame(n, t) after apply_bump_mapping: t, b, n; to_local(probe); from_local(probe)
+ *   GFX_BSDF_DIRECT_LIGHTING (12)        mat, shadingPoint = A.xyz, vOutLocal = B.xyz, Frame(C[0].xyz, C[1].xyz), light sample:
+ *                                        emittance = C[2].xyz, position = C[3].xyz, normal = (C[0].w, C[1].w, C[2].w), atInfinity = bits of C[3].w
+ *                                        -> shadow_ray dir xyz, dist2, tmax; direct_lighting rgb; target_weight */
+enum gfx_bsdf_fn { GFX_BSDF_SETUP = 0, GFX_BSDF_EVALUATE = 1, GFX_BSDF_PDF = 2, GFX_BSDF_SAMPLE = 3, GFX_BSDF_DHR = 4, GFX_BSDF_COSINE_HEMISPHERE = 5,
+                   GFX_BSDF_COORDINATE_SYSTEM = 6, GFX_BSDF_BUMP_FRAME = 7, GFX_BSDF_DIRECT_LIGHTING = 8, GFX_BSDF_FN_COUNT = 9 };
+int gfx_bsdf_eval(gfx_ctx* ctx, void* stream, int fn, const void* dMat, const void* dA, const void* dB, const void* dC, uint32_t n, void* dOut);
+/* result words per element of gfx_bsdf_eval(fn); 0 for an unknown fn */
+uint32_t gfx_bsdf_eval_words(int fn);
+
 /* ---------------------------------------------------------------- ray queries ---------------- */
 
 /* Replaces optixTrace (utils/optix_util.h:557-603) for wavefront ray queues and the scalar

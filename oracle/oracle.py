@@ -475,6 +475,58 @@ def bsdf_eval(mat, mode, v_given, v_sampled):
     return out
 
 
+def _rows(x, k):
+    return np.ascontiguousarray(x, np.float32).reshape(-1, k)
+
+
+def bsdf_eval_materials(mat8, mode, v_given=None, v_sampled=None):
+    """orc_bsdf_eval with one material per element: mat8 float32 [n, 8] = (bits of bsdfType, a, b, smoothness).  Modes 0-3 as
+    bsdf_eval; 4 = setup alone -> diffuse, specular, roughness."""
+    m = _rows(mat8, 8)
+    vg = _rows(v_given, 3) if v_given is not None else np.zeros((len(m), 3), np.float32)
+    vs = _rows(v_sampled, 3) if v_sampled is not None else np.zeros((len(m), 3), np.float32)
+    assert len(vg) == len(m) == len(vs)
+    out = np.zeros((len(m), 7), np.float32)
+    lib().orc_bsdf_eval_materials(_p(m), C.c_int(mode), _p(vg), _p(vs), _p(out), C.c_uint32(len(m)))
+    return out
+
+
+def cosine_hemisphere(u2):
+    """(dx, dy) of concentricSampleDisk and xyz of cosineSampleHemisphere: float32 [n, 5]."""
+    u = _rows(u2, 2)
+    out = np.zeros((len(u), 5), np.float32)
+    lib().orc_cosine_hemisphere(_p(u), _p(out), C.c_uint32(len(u)))
+    return out
+
+
+def coordinate_system(n3):
+    """makeCoordinateSystem: tangent, bitangent as float32 [n, 6]."""
+    v = _rows(n3, 3)
+    out = np.zeros((len(v), 6), np.float32)
+    lib().orc_coordinate_system(_p(v), _p(out), C.c_uint32(len(v)))
+    return out
+
+
+def bump_frame(n3, t3, mod3, probe3):
+    """ReferenceFrame(n, t) after applyBumpMapping(mod): tangent, bitangent, normal, toLocal(probe), fromLocal(probe): float32 [n, 15]."""
+    a, b, c, d = _rows(n3, 3), _rows(t3, 3), _rows(mod3, 3), _rows(probe3, 3)
+    assert len(a) == len(b) == len(c) == len(d)
+    out = np.zeros((len(a), 15), np.float32)
+    lib().orc_bump_frame(_p(a), _p(b), _p(c), _p(d), _p(out), C.c_uint32(len(a)))
+    return out
+
+
+def direct_lighting(mat8, point3, v_out3, n3, t3, light9, at_infinity):
+    """Shadow ray (dir, dist2, tmax), unshadowed performDirectLighting rgb and convertToWeight per element: float32 [n, 9].
+    light9 = emittance, position, normal."""
+    m, p, v, a, b, l = _rows(mat8, 8), _rows(point3, 3), _rows(v_out3, 3), _rows(n3, 3), _rows(t3, 3), _rows(light9, 9)
+    inf = np.ascontiguousarray(at_infinity, np.uint32)
+    assert len(m) == len(p) == len(v) == len(a) == len(b) == len(l) == len(inf)
+    out = np.zeros((len(m), 9), np.float32)
+    lib().orc_direct_lighting(_p(m), _p(p), _p(v), _p(a), _p(b), _p(l), _p(inf), _p(out), C.c_uint32(len(m)))
+    return out
+
+
 def reservoir_stream(weights, us):
     w = np.ascontiguousarray(weights, np.float32)
     u = np.ascontiguousarray(us, np.float32)

@@ -552,6 +552,88 @@ void orc_bsdf_eval(const gfx_material* m, int mode, const float* vGiven3, const 
         else { const RGB r = b.evaluateDHReflectanceEstimate(vg); o[0] = r.x; o[1] = r.y; o[2] = r.z; }
     }
 }
+// ---- the shading layer on lists, one material per element (counterparts of gfx_bsdf_eval, gfxexp_amd/csrc/bsdf_eval.hip)
+// mat8 = (bits of bsdfType, a.rgb, b.rgb, smoothness); no textures
+static BSDF bsdfOfConstants(const float* mat8) {
+    MaterialData d; d.bsdfType = f2bits(mat8[0]);
+    for (int i = 0; i < 3; ++i) { d.a[i] = mat8[1 + i]; d.b[i] = mat8[4 + i]; d.emittance[i] = 0; }
+    d.smoothness = mat8[7]; d.hasEmittance = 0;
+    const TextureTable noTextures; BSDF b; b.setup(noTextures, d, V2{ 0.0f, 0.0f });
+    return b;
+}
+// orc_bsdf_eval with the material per element; mode 4: setup alone -> getSurfaceParameters diffuse, specular, roughness.
+// A sampleThroughput that returns before it writes the direction reports the direction 0.
+void orc_bsdf_eval_materials(const float* mat8, int mode, const float* vGiven3, const float* vSampled3, float* out7, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) {
+        const BSDF b = bsdfOfConstants(mat8 + 8 * static_cast<size_t>(i));
+        float* o = out7 + 7 * static_cast<size_t>(i);
+        for (int k = 0; k < 7; ++k) o[k] = 0;
+        if (mode == 4) {
+            RGB d, s; float r;
+            b.getSurfaceParameters(&d, &s, &r);
+            o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = s.x; o[4] = s.y; o[5] = s.z; o[6] = r;
+            continue;
+        }
+        const V3 vg(vGiven3[3 * i], vGiven3[3 * i + 1], vGiven3[3 * i + 2]);
+        const V3 vs = mode == 3 ? V3(0.0f) : V3(vSampled3[3 * i], vSampled3[3 * i + 1], vSampled3[3 * i + 2]);
+        if (mode == 0) { const RGB r = b.evaluate(vg, vs); o[0] = r.x; o[1] = r.y; o[2] = r.z; }
+        else if (mode == 1) o[0] = b.evaluatePDF(vg, vs);
+        else if (mode == 2) {
+            V3 dir(0.0f); float pdf = 0;
+            const RGB r = b.sampleThroughput(vg, vs.x, vs.y, &dir, &pdf);
+            o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = dir.x; o[4] = dir.y; o[5] = dir.z; o[6] = pdf;
+        }
+        else { const RGB r = b.evaluateDHReflectanceEstimate(vg); o[0] = r.x; o[1] = r.y; o[2] = r.z; }
+    }
+}
+// concentricSampleDisk dx, dy and cosineSampleHemisphere xyz
+void orc_cosine_hemisphere(const float* u2, float* out5, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) {
+        float* o = out5 + 5 * static_cast<size_t>(i);
+        concentricSampleDisk(u2[2 * i], u2[2 * i + 1], &o[0], &o[1]);
+        const V3 d = cosineSampleHemisphere(u2[2 * i], u2[2 * i + 1]);
+        o[2] = d.x; o[3] = d.y; o[4] = d.z;
+    }
+}
+void orc_coordinate_system(const float* n3, float* out6, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) {
+        V3 t, b;
+        makeCoordinateSystem(V3(n3[3 * i], n3[3 * i + 1], n3[3 * i + 2]), &t, &b);
+        float* o = out6 + 6 * static_cast<size_t>(i);
+        o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = b.x; o[4] = b.y; o[5] = b.z;
+    }
+}
+// ReferenceFrame(n, t) after applyBumpMapping(modNormal): tangent, bitangent, normal, toLocal(probe), fromLocal(probe)
+void orc_bump_frame(const float* n3, const float* t3, const float* mod3, const float* probe3, float* out15, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) {
+        ReferenceFrame f(V3(n3[3 * i], n3[3 * i + 1], n3[3 * i + 2]), V3(t3[3 * i], t3[3 * i + 1], t3[3 * i + 2]));
+        applyBumpMapping(V3(mod3[3 * i], mod3[3 * i + 1], mod3[3 * i + 2]), &f);
+        const V3 p(probe3[3 * i], probe3[3 * i + 1], probe3[3 * i + 2]);
+        const V3 v[5] = { f.tangent, f.bitangent, f.normal, f.toLocal(p), f.fromLocal(p) };
+        float* o = out15 + 15 * static_cast<size_t>(i);
+        for (int k = 0; k < 5; ++k) { o[3 * k] = v[k].x; o[3 * k + 1] = v[k].y; o[3 * k + 2] = v[k].z; }
+    }
+}
+// The shadow ray of evaluateVisibility (dir, tmax; dist2 of the same vector) and the unshadowed performDirectLighting with
+// convertToWeight, per element: material, shading point, vOutLocal, ReferenceFrame(n, t) and a LightSample as constants.
+// light9 = emittance, position, normal.
+void orc_direct_lighting(const float* mat8, const float* point3, const float* vOut3, const float* n3, const float* t3,
+                         const float* light9, const uint32_t* atInfinity, float* out9, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) {
+        const BSDF b = bsdfOfConstants(mat8 + 8 * static_cast<size_t>(i));
+        const V3 sp(point3[3 * i], point3[3 * i + 1], point3[3 * i + 2]);
+        const V3 vOut(vOut3[3 * i], vOut3[3 * i + 1], vOut3[3 * i + 2]);
+        const ReferenceFrame f(V3(n3[3 * i], n3[3 * i + 1], n3[3 * i + 2]), V3(t3[3 * i], t3[3 * i + 1], t3[3 * i + 2]));
+        const float* l = light9 + 9 * static_cast<size_t>(i);
+        LightSample ls;
+        ls.emittance = RGB(l[0], l[1], l[2]); ls.position = V3(l[3], l[4], l[5]); ls.normal = V3(l[6], l[7], l[8]); ls.atInfinity = atInfinity[i];
+        float* o = out9 + 9 * static_cast<size_t>(i);
+        evaluateVisibility([&](V3, V3 dir, float, float tmax) { o[0] = dir.x; o[1] = dir.y; o[2] = dir.z; o[4] = tmax; return true; }, sp, ls);
+        o[3] = sqLength(ls.atInfinity ? ls.position : (ls.position - sp));
+        const RGB c = performDirectLighting(false, VisibilityFn(), sp, vOut, f, b, ls);
+        o[5] = c.x; o[6] = c.y; o[7] = c.z; o[8] = convertToWeight(c);
+    }
+}
 // sampleLight<false> + unshadowed performDirectLighting from one shading point (config #1 plumbing)
 void orc_sample_light(orc_scene* s, const float* shadingPoint3, const float* u3, uint32_t n,
                       float* lightSample10, float* areaPDensity) {

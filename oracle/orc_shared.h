@@ -412,7 +412,9 @@ struct BSDF {
         gm_sincos(phi, &sinPhi, &cosPhi);
         const float P1 = r * cosPhi;
         const float P2 = r * sinPhi * ((u1 < a) ? 1.0f : sv.z);
-        *m = P1 * T1 + P2 * T2 + std::sqrt(1.0f - P1 * P1 - P2 * P2) * sv;
+        // departure from :497 (shading.hip.h ggx_sample has the same): the radicand is clamped at 0 as cosineSampleHemisphere's is.
+        // sqrt(u0) rounds to 1 or 1 - 2^-24 for u0 >= 1 - 2^-23 and the reference then returns NaNs; radicands >= 0 are unchanged.
+        *m = P1 * T1 + P2 * T2 + std::sqrt(fmax2(0.0f, 1.0f - P1 * P1 - P2 * P2)) * sv;
         *m = normalize(V3(alpha_g * m->x, alpha_g * m->y, m->z));
         const float D = ggxD(alpha_g, *m);
         *mPDensity = ggxSmithG1(alpha_g, v, *m) * std::fabs(dot(v, *m)) * D / std::fabs(v.z);
@@ -516,6 +518,9 @@ struct BSDF {
         RGB ret = diffuseValue + specularValue;
         *vSampled = entering ? dirL : -dirL;
         *dirPDensity = (diffuseDirPDF * diffuseWeight + specularDirPDF * specularWeight) / sumWeights;
+        // departure from :645 (shading.hip.h sample_throughput has the same): a sample of density exactly 0 has throughput 0, not
+        // f * (z / 0), which is never finite; callers drop such a sample by its density.
+        if (*dirPDensity == 0.0f) return RGB(0.0f);
         ret *= dirL.z / *dirPDensity;
         return ret;
     }

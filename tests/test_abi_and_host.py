@@ -22,7 +22,7 @@ def _declared(header):
 def test_every_declared_symbol_is_exported(built_lib):
     names = _declared("gfxexp.h") + _declared("gfxexp_host.h")
     assert len(names) > 40
-    assert {"gfx_texture_sample", "gfx_lights_sample", "gfx_math_eval"} <= set(names) & set(api.C_ABI_SYMBOLS)      # the inspection entries
+    assert {"gfx_texture_sample", "gfx_lights_sample", "gfx_math_eval", "gfx_bsdf_eval", "gfx_bsdf_eval_words"} <= set(names) & set(api.C_ABI_SYMBOLS)      # the inspection entries
     for n in names:
         assert hasattr(built_lib, n), f"{n} declared in include/ but not exported by libgfxexp.so"
     assert set(api.C_ABI_SYMBOLS) <= set(_declared("gfxexp.h"))
