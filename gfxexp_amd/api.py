@@ -339,6 +339,7 @@ C_ABI_SYMBOLS = [
     "gfx_tfdm_default_params", "gfx_tfdm_create", "gfx_tfdm_set_params", "gfx_tfdm_destroy", "gfx_tfdm_trace", "gfx_tfdm_read", "gfx_tfdm_size",
     "gfx_tfdm_set_create", "gfx_tfdm_set_add", "gfx_tfdm_set_transform", "gfx_tfdm_set_commit", "gfx_tfdm_set_read", "gfx_tfdm_set_destroy", "gfx_trace_scene",
     "gfx_scene_bind_displaced", "gfx_restir_primary_rays", "gfx_scene_bind_displaced_passes", "gfx_restir_last_rays",
+    "gfx_tfdm_set_move", "gfx_tfdm_set_read_motion",
 ]
 HOST_ABI_SYMBOLS = [
     "gfxh_scene_create", "gfxh_scene_destroy", "gfxh_last_error", "gfxh_scene_add_material_traditional",
@@ -1378,6 +1379,7 @@ GBUFFER_DISPLACED = 0x80000000       # GFX_GBUFFER_DISPLACED: gbuffer0.instSlot 
 SCENE_HIT_DTYPE = np.dtype([("dist", "<f4"), ("bcB", "<f4"), ("bcC", "<f4"), ("index", "<u4"), ("normal", "<f4", 3), ("where", "<u4")])
 TFDM_INSTANCE_DTYPE = np.dtype([("objToWorld", "<f4", 12), ("worldToObj", "<f4", 12), ("boxLo", "<f4", 3), ("userId", "<u4"), ("boxHi", "<f4", 3), ("pad0", "<u4"),
                                 ("nodes", "<u8"), ("records", "<u8"), ("heights", "<u8"), ("pyramid", "<u8"), ("params", "<u4", 8)])
+TFDM_MOTION_DTYPE = np.dtype([("curToPrev", "<f4", 12)])      # the motion table of a set: row-major 3 x 4, previous * inverse(current)
 TFDM_SET_MAX_INSTANCES = 1024
 
 
@@ -1396,8 +1398,10 @@ def _xfm12(m):
 
 class TfdmSet:
     """gfx_tfdm_set: Tfdm objects under object-to-world transforms (row-major 3 x 4, or a 4 x 4 whose last row is dropped), the
-    displaced instances of trace_scene.  commit() before the first query, and again after add / set_transform / a member's
-    Tfdm.set_params.  The set keeps its members alive."""
+    displaced instances of trace_scene.  commit() before the first query, and again after add / set_transform / move / a member's
+    Tfdm.set_params.  move() is the per-frame update of a moving instance (previous <- current, current <- the new transform: its
+    pixels get its motion vector); set_transform() is the teleport (previous <- current <- the new transform, no motion).  The set
+    keeps its members alive."""
 
     def __init__(self, ctx):
         self.L = lib()
@@ -1421,6 +1425,11 @@ class TfdmSet:
         x = _xfm12(obj_to_world)
         self.ctx._check(self.L.gfx_tfdm_set_transform(self.h, C.c_uint32(index), _p(x)))
 
+    def move(self, index, obj_to_world):
+        """gfx_tfdm_set_move: once per frame per moving instance; two moves between two commits lose the first position."""
+        x = _xfm12(obj_to_world)
+        self.ctx._check(self.L.gfx_tfdm_set_move(self.h, C.c_uint32(index), _p(x)))
+
     def commit(self, stream=0):
         self.ctx._check(self.L.gfx_tfdm_set_commit(self.ctx.h, C.c_void_p(stream), self.h))
 
@@ -1428,6 +1437,12 @@ class TfdmSet:
         """The committed InstanceRecord table (TFDM_INSTANCE_DTYPE)."""
         out = np.zeros(len(self.objects), TFDM_INSTANCE_DTYPE)
         self.ctx._check(self.L.gfx_tfdm_set_read(self.ctx.h, self.h, _p(out), C.c_size_t(out.nbytes)))
+        return out
+
+    def read_motion(self):
+        """The committed motion table (TFDM_MOTION_DTYPE): curToPrev per instance, the exact identity where it did not move."""
+        out = np.zeros(len(self.objects), TFDM_MOTION_DTYPE)
+        self.ctx._check(self.L.gfx_tfdm_set_read_motion(self.ctx.h, self.h, _p(out), C.c_size_t(out.nbytes)))
         return out
 
     def close(self):

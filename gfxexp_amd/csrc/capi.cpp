@@ -818,6 +818,12 @@ int gfx_tfdm_set_transform(gfx_tfdm_set* set, uint32_t index, const float objToW
     tfdm_set_transform(set->s, index, objToWorld);
     GFX_CATCH(set->ctx)
 }
+int gfx_tfdm_set_move(gfx_tfdm_set* set, uint32_t index, const float objToWorld[12]) {
+    if (!set) return 1;
+    GFX_TRY(set->ctx)
+    tfdm_set_move(set->s, index, objToWorld);
+    GFX_CATCH(set->ctx)
+}
 int gfx_tfdm_set_commit(gfx_ctx* ctx, void* stream, gfx_tfdm_set* set) {
     GFX_TRY(ctx)
     if (!set) throw HipError("gfx_tfdm_set_commit: null set");
@@ -830,6 +836,13 @@ int gfx_tfdm_set_read(gfx_ctx* ctx, gfx_tfdm_set* set, void* hostOut, size_t byt
     if (!set) throw HipError("gfx_tfdm_set_read: null set");
     if (set->s.device != ctx->c.device) throw HipError("gfx_tfdm_set_read: the set belongs to another device");
     tfdm_set_read(set->s, hostOut, bytes);
+    GFX_CATCH(ctx)
+}
+int gfx_tfdm_set_read_motion(gfx_ctx* ctx, gfx_tfdm_set* set, void* hostOut, size_t bytes) {
+    GFX_TRY(ctx)
+    if (!set) throw HipError("gfx_tfdm_set_read_motion: null set");
+    if (set->s.device != ctx->c.device) throw HipError("gfx_tfdm_set_read_motion: the set belongs to another device");
+    tfdm_set_read_motion(set->s, hostOut, bytes);
     GFX_CATCH(ctx)
 }
 int gfx_tfdm_set_destroy(gfx_tfdm_set* set) {

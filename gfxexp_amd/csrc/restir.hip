@@ -203,7 +203,8 @@ __global__ __launch_bounds__(kBlock) void k_gbuffer_resolve(RestirArgs a) {
 // (tfdm/tfdm_set.hip) and a pixel's hit a gfx_scene_hit.  A plain hit or a miss is resolved by the code above; a displaced hit by
 // tfdm/displaced_surface.hip.h (the closest-hit program's displaced branch, tfdm/gpu_kernels/optix_gbuffer_kernels.cu:218-271).
 // BSDF textures are read at level 0 (the reference passes the object's targetMipLevel; this library's textures have no mip chain);
-// no bump mapping on a displaced surface, as in the reference.
+// no bump mapping on a displaced surface, as in the reference.  The motion vector follows gfx_tfdm_set_move through the set's motion
+// table, as a plain pixel's follows gfx_instance_set_transform through curToPrevTransform.
 GFX_DEV tfdm::V3 to_v3(f3 v) { return tfdm::v3(v.x, v.y, v.z); }
 GFX_DEV f3 to_f3(tfdm::V3 v) { return f3(v.x, v.y, v.z); }
 GFX_DEV tfdm::BaseVertex base_vertex(const DevVertex& v) {
@@ -232,8 +233,11 @@ __global__ __launch_bounds__(kBlock) void k_gbuffer_resolve_scene(RestirArgs a, 
     const tfdm::BaseVertex vB = base_vertex(load_vertex(a.scene.vertices + g.vertexOffset + tri[1]));
     const tfdm::BaseVertex vC = base_vertex(load_vertex(a.scene.vertices + g.vertexOffset + tri[2]));
     const tfdm::DisplacedPoint sp = tfdm::displaced_point(d.table[k], sh, tfdm::v3(ro.x, ro.y, ro.z), tfdm::v3(rd.x, rd.y, rd.z), vA, vB, vC);
+    // the instance's curToPrev (tfdm_set.hip commits it with the table): a load per lane, lanes sit on different instances
+    const float4 m0 = d.motion[3u * k], m1 = d.motion[3u * k + 1u], m2 = d.motion[3u * k + 2u];
+    const float curToPrev[12] = { m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w };
     const tfdm::DisplacedGBuffer gb = tfdm::displaced_gbuffer(sp, sh, geomInstSlot, g.materialSlot, a.f.prevCamera, px.x, px.y, a.s.imageSizeX, a.s.imageSizeY,
-                                                              a.f.resetFlowBuffer != 0);
+                                                              a.f.resetFlowBuffer != 0, curToPrev);
     const gfx_material& mat = a.scene.materials[g.materialSlot];
     Bsdf bsdf; bsdf.setup(a.scene, mat, sp.u, sp.v);
     const Frame frame(to_f3(sp.normal), to_f3(sp.tangent));

@@ -10,8 +10,10 @@
 // made orthogonal to the normal, with the reference's two fallbacks (a normal that is not finite becomes +z with tangent +x; a
 // tangent that is not finite becomes makeCoordinateSystem's).
 //
-// G-buffer encoding of a displaced pixel (include/gfxexp.h): gbuffer0.instSlot = GFX_GBUFFER_DISPLACED | set index.  Displaced
-// instances are static for the motion vector: prevPositionInWorld = positionInWorld, only the camera moves.
+// G-buffer encoding of a displaced pixel (include/gfxexp.h): gbuffer0.instSlot = GFX_GBUFFER_DISPLACED | set index.  The motion
+// vector follows a moved instance: prevPositionInWorld = curToPrev * positionInWorld (optix_gbuffer_kernels.cu:230), with the
+// instance's row of the set's motion table (tfdm_instance.hip.h make_cur_to_prev; the exact identity for an instance that did not
+// move, which gives prevPositionInWorld = positionInWorld and the words of the form without a matrix).
 //
 // Under the math contract of tfdm_core.hip.h.  The polar quantiser and the camera projection need acos / atan2 / tan: they are the
 // algorithms of the "gm" contract, version 1 (gm_math.hip.h: Cody-Waite reduction + minimax kernels, every multiply-add spelled
@@ -176,14 +178,23 @@ GFX_TFDM_FN void displaced_motion_vector(const gfx_camera& cam, V3 pw, int x, in
     if (resetFlow || pw.x != pw.x) { mvx = 0.0f; mvy = 0.0f; }
 }
 
+// Where the world point `p` of an instance was before its last move: xfm_point of gm_math.hip.h (the arithmetic of the plain
+// pixel's prevPositionInWorld, restir.hip gbuffer_resolve) with the instance's curToPrev, row-major 3 x 4.
+GFX_TFDM_FN V3 displaced_prev_position(const float* m, V3 p) {
+    return v3(m[0] * p.x + m[1] * p.y + m[2] * p.z + m[3] * 1.0f, m[4] * p.x + m[5] * p.y + m[6] * p.z + m[7] * 1.0f,
+              m[8] * p.x + m[9] * p.y + m[10] * p.z + m[11] * 1.0f);
+}
+
+// curToPrev: the instance's row of the motion table; nullptr: an instance that never moved (prevPositionInWorld = positionInWorld)
 GFX_TFDM_FN DisplacedGBuffer displaced_gbuffer(const DisplacedPoint& p, const SceneHit& h, uint32_t geomInstSlot, uint32_t matSlot, const gfx_camera& prevCamera,
-                                               int x, int y, float imageSizeX, float imageSizeY, bool resetFlow) {
+                                               int x, int y, float imageSizeX, float imageSizeY, bool resetFlow, const float* curToPrev = nullptr) {
     DisplacedGBuffer g;
     g.g0[0] = kGbufferDisplaced | (h.where >> 1);
     g.g0[1] = geomInstSlot;
     g.g0[2] = h.index;
     g.g0[3] = ds_q16(h.bcB) | (ds_q16(h.bcC) << 16);
-    displaced_motion_vector(prevCamera, p.position, x, y, imageSizeX, imageSizeY, resetFlow, g.mv[0], g.mv[1]);
+    const V3 prevPosition = curToPrev ? displaced_prev_position(curToPrev, p.position) : p.position;
+    displaced_motion_vector(prevCamera, prevPosition, x, y, imageSizeX, imageSizeY, resetFlow, g.mv[0], g.mv[1]);
     g.position[0] = p.position.x; g.position[1] = p.position.y; g.position[2] = p.position.z;
     g.qGeometricNormal = ds_encode_dir(p.normal);
     g.g3[0] = g.qGeometricNormal;

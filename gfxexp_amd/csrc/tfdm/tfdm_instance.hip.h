@@ -163,5 +163,31 @@ inline const char* make_instance(const float objToWorld[12], const Node& root, c
     return nullptr;
 }
 
+// ---------------------------------------------------------------- host: the motion of an instance between two commits
+// curToPrev = prev * inverse(cur) (tfdm/tfdm_main.cpp:2476): takes a world point of the instance now to where that point of the
+// instance was (row-major 3 x 4).  Computed in double from the float entries and rounded to float once, as make_instance makes
+// worldToObj; `cur` is a transform make_instance accepted.  prev equal to cur bit for bit gives the exact identity, not the
+// rounded product: an instance that did not move has the bytes of one that never moved.  Returns a message where `prev` is not
+// finite or the result does not fit a float.
+inline const char* make_cur_to_prev(const float prev[12], const float cur[12], float out[12]) {
+    static const float ident[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
+    if (std::memcmp(prev, cur, sizeof(float) * 12) == 0) { std::memcpy(out, ident, sizeof(ident)); return nullptr; }
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(prev[i])) return "an entry of the instance's previous transform is not finite";
+    double m[9], mi[9];
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) m[3 * r + c] = cur[4 * r + c];
+    if (!invert3(m, mi)) return "the instance transform is singular";
+    for (int r = 0; r < 3; ++r) {
+        double row[3];
+        for (int c = 0; c < 3; ++c)
+            row[c] = (static_cast<double>(prev[4 * r]) * mi[c] + static_cast<double>(prev[4 * r + 1]) * mi[3 + c]) + static_cast<double>(prev[4 * r + 2]) * mi[6 + c];
+        const double t = static_cast<double>(prev[4 * r + 3]) -
+                         ((row[0] * static_cast<double>(cur[3]) + row[1] * static_cast<double>(cur[7])) + row[2] * static_cast<double>(cur[11]));
+        for (int c = 0; c < 3; ++c) out[4 * r + c] = static_cast<float>(row[c]);
+        out[4 * r + 3] = static_cast<float>(t);
+    }
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(out[i])) return "the motion of the instance does not fit a float";
+    return nullptr;
+}
+
 } // namespace tfdm
 } // namespace gfx

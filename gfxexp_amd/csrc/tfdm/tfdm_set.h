@@ -11,21 +11,26 @@ struct TfdmSet {
     struct Member {
         TfdmObject* obj;            // not owned: objects outlive the set
         float objToWorld[12];
+        float prevObjToWorld[12];   // where the instance was: the transform tfdm_set_move replaced (add and tfdm_set_transform: objToWorld)
         uint32_t userId;
         uint64_t generation;        // the object's generation the committed record was made from
     };
     std::vector<Member> members;
-    bool dirty = false;             // an add or a transform since the last commit
+    bool dirty = false;             // an add, a transform or a move since the last commit
     std::vector<tfdm::InstanceRecord> host;   // the committed table
+    std::vector<float> hostMotion;  // the committed motion table: curToPrev[12] per member (tfdm_instance.hip.h make_cur_to_prev)
     bool anyBilinear = false;       // ... has a member of GFX_TFDM_BILINEAR: the instance phase launches the instantiation that can run it
     DevBuf table;                   // InstanceRecord[members]
+    DevBuf motion;                  // float4[3 * members], the motion table: committed together with `table`
     DevBuf plain;                   // gfx_hit[numRays] of the plain phase of a closest-hit query; grows on demand
 };
 
 uint32_t tfdm_set_add(TfdmSet& s, TfdmObject* obj, const float objToWorld[12], uint32_t userId);
-void tfdm_set_transform(TfdmSet& s, uint32_t index, const float objToWorld[12]);
+void tfdm_set_transform(TfdmSet& s, uint32_t index, const float objToWorld[12]);   // the teleport: prev <- cur <- objToWorld
+void tfdm_set_move(TfdmSet& s, uint32_t index, const float objToWorld[12]);        // prev <- cur, cur <- objToWorld
 void tfdm_set_commit(TfdmSet& s, hipStream_t stream);
 void tfdm_set_read(TfdmSet& s, void* hostOut, size_t bytes);
+void tfdm_set_read_motion(TfdmSet& s, void* hostOut, size_t bytes);
 void tfdm_set_release(TfdmSet& s);
 // The scene query as the passes launch it (restir.hip, pathtrace.hip).  The ray count may be a device word (numRaysPtr; numRays is
 // then the queue capacity: k_scene_instances launches over it and the waves beyond the count leave at once), as TraceLaunch's is for
@@ -48,9 +53,10 @@ struct SceneTrace {
 void trace_scene_launch(Context& ctx, hipStream_t stream, const SceneTrace& t);
 void trace_scene_check_set(const TfdmSet& set, int device, const char* who);   // throws: foreign device, uncommitted change, stale member
 
-// what the set-bound passes read of a displaced hit: gfx_scene_hit[] as two float4 per entry, the committed instance table and the
-// geometry each instance is shaded with (Context::displaced)
-struct DisplacedArgs { const float4* hits; const tfdm::InstanceRecord* table; const uint32_t* geomSlots; };
+// what the set-bound passes read of a displaced hit: gfx_scene_hit[] as two float4 per entry, the committed instance table, the
+// geometry each instance is shaded with (Context::displaced) and the committed motion table (three float4 per instance: the rows
+// of curToPrev; only the G-buffer pass reads it)
+struct DisplacedArgs { const float4* hits; const tfdm::InstanceRecord* table; const uint32_t* geomSlots; const float4* motion; };
 
 // gfx_scene_bind_displaced_passes (set == nullptr: unbind; passMask: GFX_DISPLACED_*, the G-buffer pass and the path tracer are
 // always in it) and the check every set-bound launch repeats: the set as gfx_trace_scene wants it, and no bound geometry's material

@@ -107,6 +107,7 @@ uint32_t tfdm_set_add(TfdmSet& s, TfdmObject* obj, const float objToWorld[12], u
     TfdmSet::Member m;
     m.obj = obj; m.userId = userId; m.generation = 0;
     std::memcpy(m.objToWorld, objToWorld, sizeof(m.objToWorld));
+    std::memcpy(m.prevObjToWorld, objToWorld, sizeof(m.prevObjToWorld));
     s.members.push_back(m);
     s.dirty = true;
     return static_cast<uint32_t>(s.members.size() - 1);
@@ -116,25 +117,41 @@ void tfdm_set_transform(TfdmSet& s, uint32_t index, const float objToWorld[12]) 
     if (index >= s.members.size()) throw HipError("gfx_tfdm_set_transform: no such instance");
     if (!objToWorld) throw HipError("gfx_tfdm_set_transform: null transform");
     std::memcpy(s.members[index].objToWorld, objToWorld, sizeof(s.members[index].objToWorld));
+    std::memcpy(s.members[index].prevObjToWorld, objToWorld, sizeof(s.members[index].prevObjToWorld));      // a teleport: no motion
     s.dirty = true;
 }
 
-// The records are derived into a fresh table and swapped in only when every one of them worked.
+// InstanceController::update for a displaced instance, as gfx_instance_set_transform is for a plain one.
+void tfdm_set_move(TfdmSet& s, uint32_t index, const float objToWorld[12]) {
+    if (index >= s.members.size()) throw HipError("gfx_tfdm_set_move: no such instance");
+    if (!objToWorld) throw HipError("gfx_tfdm_set_move: null transform");
+    TfdmSet::Member& m = s.members[index];
+    std::memcpy(m.prevObjToWorld, m.objToWorld, sizeof(m.prevObjToWorld));
+    std::memcpy(m.objToWorld, objToWorld, sizeof(m.objToWorld));
+    s.dirty = true;
+}
+
+// The records and the motion table are derived into fresh tables and swapped in only when every one of them worked.
 void tfdm_set_commit(TfdmSet& s, hipStream_t stream) {
     std::vector<InstanceRecord> recs(s.members.size());
+    std::vector<float> motion(12 * s.members.size());
     for (size_t k = 0; k < s.members.size(); ++k) {
         const TfdmSet::Member& m = s.members[k];
         const TfdmObject& o = *m.obj;
         const char* err = make_instance(m.objToWorld, o.root, o.nodes.as<Node>(), o.records.as<TriRecord>(), o.heights.as<float>(), o.pyramid.as<F2>(), o.params,
                                         m.userId, recs[k]);
+        if (!err) err = make_cur_to_prev(m.prevObjToWorld, m.objToWorld, motion.data() + 12 * k);
         if (err) throw HipError("gfx_tfdm_set_commit: instance " + std::to_string(k) + ": " + err);
     }
     if (!recs.empty()) {
         s.table.reserve(sizeof(InstanceRecord) * recs.size());
+        s.motion.reserve(sizeof(float) * motion.size());
         GFX_HIP(hipMemcpyAsync(s.table.p, recs.data(), sizeof(InstanceRecord) * recs.size(), hipMemcpyHostToDevice, stream));
-        GFX_HIP(hipStreamSynchronize(stream));       // `recs` is pageable memory
+        GFX_HIP(hipMemcpyAsync(s.motion.p, motion.data(), sizeof(float) * motion.size(), hipMemcpyHostToDevice, stream));
+        GFX_HIP(hipStreamSynchronize(stream));       // `recs` and `motion` are pageable memory
     }
     s.host.swap(recs);
+    s.hostMotion.swap(motion);
     s.anyBilinear = false;
     for (const InstanceRecord& r : s.host) s.anyBilinear = s.anyBilinear || r.params.local == kBilinear;
     for (TfdmSet::Member& m : s.members) m.generation = m.obj->generation;
@@ -150,7 +167,16 @@ void tfdm_set_read(TfdmSet& s, void* hostOut, size_t bytes) {
     GFX_HIP(hipMemcpy(hostOut, s.table.p, need, hipMemcpyDeviceToHost));
 }
 
-void tfdm_set_release(TfdmSet& s) { s.table.release(); s.plain.release(); }
+void tfdm_set_read_motion(TfdmSet& s, void* hostOut, size_t bytes) {
+    if (s.dirty) throw HipError("gfx_tfdm_set_read_motion: the set has an add, a transform or a move that is not committed");
+    const size_t need = sizeof(float) * s.hostMotion.size();
+    if (bytes != need || (need && !hostOut)) throw HipError("gfx_tfdm_set_read_motion: the buffer must hold exactly 48 bytes per instance");
+    if (!need) return;
+    GFX_HIP(hipDeviceSynchronize());
+    GFX_HIP(hipMemcpy(hostOut, s.motion.p, need, hipMemcpyDeviceToHost));
+}
+
+void tfdm_set_release(TfdmSet& s) { s.table.release(); s.motion.release(); s.plain.release(); }
 
 void trace_scene_check_set(const TfdmSet& set, int device, const char* who) {
     const std::string w(who);
@@ -244,6 +270,7 @@ DisplacedArgs displaced_args(const Context& ctx, const void* hits) {
     d.hits = static_cast<const float4*>(hits);
     d.table = ctx.displaced.set->table.as<InstanceRecord>();
     d.geomSlots = ctx.displaced.dGeomSlots.as<uint32_t>();
+    d.motion = ctx.displaced.set->motion.as<float4>();
     return d;
 }
 

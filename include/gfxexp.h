@@ -534,7 +534,9 @@ typedef struct gfx_taa gfx_taa;              /* opaque; owns its double-buffered
  * that is GBuffer1.motionVector less the pixel's jitter offset ((x + 0.5) minus the hit point's current raster position); for a
  * pixel without a surface, the motion of its view direction under the camera rotation (svgf.cu:443-449; restir_di's miss program
  * projects the direction as a point, optix_gbuffer_kernels.cu:205-221); 0 under resetFlowBuffer.  The motion vector itself, fed
- * to TAA under enableJittering, resamples the history at a random sub-pixel offset every frame. */
+ * to TAA under enableJittering, resamples the history at a random sub-pixel offset every frame.  It reads only
+ * the G-buffers, so it follows whatever moved the surface: a plain instance under gfx_instance_set_transform and a displaced
+ * instance under gfx_tfdm_set_move alike. */
 int gfx_restir_copy_taa_flow_to_linear(gfx_ctx* ctx, void* stream, void* dLinearFlow);
 typedef struct gfx_taa_inputs {
     uint32_t width, height;                  /* of both buffers; must equal gfx_taa_create's */
@@ -849,14 +851,27 @@ int gfx_tfdm_size(gfx_ctx* ctx, gfx_tfdm* obj, int what, uint32_t level, size_t*
  * InstanceRecord: both matrices, the padded world box, the object's device pointers and parameters, userId) and uploads the
  * table; a transform that is not finite or is singular is refused there and the committed table stays.  gfx_tfdm_set_params
  * on a member gives the object new device buffers, so the set must be committed again before the next query.  Errors of the
- * functions without a context argument are reported through the context the set was created on (gfx_last_error). */
+ * functions without a context argument are reported through the context the set was created on (gfx_last_error).
+ * Motion.  Every instance has a current and a previous transform; gfx_tfdm_set_add sets both.
+ *   gfx_tfdm_set_move       previous <- the instance's transform at the call, current <- objToWorld: InstanceController::update, what
+ *                           gfx_instance_set_transform is for a plain instance.  Call it once per frame per moving instance: two
+ *                           moves between two commits lose the first position, as for plain instances.
+ *   gfx_tfdm_set_transform  the teleport: previous <- current <- objToWorld, no motion.
+ * gfx_tfdm_set_commit derives a second table from the pair, one 48-byte curToPrev per instance (row-major 3 x 4): previous *
+ * inverse(current), computed in double from the float entries and rounded to float once; the exact identity where the two are
+ * equal bit for bit.  The G-buffer pass of a binding takes a displaced pixel's previous position through it.  Both tables are
+ * swapped in together and only when every instance worked: a refused commit leaves both committed tables in force.  An instance
+ * keeps its motion until the next move or teleport, as a plain instance does. */
 typedef struct gfx_tfdm_set gfx_tfdm_set;
 int gfx_tfdm_set_create(gfx_ctx* ctx, gfx_tfdm_set** out);
 int gfx_tfdm_set_add(gfx_tfdm_set* set, gfx_tfdm* obj, const float objToWorld[12], uint32_t userId, uint32_t* index);
 int gfx_tfdm_set_transform(gfx_tfdm_set* set, uint32_t index, const float objToWorld[12]);
+int gfx_tfdm_set_move(gfx_tfdm_set* set, uint32_t index, const float objToWorld[12]);
 int gfx_tfdm_set_commit(gfx_ctx* ctx, void* stream, gfx_tfdm_set* set);
 /* The committed InstanceRecord table, 192 bytes per instance (`bytes` must be exactly that), for tests. */
 int gfx_tfdm_set_read(gfx_ctx* ctx, gfx_tfdm_set* set, void* hostOut, size_t bytes);
+/* The committed motion table, 48 bytes per instance (`bytes` must be exactly that), for tests; refuses what gfx_tfdm_set_read refuses. */
+int gfx_tfdm_set_read_motion(gfx_ctx* ctx, gfx_tfdm_set* set, void* hostOut, size_t bytes);
 int gfx_tfdm_set_destroy(gfx_tfdm_set* set);
 
 /* closest-hit record of gfx_trace_scene, 32 B (what a renderer needs from a displaced hit: tfdm/tfdm_shared.h:570-577).
@@ -892,7 +907,9 @@ int gfx_trace_scene(gfx_ctx* ctx, void* stream, uint64_t accel, gfx_tfdm_set* se
  * A displaced pixel in the G-buffers:
  *   gbuffer0   instSlot = GFX_GBUFFER_DISPLACED | k (k: the set index; 0xFFFFFFFF stays "no surface"), geomInstSlot = the bound
  *              geometry, primIndex = the base triangle, qbcB / qbcC = the base barycentrics
- *   gbuffer1   displaced instances are static for the motion vector: prevPositionInWorld = positionInWorld, only the camera moves
+ *   gbuffer1   the motion vector of prevPositionInWorld = curToPrev * positionInWorld under the previous camera, curToPrev being the
+ *              instance's entry of the set's motion table: an instance moved with gfx_tfdm_set_move carries its own motion, one that
+ *              was not moved (or was teleported with gfx_tfdm_set_transform) only the camera's
  *   gbuffer2   positionInWorld = origin + distance * direction of the world ray; qGeometricNormal = the hit's world normal
  *   gbuffer3   qShadingNormal = the same normal (no bump mapping on a displaced surface, as in the reference), qShadingTangent =
  *              texCoord0Dir of the base triangle in world space, orthogonal to it; qTexCoord, matSlot from the base triangle

@@ -11,6 +11,13 @@ INITIAL_AND_TEMPORAL_BIASED (INITIAL_RIS in frame 0), two SPATIAL_BIASED passes 
 displaced / tessellated: milliseconds per frame (HIP events around --frames frames after 3 warm-up frames), per-kernel times of one
 more frame from the context's timers, device bytes of the geometry (as tools/bench_displaced_render.py counts them).  Prints one JSON line.
 
+    python tools/bench_displaced_restir.py --move [--size 1024] [--frames 20] [--width 1920] [--height 1080]
+
+--move: the cost of the motion path.  Two steps over the displaced scene, each with one change of the wall's transform and one
+gfx_tfdm_set_commit per frame inside the timed loop: "move" changes it with gfx_tfdm_set_move (the wall's pixels get a motion vector
+and the temporal pass reprojects through it), "teleport" with gfx_tfdm_set_transform (no motion: the loop as it ran before moves
+existed).  The wall translates by 0.01 per frame along x.  move_minus_teleport_ms is the difference of the two ms_per_frame.
+
 Every GPU step is a child process of its own under a time limit (--step-timeout seconds); the first step that fails or runs out of
 time ends the run, and nothing more is started on the GPU after it."""
 import json
@@ -23,6 +30,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
 STEPS = ["displaced", "tessellated"]
+MOVE_STEPS = ["move", "teleport"]
 
 
 def _arg(argv, name, default):
@@ -51,7 +59,7 @@ def _setup(size, tess):
         tset.commit()
         ctx.bind_displaced(tset, [slot] * len(instances), restir=True)
         out["device_bytes"] = tf.device_bytes() + api.TFDM_RECORD_BYTES * len(instances)
-        keep = (tf, tset)
+        keep = (tf, tset, instances)
     return ctx, accel, keep, pos, target, out
 
 
@@ -62,11 +70,26 @@ def step_frames(name, size, frames, w, h):
     fr = K.RestirFrames(ctx, accel, w, h)
     cam = K.look_at_camera(w, h, pos, target)
     stream = torch.cuda.current_stream().cuda_stream
+    change = None
+    if name in MOVE_STEPS:
+        import numpy as np
+        tset = keep[1]
+        wall = np.array(keep[2][1][0], np.float32)        # instance 1 of the scene: the wall
+
+        def change(k):
+            m = wall.copy()
+            m[0, 3] += 0.01 * k
+            (tset.move if name == "move" else tset.set_transform)(1, m)
+            tset.commit(stream)
     for k in range(3):
+        if change:
+            change(k)
         fr.frame(k, cam, stream=stream)
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
     for k in range(frames):
+        if change:
+            change(3 + k)
         fr.frame(3 + k, cam, stream=stream)
     b.record()
     b.synchronize()
@@ -89,8 +112,9 @@ def main(argv):
         print("STEP_RESULT " + json.dumps(step_frames(name, size, frames, w, h)))
         return 0
     limit = _arg(argv, "--step-timeout", 300)
-    result = {"metric": "displaced_restir", "size": size, "frames": frames, "width": w, "height": h}
-    for name in STEPS:
+    move = "--move" in argv
+    result = {"metric": "displaced_restir_move" if move else "displaced_restir", "size": size, "frames": frames, "width": w, "height": h}
+    for name in (MOVE_STEPS if move else STEPS):
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name, "--size", str(size), "--frames", str(frames),
                "--width", str(w), "--height", str(h)]
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -100,6 +124,10 @@ def main(argv):
             print(json.dumps(result))
             return 1
         result[name] = json.loads(line[-1][len("STEP_RESULT "):])
+    if move:
+        result["move_minus_teleport_ms"] = round(result["move"]["ms_per_frame"] - result["teleport"]["ms_per_frame"], 4)
+        print(json.dumps(result))
+        return 0
     result["tessellated_over_displaced_ms"] = round(result["tessellated"]["ms_per_frame"] / result["displaced"]["ms_per_frame"], 3)
     result["tessellated_over_displaced_bytes"] = round(result["tessellated"]["device_bytes"] / result["displaced"]["device_bytes"], 1)
     print(json.dumps(result))

@@ -24,7 +24,13 @@ G-buffer pass and the baseline path tracer), --frames accumulated frames, writte
 
 --restir: the scene of --render by ReSTIR DI under a binding that carries GFX_DISPLACED_RESTIR (G-buffer, initial + temporal, two
 spatial passes, shading; the shadow rays are the scene's any-hit query), --frames accumulated frames, written tone-mapped as
-<out>_restir.png."""
+<out>_restir.png.
+
+    python tools/tfdm_view.py --scene --restir --move N [--step 0.02] [--size 256] [--width 960] [--height-px 540] [--out tfdm_view]
+
+--move N: N frames of the --restir scene with the wall translating by --step along x per frame (gfx_tfdm_set_move + commit before each
+frame after the first) and the ground fixed; temporal reuse is on and nothing is accumulated.  Writes the last frame as
+<out>_move.png and its motion vectors as <out>_motion.png (red / green = 0.5 + mv / 16 pixels: grey stands still)."""
 import argparse
 import json
 import os
@@ -69,6 +75,8 @@ def scene_render(a):
     frames = K.RestirFrames(ctx, accel, w, h) if a.restir else K.PathTraceFrames(ctx, accel, w, h)
     cam = K.look_at_camera(w, h, pos, target)
     stream = torch.cuda.current_stream().cuda_stream
+    if a.move:
+        return scene_move(a, ctx, tset, instances, frames, cam, stream)
     for k in range(a.frames):
         frames.frame(k, cam, stream=stream)
     beauty = frames.beauty()
@@ -79,6 +87,38 @@ def scene_render(a):
     print(json.dumps({"scene": "teapot on displaced ground, displaced wall, emissive rectangle", "size": int(heights.shape[0]), "frames": a.frames,
                       "displaced_pixel_share": round(float(((g0 != api.GFX_INVALID_SLOT) & (g0 >= api.GBUFFER_DISPLACED)).mean()), 4),
                       "renderer": "restir_di" if a.restir else "path_tracer", "mean_radiance": round(float(beauty[:, :3].mean()), 5), "images": [image]}))
+    return 0
+
+
+def scene_move(a, ctx, tset, instances, frames, cam, stream):
+    """--move: the wall (instance 1) translates along x, one gfx_tfdm_set_move + commit per frame; the ground stays."""
+    w, h = a.width, a.height_px
+    wall = np.array(instances[1][0], np.float32)
+    for k in range(a.move):
+        if k:
+            m = wall.copy()
+            m[0, 3] += a.step * k
+            tset.move(1, m)
+            tset.commit(stream)
+        frames.frame(k, cam, stream=stream, accumulate=False)
+    beauty = frames.beauty()
+    ctx.bind_displaced(None)
+    b = (a.move - 1) % 2
+    g0 = frames.t["gb0_%d" % b].cpu().numpy().view(np.uint32).reshape(-1, 4)[:, 0]
+    mv = frames.t["gb1_%d" % b].cpu().numpy().view(np.float32).reshape(-1, 2)
+    image, motion = a.out + "_move.png", a.out + "_motion.png"
+    api.save_image_sdr(image, beauty, w, h, api.sdr_config(brightness=1.0, tone_map=True, gamma=True))
+    img = np.zeros((w * h, 4), np.float32)
+    img[:, :2] = np.clip(0.5 + mv / 16.0, 0.0, 1.0)
+    img[:, 2:] = (0.5, 1.0)
+    api.save_image_sdr(motion, img, w, h, api.sdr_config(brightness=1.0, tone_map=False, gamma=False))
+    is_wall, is_ground = g0 == (api.GBUFFER_DISPLACED | 1), g0 == api.GBUFFER_DISPLACED
+    speed = np.hypot(mv[:, 0], mv[:, 1])
+    print(json.dumps({"scene": "teapot on displaced ground, displaced wall translating by %g per frame" % a.step, "frames": a.move,
+                      "wall_pixel_share": round(float(is_wall.mean()), 4),
+                      "wall_motion_pixels": round(float(speed[is_wall].mean()), 3) if is_wall.any() else None,
+                      "ground_motion_pixels": round(float(speed[is_ground].mean()), 5) if is_ground.any() else None,
+                      "mean_radiance": round(float(beauty[:, :3].mean()), 5), "images": [image, motion]}))
     return 0
 
 
@@ -148,7 +188,11 @@ def main():
     ap.add_argument("--render", action="store_true")
     ap.add_argument("--restir", action="store_true")
     ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--move", type=int, default=0)
+    ap.add_argument("--step", type=float, default=0.02)
     a = ap.parse_args()
+    if a.move and not (a.scene and a.restir):
+        ap.error("--move goes with --scene --restir")
     if a.render or a.restir:
         return scene_render(a)
     if a.scene:
