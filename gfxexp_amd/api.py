@@ -340,6 +340,7 @@ C_ABI_SYMBOLS = [
     "gfx_tfdm_set_create", "gfx_tfdm_set_add", "gfx_tfdm_set_transform", "gfx_tfdm_set_commit", "gfx_tfdm_set_read", "gfx_tfdm_set_destroy", "gfx_trace_scene",
     "gfx_scene_bind_displaced", "gfx_restir_primary_rays", "gfx_scene_bind_displaced_passes", "gfx_restir_last_rays",
     "gfx_tfdm_set_move", "gfx_tfdm_set_read_motion",
+    "gfx_nrtdsm_create", "gfx_nrtdsm_set_params", "gfx_nrtdsm_destroy", "gfx_nrtdsm_trace", "gfx_nrtdsm_read", "gfx_nrtdsm_size",
 ]
 HOST_ABI_SYMBOLS = [
     "gfxh_scene_create", "gfxh_scene_destroy", "gfxh_last_error", "gfxh_scene_add_material_traditional",
@@ -1364,6 +1365,84 @@ class Tfdm:
     def close(self):
         if self.h:
             self.L.gfx_tfdm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+NRTDSM_RECORD_DTYPE = np.dtype([("pos", "<f4", 9), ("nrm", "<f4", 9), ("tc", "<f4", 6), ("minHeight", "<f4"), ("amplitude", "<f4"),
+                                ("rootMinX", "<i4"), ("rootMinY", "<i4"), ("rootMaxX", "<i4"), ("rootMaxY", "<i4"), ("rootLod", "<i4"), ("numRoots", "<u4"),
+                                ("flipped", "<u4"), ("pad", "<u4", 3)])
+assert NRTDSM_RECORD_DTYPE.itemsize == 144
+
+
+class Nrtdsm:
+    """gfx_nrtdsm: a base mesh displaced by a height map along its interpolated, not renormalised normals, queried by rays
+    without tessellation and without cracks across shared base edges (csrc/nrtdsm/).  Arguments, ray and result layouts as Tfdm;
+    params: tfdm_params with target_mip_level 0 and the default local intersection; map values in [0, 1]."""
+
+    def __init__(self, ctx, vertices, triangles, heights, params=None, stream=0):
+        self.L = lib()
+        self.ctx = ctx
+        v = np.ascontiguousarray(vertices, VERTEX_DTYPE)
+        t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+        levels = [heights] if isinstance(heights, np.ndarray) else list(heights)
+        levels = [np.ascontiguousarray(a, np.float32) for a in levels]
+        if not levels or levels[0].ndim != 2 or levels[0].shape[0] != levels[0].shape[1]:
+            raise GfxError("Nrtdsm: the height map must be square (gfx_nrtdsm_create takes one size)")
+        self.size = int(levels[0].shape[0])
+        ptrs = (C.POINTER(C.c_float) * len(levels))(*[a.ctypes.data_as(C.POINTER(C.c_float)) for a in levels])
+        h = C.c_void_p()
+        ctx._check(self.L.gfx_nrtdsm_create(ctx.h, C.c_void_p(stream), _p(v), C.c_uint32(v.itemsize), C.c_uint32(len(v)), _p(t), C.c_uint32(len(t)),
+                                            ptrs, C.c_uint32(len(levels)), C.c_uint32(self.size), C.byref(params) if params is not None else None, C.byref(h)))
+        self.h = h
+        self.num_triangles = len(t)
+
+    def set_params(self, params, stream=0):
+        self.ctx._check(self.L.gfx_nrtdsm_set_params(self.ctx.h, C.c_void_p(stream), self.h, C.byref(params)))
+
+    def trace(self, mode, d_ray_org, d_ray_dir, num_rays, d_out, d_counters=0, stream=0):
+        """CLOSEST: d_out = TFDM_HIT_DTYPE[num_rays]; ANY: uint32[num_rays].  d_counters: device u64[4], added to."""
+        self.ctx._check(self.L.gfx_nrtdsm_trace(self.ctx.h, C.c_void_p(stream), self.h, C.c_int(mode), C.c_void_p(d_ray_org), C.c_void_p(d_ray_dir),
+                                                C.c_uint32(num_rays), C.c_void_p(d_out), C.c_void_p(d_counters or None)))
+
+    def size_of(self, what, level=0):
+        n = C.c_size_t()
+        self.ctx._check(self.L.gfx_nrtdsm_size(self.ctx.h, self.h, C.c_int(what), C.c_uint32(level), C.byref(n)))
+        return n.value
+
+    def device_bytes(self):
+        return self.size_of(-1)
+
+    def _read(self, what, level, dtype):
+        out = np.zeros(self.size_of(what, level), np.uint8)
+        self.ctx._check(self.L.gfx_nrtdsm_read(self.ctx.h, self.h, C.c_int(what), C.c_uint32(level), _p(out), C.c_size_t(out.nbytes)))
+        return out.view(dtype)
+
+    def read_pyramid(self, level):
+        w = self.size >> level
+        return self._read(TFDM_READ_PYRAMID, level, np.float32).reshape(w, w, 2)
+
+    def read_heights(self, level):
+        w = self.size >> level
+        return self._read(TFDM_READ_HEIGHTS, level, np.float32).reshape(w, w)
+
+    def read_aabbs(self):
+        return self._read(TFDM_READ_AABBS, 0, np.float32).reshape(-1, 6)
+
+    def read_records(self):
+        return self._read(TFDM_READ_RECORDS, 0, NRTDSM_RECORD_DTYPE)
+
+    def read_nodes(self):
+        return self._read(TFDM_READ_NODES, 0, TFDM_NODE_DTYPE)
+
+    def close(self):
+        if self.h:
+            self.L.gfx_nrtdsm_destroy(self.h)
             self.h = None
 
     def __del__(self):

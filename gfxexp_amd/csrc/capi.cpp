@@ -13,6 +13,7 @@
 #include "host/tex_format.h"
 #include "tfdm/tfdm.h"
 #include "tfdm/tfdm_set.h"
+#include "nrtdsm/nrtdsm.h"
 
 using namespace gfx;
 
@@ -24,6 +25,7 @@ struct gfx_denoiser { Denoiser d; };
 struct gfx_taa { TemporalAA t; };
 struct gfx_tfdm { TfdmObject o; };
 struct gfx_tfdm_set { TfdmSet s; gfx_ctx* ctx; };
+struct gfx_nrtdsm { NrtdsmObject o; };
 
 static thread_local std::string g_createError;
 
@@ -794,6 +796,59 @@ int gfx_tfdm_size(gfx_ctx* ctx, gfx_tfdm* obj, int what, uint32_t level, size_t*
     GFX_TRY(ctx)
     if (!obj || !bytes) throw HipError("gfx_tfdm_size: null object or output");
     *bytes = tfdm_size(obj->o, what, level);
+    GFX_CATCH(ctx)
+}
+
+int gfx_nrtdsm_create(gfx_ctx* ctx, void* stream, const void* vertices, uint32_t stride, uint32_t numVertices, const uint32_t* triangles, uint32_t numTriangles,
+                      const float* const* heightLevels, uint32_t numLevels, uint32_t size, const gfx_tfdm_params* params, gfx_nrtdsm** out) {
+    GFX_TRY(ctx)
+    if (!out) throw HipError("gfx_nrtdsm_create: null output handle");
+    *out = nullptr;
+    gfx_tfdm_params p;
+    if (params) p = *params;
+    else tfdm_default_params(&p);
+    std::unique_ptr<gfx_nrtdsm> t(new gfx_nrtdsm());
+    t->o.device = ctx->c.device;
+    try { nrtdsm_init(t->o, static_cast<hipStream_t>(stream), vertices, stride, numVertices, triangles, numTriangles, heightLevels, numLevels, size, p); }
+    catch (...) { nrtdsm_release(t->o); throw; }
+    *out = t.release();
+    GFX_CATCH(ctx)
+}
+int gfx_nrtdsm_set_params(gfx_ctx* ctx, void* stream, gfx_nrtdsm* obj, const gfx_tfdm_params* params) {
+    GFX_TRY(ctx)
+    if (!obj || !params) throw HipError("gfx_nrtdsm_set_params: null object or parameters");
+    if (obj->o.device != ctx->c.device) throw HipError("gfx_nrtdsm_set_params: the object belongs to another device");
+    nrtdsm_set_params(obj->o, static_cast<hipStream_t>(stream), *params);
+    GFX_CATCH(ctx)
+}
+int gfx_nrtdsm_destroy(gfx_nrtdsm* obj) {
+    if (!obj) return 1;
+    int prev = -1;
+    const bool switched = hipGetDevice(&prev) == hipSuccess && prev != obj->o.device && hipSetDevice(obj->o.device) == hipSuccess;
+    (void)hipDeviceSynchronize();
+    nrtdsm_release(obj->o);
+    if (switched) (void)hipSetDevice(prev);
+    delete obj;
+    return 0;
+}
+int gfx_nrtdsm_trace(gfx_ctx* ctx, void* stream, gfx_nrtdsm* obj, int mode, const void* dRayOrgTmin, const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters) {
+    GFX_TRY(ctx)
+    if (!obj) throw HipError("gfx_nrtdsm_trace: null object");
+    if (obj->o.device != ctx->c.device) throw HipError("gfx_nrtdsm_trace: the object belongs to another device");
+    ScopedKernelTimer timer(ctx->c, static_cast<hipStream_t>(stream), "k_nrtdsm_trace");
+    nrtdsm_trace(obj->o, static_cast<hipStream_t>(stream), mode, dRayOrgTmin, dRayDirTmax, numRays, dOut, dCounters);
+    GFX_CATCH(ctx)
+}
+int gfx_nrtdsm_read(gfx_ctx* ctx, gfx_nrtdsm* obj, int what, uint32_t level, void* hostOut, size_t bytes) {
+    GFX_TRY(ctx)
+    if (!obj) throw HipError("gfx_nrtdsm_read: null object");
+    nrtdsm_read(obj->o, what, level, hostOut, bytes);
+    GFX_CATCH(ctx)
+}
+int gfx_nrtdsm_size(gfx_ctx* ctx, gfx_nrtdsm* obj, int what, uint32_t level, size_t* bytes) {
+    GFX_TRY(ctx)
+    if (!obj || !bytes) throw HipError("gfx_nrtdsm_size: null object or output");
+    *bytes = nrtdsm_size(obj->o, what, level);
     GFX_CATCH(ctx)
 }
 

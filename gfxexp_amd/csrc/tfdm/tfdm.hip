@@ -35,19 +35,7 @@ namespace {
 #endif
 constexpr int kTraceBlock = GFX_TFDM_TRACE_BLOCK;
 
-__global__ void __launch_bounds__(256) k_tfdm_minmax_first(const float* __restrict__ heights, F2* __restrict__ pyramid, int maxDepth) {
-    const int w = 1 << maxDepth;
-    const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
-    if (x >= w || y >= w) return;
-    pyramid[y * w + x] = texel_min_max(heights, maxDepth, 0, x, y);
-}
-
-__global__ void __launch_bounds__(256) k_tfdm_minmax_level(const float* __restrict__ heights, F2* pyramid, int maxDepth, int level) {
-    const int w = 1 << (maxDepth - level);
-    const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
-    if (x >= w || y >= w) return;
-    pyramid[level_offset(maxDepth, level) + static_cast<uint32_t>(y * w + x)] = pyramid_reduce(heights, pyramid, maxDepth, level, x, y);
-}
+#include "tfdm_pyramid.hip.h"       // k_tfdm_minmax_first, k_tfdm_minmax_level
 
 __global__ void __launch_bounds__(64) k_tfdm_prim_aabbs(const TriRecord* __restrict__ records, const F2* __restrict__ pyramid, Params p, uint32_t numTriangles,
                                                         Box* __restrict__ aabbs) {

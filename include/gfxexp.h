@@ -844,6 +844,30 @@ int gfx_tfdm_read(gfx_ctx* ctx, gfx_tfdm* obj, int what, uint32_t level, void* h
 /* Size in bytes of what gfx_tfdm_read(what, level) returns; with what = -1 the device bytes the object owns in all. */
 int gfx_tfdm_size(gfx_ctx* ctx, gfx_tfdm* obj, int what, uint32_t level, size_t* bytes);
 
+/* ---------------------------------------------------------------- crack-free displacement mapping (NRTDSM) ----------------
+ * A second ray query on a displaced base mesh (the reference's nrtdsm/ program, displacement mapping only; DESIGN.md section
+ * 20).  The surface is S(alpha, beta) = P + (hOffset - s hBias + s h(tc)) N with s = hScale / sqrt(texScale[0] texScale[1]),
+ * P, tc and N the barycentric interpolations of the vertices, N NOT renormalised, h affine over each half texel (split along
+ * the TL-BR diagonal): two base triangles that share the two vertices of an edge (position, normal and texture coordinate)
+ * share the surface above it, which gfx_tfdm_* does not promise.  Parameters, hit record, counters, ray layout, alignment and
+ * the items of read / size are those of gfx_tfdm_*; GFX_TFDM_READ_RECORDS gives the 144-byte records of
+ * csrc/nrtdsm/nrtdsm_core.hip.h.  The hit's normal is the unit normal of the curved micro-patch at the hit, on the side of
+ * growing height.  create and set_params refuse, with a message and without launching anything: targetMipLevel != 0; a
+ * localIntersection other than GFX_TFDM_TWO_TRIANGLE; a map value outside [0, 1] at any level; parameters that are not finite or a
+ * texScale that is not positive; a texture coordinate that reaches 2^24 texels.  After a refused set_params the object is as before.
+ * A ray that is not finite or has a zero direction misses. */
+typedef struct gfx_nrtdsm gfx_nrtdsm;                   /* opaque; owns heights, pyramid, records, AABBs, tree */
+int gfx_nrtdsm_create(gfx_ctx* ctx, void* stream, const void* vertices, uint32_t stride, uint32_t numVertices,
+                      const uint32_t* triangles, uint32_t numTriangles,
+                      const float* const* heightLevels, uint32_t numLevels, uint32_t size,
+                      const gfx_tfdm_params* params, gfx_nrtdsm** out);
+int gfx_nrtdsm_set_params(gfx_ctx* ctx, void* stream, gfx_nrtdsm* obj, const gfx_tfdm_params* params);
+int gfx_nrtdsm_destroy(gfx_nrtdsm* obj);
+int gfx_nrtdsm_trace(gfx_ctx* ctx, void* stream, gfx_nrtdsm* obj, int mode, const void* dRayOrgTmin, const void* dRayDirTmax,
+                     uint32_t numRays, void* dOut, void* dCounters);
+int gfx_nrtdsm_read(gfx_ctx* ctx, gfx_nrtdsm* obj, int what, uint32_t level, void* hostOut, size_t bytes);
+int gfx_nrtdsm_size(gfx_ctx* ctx, gfx_nrtdsm* obj, int what, uint32_t level, size_t* bytes);
+
 /* ---------------------------------------------------------------- plain and displaced instances in one query -------------
  * A set of displaced instances: gfx_tfdm objects under object-to-world transforms (row-major 3 x 4, as
  * gfx_instance_set_transform takes them), at most 1024.  One object may be added many times; objects and the context must

@@ -6,8 +6,9 @@
 the Box, the TwoTriangle and the Bilinear (Newton) local intersection at map levels 0 and 2; and the same quad rays through gfx_trace on the quad
 tessellated to 2 x size x size triangles.  Per variant: microseconds per launch (HIP events around --iters launches after a
 warm-up), Mrays/s, texel AABB tests / leaf tests / base triangles per ray from a counting launch of its own, and the device bytes
-of either representation.  --variants: only these (two_triangle_l0, box_l2, bilinear_l0, ...), for a library that lacks one.  Prints
-one JSON line.
+of either representation.  Beside them the crack-free NRTDSM query (gfx_nrtdsm_trace, "nrtdsm") on the same mesh, map and rays, with
+its own device bytes.  --variants: only these (two_triangle_l0, box_l2, bilinear_l0, nrtdsm, ...), for a library that lacks one.
+Prints one JSON line.
 
 Every GPU step is a child process of its own under a time limit (--step-timeout seconds); the first step that fails or runs out of
 time ends the run, and nothing more is started on the GPU after it."""
@@ -98,6 +99,22 @@ def step(name, size, iters, w, h, only=None):
                                   "hit_share": round(float((hits["primIndex"] != api.GFX_INVALID_SLOT).mean()), 4),
                                   "aabb_tests_per_ray": round(float(cnt[0]) / n, 2), "leaf_tests_per_ray": round(float(cnt[1]) / n, 2),
                                   "base_triangles_per_ray": round(float(cnt[3]) / n, 2)}
+    if not only or "nrtdsm" in only:
+        # the crack-free query (csrc/nrtdsm/) on the same mesh, map and rays: one variant, level 0
+        nr = api.Nrtdsm(ctx, v, t, heights, api.tfdm_params(h_scale=h_scale))
+        secs = timed(lambda: nr.trace(api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), stream=stream), iters)
+        hits = d_out.cpu().numpy().view(api.TFDM_HIT_DTYPE)[:n]
+        d_cnt = torch.zeros(4, dtype=torch.int64, device="cuda")
+        nr.trace(api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), d_cnt.data_ptr(), stream=stream)
+        torch.cuda.synchronize()
+        cnt = d_cnt.cpu().numpy()
+        out["nrtdsm"] = {"us": round(secs * 1e6, 1), "Mrays_per_s": round(n / secs / 1e6, 1),
+                         "hit_share": round(float((hits["primIndex"] != api.GFX_INVALID_SLOT).mean()), 4),
+                         "aabb_tests_per_ray": round(float(cnt[0]) / n, 2), "leaf_tests_per_ray": round(float(cnt[1]) / n, 2),
+                         "base_triangles_per_ray": round(float(cnt[3]) / n, 2), "device_bytes": nr.device_bytes()}
+        nr.close()
+    if tf is None:
+        return out
     out["device_bytes"] = tf.device_bytes()
     out["pyramid_and_heights_bytes"] = tf.size_of(api.TFDM_READ_PYRAMID, 0) * 4 // 3 + tf.size_of(api.TFDM_READ_HEIGHTS, 0) * 4 // 3
     return out
@@ -123,7 +140,8 @@ def main(argv):
             return 1
         result[name] = json.loads(line[-1][len("STEP_RESULT "):])
     q, m = result["tfdm_quad"], result["mesh_quad"]
-    result["memory_ratio_mesh_over_tfdm"] = round((m["bvh_bytes"] + m["scene_geometry_bytes"]) / q["device_bytes"], 2)
+    if "device_bytes" in q:
+        result["memory_ratio_mesh_over_tfdm"] = round((m["bvh_bytes"] + m["scene_geometry_bytes"]) / q["device_bytes"], 2)
     print(json.dumps(result))
     return 0
 

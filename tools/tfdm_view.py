@@ -9,6 +9,11 @@ Newton's iteration) instead of two triangles per texel; with --scene, --render a
 displaced object.  Writes <out>_normal.png (n * 0.5 + 0.5 in object space) and <out>_depth.png (near = bright), and
 prints the hit share and the traversal counters per ray.
 
+    python tools/tfdm_view.py --nrtdsm [--mesh teapot] [--height FILE] [--size 256] [--scale 0.05] [--out tfdm_view]
+
+--nrtdsm: the same images through gfx_nrtdsm_trace, the crack-free query that displaces along the interpolated, not renormalised normals
+(csrc/nrtdsm/); the teapot unless --mesh says otherwise.  Map values must lie in [0, 1].
+
     python tools/tfdm_view.py --scene [--size 256] [--width 960] [--height-px 540] [--out tfdm_view]
 
 --scene: a plain teapot on a displaced ground quad with a second displaced quad as a tilted wall (tfdm_common.mixed_scene), through
@@ -171,7 +176,7 @@ def scene_view(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mesh", default="quad", choices=["quad", "bunny", "teapot"])
+    ap.add_argument("--mesh", default=None, choices=["quad", "bunny", "teapot"])      # the quad; with --nrtdsm the teapot
     ap.add_argument("--height")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--scale", type=float, default=0.05)
@@ -184,6 +189,7 @@ def main():
     ap.add_argument("--width", type=int, default=960)
     ap.add_argument("--height-px", type=int, default=540)
     ap.add_argument("--out", default="tfdm_view")
+    ap.add_argument("--nrtdsm", action="store_true")
     ap.add_argument("--scene", action="store_true")
     ap.add_argument("--render", action="store_true")
     ap.add_argument("--restir", action="store_true")
@@ -191,6 +197,8 @@ def main():
     ap.add_argument("--move", type=int, default=0)
     ap.add_argument("--step", type=float, default=0.02)
     a = ap.parse_args()
+    if a.mesh is None:
+        a.mesh = "teapot" if a.nrtdsm and not a.scene else "quad"
     if a.move and not (a.scene and a.restir):
         ap.error("--move goes with --scene --restir")
     if a.render or a.restir:
@@ -202,7 +210,12 @@ def main():
     gp = api.tfdm_params(h_scale=a.scale * K.extent(v), tex_scale=(a.tex_scale, a.tex_scale), tex_rotation=a.rotation, target_mip_level=a.level,
                          local_intersection=_local(a))
     ctx = api.Context(0)
-    tf = api.Tfdm(ctx, v, t, heights, gp)
+    if a.nrtdsm:
+        if a.box or a.bilinear or a.level:
+            ap.error("--nrtdsm has one local intersection and descends to level 0")
+        tf = api.Nrtdsm(ctx, v, t, heights, gp)
+    else:
+        tf = api.Tfdm(ctx, v, t, heights, gp)
     w, h = a.width, a.height_px
     org, dirs = api.camera_rays(K.look_at_camera(w, h, pos, target, up=up), w, h)
     d_org, d_dir = torch.from_numpy(org).cuda(), torch.from_numpy(dirs).cuda()
@@ -224,7 +237,7 @@ def main():
         d = hits["dist"][hit]
         depth[hit, :3] = (1.0 - 0.9 * (d - d.min()) / max(float(d.max() - d.min()), 1e-30))[:, None]
     api.save_image_sdr(a.out + "_depth.png", depth, w, h, sdr)
-    print(json.dumps({"mesh": a.mesh, "size": int(heights.shape[0]), "triangles": int(len(t)), "rays": w * h, "hit_share": round(float(hit.mean()), 4),
+    print(json.dumps({"query": "nrtdsm" if a.nrtdsm else "tfdm", "mesh": a.mesh, "size": int(heights.shape[0]), "triangles": int(len(t)), "rays": w * h, "hit_share": round(float(hit.mean()), 4),
                       "aabb_tests_per_ray": round(float(cnt[0]) / (w * h), 2), "leaf_tests_per_ray": round(float(cnt[1]) / (w * h), 2),
                       "base_triangles_per_ray": round(float(cnt[3]) / (w * h), 2), "device_bytes": tf.device_bytes(),
                       "images": [a.out + "_normal.png", a.out + "_depth.png"]}))
