@@ -212,7 +212,8 @@ def abi_mirrors():
             "gfxh_nrc_config": GfxhNrcConfig, "gfxh_sdr_config": GfxhSdrConfig,
             "gfx_denoiser_settings": GfxDenoiserSettings, "gfx_denoiser_inputs": GfxDenoiserInputs,
             "gfx_denoiser_history_buffers": GfxDenoiserHistoryBuffers, "gfx_taa_inputs": GfxTaaInputs, "gfxh_dds_info": GfxhDdsInfo,
-            "gfxh_image_desc": GfxhImageDesc, "gfx_tfdm_params": GfxTfdmParams, "gfx_tfdm_hit": GfxTfdmHit, "gfx_scene_hit": GfxSceneHit}
+            "gfxh_image_desc": GfxhImageDesc, "gfx_tfdm_params": GfxTfdmParams, "gfx_tfdm_hit": GfxTfdmHit, "gfx_scene_hit": GfxSceneHit,
+            "gfx_shell_hit": GfxShellHit, "gfx_shell_geom": GfxShellGeom}
 
 
 class RcclExchange:
@@ -341,10 +342,11 @@ C_ABI_SYMBOLS = [
     "gfx_scene_bind_displaced", "gfx_restir_primary_rays", "gfx_scene_bind_displaced_passes", "gfx_restir_last_rays",
     "gfx_tfdm_set_move", "gfx_tfdm_set_read_motion",
     "gfx_nrtdsm_create", "gfx_nrtdsm_set_params", "gfx_nrtdsm_destroy", "gfx_nrtdsm_trace", "gfx_nrtdsm_read", "gfx_nrtdsm_size",
+    "gfx_shell_create", "gfx_shell_set_params", "gfx_shell_set_geometry", "gfx_shell_destroy", "gfx_shell_trace", "gfx_shell_read", "gfx_shell_size",
 ]
 HOST_ABI_SYMBOLS = [
     "gfxh_scene_create", "gfxh_scene_destroy", "gfxh_last_error", "gfxh_scene_add_material_traditional",
-    "gfxh_scene_add_material", "gfxh_scene_add_texture", "gfxh_scene_load_texture", "gfxh_scene_num_textures", "gfxh_scene_get_texture", "gfxh_scene_add_texture_bc", "gfxh_scene_get_texture_bc", "gfxh_dds_parse", "gfxh_image_info", "gfxh_image_decode_rgba8", "gfxh_tfdm_load_height", "gfxh_tfdm_free_height", "gfxh_scene_add_geom", "gfxh_scene_add_group", "gfxh_scene_add_instance",
+    "gfxh_scene_add_material", "gfxh_scene_add_texture", "gfxh_scene_load_texture", "gfxh_scene_num_textures", "gfxh_scene_get_texture", "gfxh_scene_add_texture_bc", "gfxh_scene_get_texture_bc", "gfxh_dds_parse", "gfxh_image_info", "gfxh_image_decode_rgba8", "gfxh_tfdm_load_height", "gfxh_tfdm_free_height", "gfxh_shell_fit", "gfxh_shell_box", "gfxh_scene_add_geom", "gfxh_scene_add_group", "gfxh_scene_add_instance",
     "gfxh_scene_load_obj", "gfxh_scene_load_obj_conv", "gfxh_scene_add_rectangle_textured", "gfxh_scene_add_rectangle", "gfxh_scene_make_street", "gfxh_scene_counts",
     "gfxh_scene_get_material", "gfxh_scene_get_geom", "gfxh_scene_get_group", "gfxh_scene_get_instance",
     "gfxh_scene_bounds", "gfxh_scene_upload", "gfxh_make_transform", "gfxh_make_orientation",
@@ -1650,3 +1652,122 @@ class RestirRenderer:
         a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
         self.L.gfxh_restir_get_params(self.h, C.byref(s), C.byref(f), C.byref(a), C.byref(b), C.byref(c))
         return s, f, a.value, b.value, c.value
+
+
+SHELL_READ_SHELL_NODES, SHELL_READ_SHELL_TRIANGLES = 5, 6
+SHELL_HIT_DTYPE = np.dtype([("dist", "<f4"), ("bcB", "<f4"), ("bcC", "<f4"), ("primIndex", "<u4"), ("normal", "<f4", 3), ("frontFace", "<u4"),
+                            ("shellTriangle", "<u4"), ("shellGeom", "<u4"), ("tile", "<i4", 2)])
+SHELL_TRI_DTYPE = np.dtype([("a", "<f4", 3), ("b", "<f4", 3), ("c", "<f4", 3), ("geom", "<u4"), ("pad", "<u4", 2)])
+assert SHELL_HIT_DTYPE.itemsize == 48 and SHELL_TRI_DTYPE.itemsize == 48
+
+
+class GfxShellHit(C.Structure):
+    _fields_ = [("dist", C.c_float), ("bcB", C.c_float), ("bcC", C.c_float), ("primIndex", C.c_uint32), ("normal", C.c_float * 3), ("frontFace", C.c_uint32),
+                ("shellTriangle", C.c_uint32), ("shellGeom", C.c_uint32), ("tile", C.c_int32 * 2)]
+
+
+class GfxShellGeom(C.Structure):
+    _fields_ = [("positions", C.c_void_p), ("stride", C.c_uint32), ("numVertices", C.c_uint32), ("triangles", C.c_void_p), ("numTriangles", C.c_uint32)]
+
+
+def shell_params(h_offset=0.0, h_scale=1.0, h_bias=0.0, tex_scale=(1.0, 1.0), tex_rotation=0.0, tex_offset=(0.0, 0.0)):
+    """gfx_tfdm_params for a Shell: targetMipLevel and localIntersection 0."""
+    return tfdm_params(h_offset, h_scale, h_bias, tex_scale, tex_rotation, tex_offset, 0, 0)
+
+
+def shell_fit(positions, y_up=False):
+    """gfxh_shell_fit: [n, 3] points placed in the unit tile as float32 (u, v, h)."""
+    p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    out = np.zeros_like(p)
+    if lib().gfxh_shell_fit(_p(p), C.c_uint32(len(p)), C.c_int(1 if y_up else 0), _p(out)):
+        raise GfxError(lib().gfxh_last_error().decode(errors="replace"))
+    return out
+
+
+def shell_box():
+    """gfxh_shell_box: (positions float32 [8, 3], triangles uint32 [12, 3]) of the "One Box" shell."""
+    pos, tri = np.zeros((8, 3), np.float32), np.zeros((12, 3), np.uint32)
+    if lib().gfxh_shell_box(_p(pos), _p(tri)):
+        raise GfxError(lib().gfxh_last_error().decode(errors="replace"))
+    return pos, tri
+
+
+def _shell_geoms(geoms):
+    """[(positions [n, 3], triangles [m, 3]), ...] -> (gfx_shell_geom array, the arrays it points into)"""
+    keep = [(np.ascontiguousarray(p, np.float32).reshape(-1, 3), np.ascontiguousarray(t, np.uint32).reshape(-1, 3)) for p, t in geoms]
+    arr = (GfxShellGeom * max(len(keep), 1))()
+    for k, (p, t) in enumerate(keep):
+        arr[k].positions, arr[k].stride, arr[k].numVertices = p.ctypes.data, 12, len(p)
+        arr[k].triangles, arr[k].numTriangles = t.ctypes.data, len(t)
+    return arr, keep
+
+
+class Shell:
+    """gfx_shell: a small triangle mesh in the unit tile of shell space (u, v, h), repeated over a base mesh like a texture and
+    queried by rays without being instantiated (csrc/nrtdsm/shell*).  vertices / triangles: the base mesh as for Nrtdsm; geoms: a
+    list of (positions [n, 3] as (u, v, h), triangles [m, 3]), at most 8; params: shell_params().  Rays as Context.trace; a closest
+    hit is SHELL_HIT_DTYPE."""
+
+    def __init__(self, ctx, vertices, triangles, geoms, params=None, stream=0):
+        self.L = lib()
+        self.ctx = ctx
+        v = np.ascontiguousarray(vertices, VERTEX_DTYPE)
+        t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+        arr, keep = _shell_geoms(geoms)
+        h = C.c_void_p()
+        ctx._check(self.L.gfx_shell_create(ctx.h, C.c_void_p(stream), _p(v), C.c_uint32(v.itemsize), C.c_uint32(len(v)), _p(t), C.c_uint32(len(t)),
+                                           arr, C.c_uint32(len(keep)), C.byref(params) if params is not None else None, C.byref(h)))
+        self.h = h
+        self.num_triangles = len(t)
+
+    def set_params(self, params, stream=0):
+        self.ctx._check(self.L.gfx_shell_set_params(self.ctx.h, C.c_void_p(stream), self.h, C.byref(params)))
+
+    def set_geometry(self, geoms, stream=0):
+        """Another shell mesh over the same base mesh; a refused call leaves the object as it was."""
+        arr, keep = _shell_geoms(geoms)
+        self.ctx._check(self.L.gfx_shell_set_geometry(self.ctx.h, C.c_void_p(stream), self.h, arr, C.c_uint32(len(keep))))
+
+    def trace(self, mode, d_ray_org, d_ray_dir, num_rays, d_out, d_counters=0, stream=0):
+        """CLOSEST: d_out = SHELL_HIT_DTYPE[num_rays]; ANY: uint32[num_rays].  d_counters: device u64[4], added to."""
+        self.ctx._check(self.L.gfx_shell_trace(self.ctx.h, C.c_void_p(stream), self.h, C.c_int(mode), C.c_void_p(d_ray_org), C.c_void_p(d_ray_dir),
+                                               C.c_uint32(num_rays), C.c_void_p(d_out), C.c_void_p(d_counters or None)))
+
+    def size_of(self, what):
+        n = C.c_size_t()
+        self.ctx._check(self.L.gfx_shell_size(self.ctx.h, self.h, C.c_int(what), C.byref(n)))
+        return n.value
+
+    def device_bytes(self):
+        return self.size_of(-1)
+
+    def _read(self, what, dtype):
+        out = np.zeros(self.size_of(what), np.uint8)
+        self.ctx._check(self.L.gfx_shell_read(self.ctx.h, self.h, C.c_int(what), _p(out), C.c_size_t(out.nbytes)))
+        return out.view(dtype)
+
+    def read_aabbs(self):
+        return self._read(TFDM_READ_AABBS, np.float32).reshape(-1, 6)
+
+    def read_records(self):
+        return self._read(TFDM_READ_RECORDS, NRTDSM_RECORD_DTYPE)
+
+    def read_nodes(self):
+        return self._read(TFDM_READ_NODES, TFDM_NODE_DTYPE)
+
+    def read_shell_nodes(self):
+        return self._read(SHELL_READ_SHELL_NODES, TFDM_NODE_DTYPE)
+
+    def read_shell_triangles(self):
+        return self._read(SHELL_READ_SHELL_TRIANGLES, SHELL_TRI_DTYPE)
+
+    def close(self):
+        if self.h:
+            self.L.gfx_shell_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

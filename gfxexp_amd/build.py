@@ -19,8 +19,8 @@ LIB = os.path.join(HERE, "libgfxexp.so")
 CLI = os.path.join(HERE, "restir_di_headless")       # host/restir_di_headless.cpp: the reference's command line, windowless
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-SOURCES = ["capi.cpp", "scene.cpp", "lights.hip", "lights_sample.hip", "math_eval.hip", "bsdf_eval.hip", "lbvh.hip", "trace.hip", "restir.hip", "pathtrace.hip", "nrc.hip", "textures.hip", "diag.hip", "denoise/denoise.hip", "denoise/taa.hip", "bc/bc_expand.hip", "tfdm/tfdm.hip", "tfdm/tfdm_set.hip", "nrtdsm/nrtdsm.hip",
-           "host/scene_builder.cpp", "host/image_formats.cpp", "host/image_codecs.cpp", "host/obj_loader.cpp", "host/street_scene.cpp", "host/env_tables.cpp", "host/image_output.cpp", "host/restir_driver.cpp", "host/nrc_driver.cpp", "host/rccl_exchange.cpp", "host/abi_layout.cpp"]
+SOURCES = ["capi.cpp", "scene.cpp", "lights.hip", "lights_sample.hip", "math_eval.hip", "bsdf_eval.hip", "lbvh.hip", "trace.hip", "restir.hip", "pathtrace.hip", "nrc.hip", "textures.hip", "diag.hip", "denoise/denoise.hip", "denoise/taa.hip", "bc/bc_expand.hip", "tfdm/tfdm.hip", "tfdm/tfdm_set.hip", "nrtdsm/nrtdsm.hip", "nrtdsm/shell.hip",
+           "host/scene_builder.cpp", "host/image_formats.cpp", "host/image_codecs.cpp", "host/obj_loader.cpp", "host/street_scene.cpp", "host/env_tables.cpp", "host/image_output.cpp", "host/restir_driver.cpp", "host/nrc_driver.cpp", "host/rccl_exchange.cpp", "host/abi_layout.cpp", "host/shell_shapes.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-fno-slp-vectorize", "-Wall", "-Wno-unused-function",
          "-I" + os.path.join(HERE, "..", "include")]

@@ -14,6 +14,7 @@
 #include "tfdm/tfdm.h"
 #include "tfdm/tfdm_set.h"
 #include "nrtdsm/nrtdsm.h"
+#include "nrtdsm/shell.h"
 
 using namespace gfx;
 
@@ -26,6 +27,7 @@ struct gfx_taa { TemporalAA t; };
 struct gfx_tfdm { TfdmObject o; };
 struct gfx_tfdm_set { TfdmSet s; gfx_ctx* ctx; };
 struct gfx_nrtdsm { NrtdsmObject o; };
+struct gfx_shell { ShellObject o; };
 
 static thread_local std::string g_createError;
 
@@ -849,6 +851,66 @@ int gfx_nrtdsm_size(gfx_ctx* ctx, gfx_nrtdsm* obj, int what, uint32_t level, siz
     GFX_TRY(ctx)
     if (!obj || !bytes) throw HipError("gfx_nrtdsm_size: null object or output");
     *bytes = nrtdsm_size(obj->o, what, level);
+    GFX_CATCH(ctx)
+}
+
+int gfx_shell_create(gfx_ctx* ctx, void* stream, const void* vertices, uint32_t stride, uint32_t numVertices, const uint32_t* triangles, uint32_t numTriangles,
+                     const gfx_shell_geom* geoms, uint32_t numGeoms, const gfx_tfdm_params* params, gfx_shell** out) {
+    GFX_TRY(ctx)
+    if (!out) throw HipError("gfx_shell_create: null output handle");
+    *out = nullptr;
+    gfx_tfdm_params p;
+    if (params) p = *params;
+    else { tfdm_default_params(&p); p.localIntersection = 0u; }
+    std::unique_ptr<gfx_shell> t(new gfx_shell());
+    t->o.device = ctx->c.device;
+    try { shell_init(t->o, static_cast<hipStream_t>(stream), vertices, stride, numVertices, triangles, numTriangles, geoms, numGeoms, p); }
+    catch (...) { shell_release(t->o); throw; }
+    *out = t.release();
+    GFX_CATCH(ctx)
+}
+int gfx_shell_set_params(gfx_ctx* ctx, void* stream, gfx_shell* obj, const gfx_tfdm_params* params) {
+    GFX_TRY(ctx)
+    if (!obj || !params) throw HipError("gfx_shell_set_params: null object or parameters");
+    if (obj->o.device != ctx->c.device) throw HipError("gfx_shell_set_params: the object belongs to another device");
+    shell_set_params(obj->o, static_cast<hipStream_t>(stream), *params);
+    GFX_CATCH(ctx)
+}
+int gfx_shell_set_geometry(gfx_ctx* ctx, void* stream, gfx_shell* obj, const gfx_shell_geom* geoms, uint32_t numGeoms) {
+    GFX_TRY(ctx)
+    if (!obj) throw HipError("gfx_shell_set_geometry: null object");
+    if (obj->o.device != ctx->c.device) throw HipError("gfx_shell_set_geometry: the object belongs to another device");
+    shell_set_geometry(obj->o, static_cast<hipStream_t>(stream), geoms, numGeoms);
+    GFX_CATCH(ctx)
+}
+int gfx_shell_destroy(gfx_shell* obj) {
+    if (!obj) return 1;
+    int prev = -1;
+    const bool switched = hipGetDevice(&prev) == hipSuccess && prev != obj->o.device && hipSetDevice(obj->o.device) == hipSuccess;
+    (void)hipDeviceSynchronize();
+    shell_release(obj->o);
+    if (switched) (void)hipSetDevice(prev);
+    delete obj;
+    return 0;
+}
+int gfx_shell_trace(gfx_ctx* ctx, void* stream, gfx_shell* obj, int mode, const void* dRayOrgTmin, const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters) {
+    GFX_TRY(ctx)
+    if (!obj) throw HipError("gfx_shell_trace: null object");
+    if (obj->o.device != ctx->c.device) throw HipError("gfx_shell_trace: the object belongs to another device");
+    ScopedKernelTimer timer(ctx->c, static_cast<hipStream_t>(stream), "k_shell_trace");
+    shell_trace(obj->o, static_cast<hipStream_t>(stream), mode, dRayOrgTmin, dRayDirTmax, numRays, dOut, dCounters);
+    GFX_CATCH(ctx)
+}
+int gfx_shell_read(gfx_ctx* ctx, gfx_shell* obj, int what, void* hostOut, size_t bytes) {
+    GFX_TRY(ctx)
+    if (!obj) throw HipError("gfx_shell_read: null object");
+    shell_read(obj->o, what, hostOut, bytes);
+    GFX_CATCH(ctx)
+}
+int gfx_shell_size(gfx_ctx* ctx, gfx_shell* obj, int what, size_t* bytes) {
+    GFX_TRY(ctx)
+    if (!obj || !bytes) throw HipError("gfx_shell_size: null object or output");
+    *bytes = shell_size(obj->o, what);
     GFX_CATCH(ctx)
 }
 

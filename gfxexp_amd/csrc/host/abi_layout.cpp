@@ -34,6 +34,9 @@ const Field kFields[] = {
     S(gfx_tfdm_params), F(gfx_tfdm_params, hOffset), F(gfx_tfdm_params, hScale), F(gfx_tfdm_params, hBias), F(gfx_tfdm_params, texScale), F(gfx_tfdm_params, texRotation),
     F(gfx_tfdm_params, texOffset), F(gfx_tfdm_params, targetMipLevel), F(gfx_tfdm_params, localIntersection),
     S(gfx_tfdm_hit), F(gfx_tfdm_hit, dist), F(gfx_tfdm_hit, bcB), F(gfx_tfdm_hit, bcC), F(gfx_tfdm_hit, primIndex), F(gfx_tfdm_hit, normal), F(gfx_tfdm_hit, frontFace),
+    S(gfx_shell_hit), F(gfx_shell_hit, dist), F(gfx_shell_hit, bcB), F(gfx_shell_hit, bcC), F(gfx_shell_hit, primIndex), F(gfx_shell_hit, normal), F(gfx_shell_hit, frontFace),
+    F(gfx_shell_hit, shellTriangle), F(gfx_shell_hit, shellGeom), F(gfx_shell_hit, tile),
+    S(gfx_shell_geom), F(gfx_shell_geom, positions), F(gfx_shell_geom, stride), F(gfx_shell_geom, numVertices), F(gfx_shell_geom, triangles), F(gfx_shell_geom, numTriangles),
     S(gfx_scene_hit), F(gfx_scene_hit, dist), F(gfx_scene_hit, bcB), F(gfx_scene_hit, bcC), F(gfx_scene_hit, index), F(gfx_scene_hit, normal), F(gfx_scene_hit, where),
     S(gfx_restir_static_params), F(gfx_restir_static_params, imageSizeX), F(gfx_restir_static_params, imageSizeY), F(gfx_restir_static_params, rngBuffer),
     F(gfx_restir_static_params, gbuffer0), F(gfx_restir_static_params, gbuffer1), F(gfx_restir_static_params, gbuffer2), F(gfx_restir_static_params, gbuffer3),

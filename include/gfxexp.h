@@ -868,6 +868,45 @@ int gfx_nrtdsm_trace(gfx_ctx* ctx, void* stream, gfx_nrtdsm* obj, int mode, cons
 int gfx_nrtdsm_read(gfx_ctx* ctx, gfx_nrtdsm* obj, int what, uint32_t level, void* hostOut, size_t bytes);
 int gfx_nrtdsm_size(gfx_ctx* ctx, gfx_nrtdsm* obj, int what, uint32_t level, size_t* bytes);
 
+/* ---------------------------------------------------------------- shell mapping (the other half of NRTDSM) ----------------
+ * A third ray query on a base mesh.  A small triangle mesh, the shell mesh, is authored once in the tile
+ * [0, 1]^2 x [hLo, hHi] of shell space (u, v, h) and repeated over the base mesh like a texture: tile (i, j), for any integers,
+ * holds a copy shifted by (i, j, 0).  A shell-space point lies at S = P + (hOffset - s hBias + s h) N with s, P and N as for
+ * gfx_nrtdsm_* and (u, v) the base mesh's texture coordinates after the texture transform.  Nothing is instantiated: the object
+ * owns one BVH over the shell mesh (32-byte nodes, 48-byte triangles) and 144 bytes, a box and two tree nodes per base triangle.
+ * positions of a gfx_shell_geom are (u, v, h) floats `stride` bytes apart; up to 8 geometries, 2^20 triangles in all.
+ * create and set_geometry refuse, with a message and leaving an existing object unchanged: no triangles or more than 2^20; more
+ * than 8 geometries; a vertex that is not finite or has u or v outside [0, 1]; an index beyond numVertices.  A flat shell mesh
+ * (every h equal, 0 included) is a decal and is accepted.  params: targetMipLevel and localIntersection must be 0; the other
+ * refusals are gfx_nrtdsm_*'s, with 2^22 tiles in place of 2^24 texels.  params == NULL: hOffset 0, hScale 1, hBias 0, unit
+ * texture transform. */
+typedef struct gfx_shell gfx_shell;                     /* opaque; owns records, AABBs, the base tree, shell nodes and triangles */
+typedef struct gfx_shell_geom { const float* positions; uint32_t stride, numVertices; const uint32_t* triangles; uint32_t numTriangles; } gfx_shell_geom;
+/* closest-hit record of gfx_shell_trace, 48 B.  The first 32 bytes are a gfx_tfdm_hit: bcB / bcC are barycentrics on the BASE
+ * triangle primIndex; normal is the unit object-space normal of the mapped shell triangle at the hit, on the side its winding
+ * faces in shell space ((u, v, h) right-handed) whatever the base triangle's parametrisation; frontFace = dot(dir, normal) < 0.
+ * shellTriangle indexes the concatenation of the geometries in the order given, shellGeom is its geometry, tile the copy that
+ * was hit.  Miss: as gfx_tfdm_hit, the new fields zero. */
+typedef struct gfx_shell_hit { float dist, bcB, bcC; uint32_t primIndex; float normal[3]; uint32_t frontFace;
+                               uint32_t shellTriangle, shellGeom; int32_t tile[2]; } gfx_shell_hit;
+int gfx_shell_create(gfx_ctx* ctx, void* stream, const void* vertices, uint32_t stride, uint32_t numVertices,
+                     const uint32_t* triangles, uint32_t numTriangles, const gfx_shell_geom* geoms, uint32_t numGeoms,
+                     const gfx_tfdm_params* params, gfx_shell** out);
+int gfx_shell_set_params(gfx_ctx* ctx, void* stream, gfx_shell* obj, const gfx_tfdm_params* params);
+/* Another shell mesh over the same base mesh and parameters.  A refused call leaves the object as it was. */
+int gfx_shell_set_geometry(gfx_ctx* ctx, void* stream, gfx_shell* obj, const gfx_shell_geom* geoms, uint32_t numGeoms);
+int gfx_shell_destroy(gfx_shell* obj);
+/* As gfx_nrtdsm_trace; GFX_TRACE_CLOSEST: dOut = gfx_shell_hit[numRays], 16-byte aligned.  The counters: box tests (squares of
+ * tiles and shell nodes), leaf tests (shell triangles), rays, base triangles tested. */
+int gfx_shell_trace(gfx_ctx* ctx, void* stream, gfx_shell* obj, int mode, const void* dRayOrgTmin, const void* dRayDirTmax,
+                    uint32_t numRays, void* dOut, void* dCounters);
+/* Inspection: GFX_TFDM_READ_AABBS, _RECORDS (144 bytes each, csrc/nrtdsm/nrtdsm_core.hip.h; the root fields are tiles) and _NODES
+ * (the tree over the base triangles' boxes) as for gfx_nrtdsm_read, and the shell BVH's 32-byte nodes and 48-byte triangles
+ * (csrc/nrtdsm/shell_core.hip.h).  what = -1 in gfx_shell_size: the device bytes the object owns in all. */
+enum gfx_shell_read_what { GFX_SHELL_READ_SHELL_NODES = 5, GFX_SHELL_READ_SHELL_TRIANGLES = 6 };
+int gfx_shell_read(gfx_ctx* ctx, gfx_shell* obj, int what, void* hostOut, size_t bytes);
+int gfx_shell_size(gfx_ctx* ctx, gfx_shell* obj, int what, size_t* bytes);
+
 /* ---------------------------------------------------------------- plain and displaced instances in one query -------------
  * A set of displaced instances: gfx_tfdm objects under object-to-world transforms (row-major 3 x 4, as
  * gfx_instance_set_transform takes them), at most 1024.  One object may be added many times; objects and the context must

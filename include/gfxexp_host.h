@@ -93,6 +93,15 @@ int gfxh_image_decode_rgba8(const void* data, size_t bytes, void* out, size_t ca
 int gfxh_tfdm_load_height(const char* path, uint32_t* size, float** heights);
 void gfxh_tfdm_free_height(float* heights);
 
+/* Shell meshes for gfx_shell_create.  gfxh_shell_fit places `n` points (x, y, z floats, tightly packed) in the unit tile as the
+ * reference does (nrtdsm_main.cpp:835-845): with yUp the points are first turned by +90 degrees about x ((x, y, z) -> (x, -z, y));
+ * then xy is centred on 0.5 and everything is scaled by 1 / max(dx, dy), and the lowest z goes to 0.  out: 3 n floats (u, v, h);
+ * may be `positions`.  Returns 1 with a gfxh_last_error for no points, a point that is not finite, or dx = dy = 0.
+ * gfxh_shell_box writes the reference's "One Box" (nrtdsm_main.cpp:778-798): 8 vertices, 0.2 .. 0.8 in u and v, h 0 .. 0.08, into
+ * positions[24], and its 12 triangles, facing outward, into triangles[36]. */
+int gfxh_shell_fit(const float* positions, uint32_t n, int yUp, float* out);
+int gfxh_shell_box(float* positions, uint32_t* triangles);
+
 /* Geometry / groups / instances (return slot indices). */
 uint32_t gfxh_scene_add_geom(gfxh_scene* s, const gfx_vertex* v, uint32_t nv, const uint32_t* tris, uint32_t nt, uint32_t matSlot);
 uint32_t gfxh_scene_add_group(gfxh_scene* s, const uint32_t* geomSlots, uint32_t n);

@@ -8,6 +8,9 @@ tessellated to 2 x size x size triangles.  Per variant: microseconds per launch 
 warm-up), Mrays/s, texel AABB tests / leaf tests / base triangles per ray from a counting launch of its own, and the device bytes
 of either representation.  Beside them the crack-free NRTDSM query (gfx_nrtdsm_trace, "nrtdsm") on the same mesh, map and rays, with
 its own device bytes.  --variants: only these (two_triangle_l0, box_l2, bilinear_l0, nrtdsm, ...), for a library that lacks one.
+Shell mapping (gfx_shell_trace): the steps shell_box and shell_bunny trace the "One Box" and the 309-face bunny as shell meshes at
+--tiles x --tiles (64) tiles on the quad, and the same tiles instantiated as ordinary triangles through gfx_trace on the same rays,
+with the device bytes of either.  --steps: only these steps (tfdm_quad, tfdm_teapot, mesh_quad, shell_box, shell_bunny).
 Prints one JSON line.
 
 Every GPU step is a child process of its own under a time limit (--step-timeout seconds); the first step that fails or runs out of
@@ -23,7 +26,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
-STEPS = ["tfdm_quad", "tfdm_teapot", "mesh_quad"]
+STEPS = ["tfdm_quad", "tfdm_teapot", "mesh_quad", "shell_box", "shell_bunny"]
 VARIANTS = [("two_triangle_l0", 1, 0), ("two_triangle_l2", 1, 2), ("box_l0", 0, 0), ("box_l2", 0, 2), ("bilinear_l0", 4, 0), ("bilinear_l2", 4, 2)]
 
 
@@ -44,10 +47,57 @@ def timed(fn, iters, warmup=3):
     return a.elapsed_time(b) * 1e-3 / iters
 
 
-def step(name, size, iters, w, h, only=None):
+def shell_step(name, tiles, iters, w, h):
+    """gfx_shell_trace on the quad against gfx_trace on the same tiles instantiated as ordinary triangles."""
     import torch
     from gfxexp_amd import api
     import tfdm_common as K
+    v, t, pos, target, up = K.base_mesh("quad")
+    geom = K.shell_geom("box" if name == "shell_box" else "bunny")
+    h_scale = 6.0 if name == "shell_box" else 1.0        # at 64 tiles: a box half a tile high, a bunny one tile high
+    org, dirs = api.camera_rays(K.look_at_camera(w, h, pos, target, up=up), w, h)
+    n = w * h
+    d_org, d_dir = torch.from_numpy(org).cuda(), torch.from_numpy(dirs).cuda()
+    d_out = torch.zeros(n * 12, dtype=torch.int32, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    ctx = api.Context(0)
+    sh = api.Shell(ctx, v, t, [geom], api.shell_params(h_scale=h_scale, tex_scale=(float(tiles), float(tiles))))
+    secs = timed(lambda: sh.trace(api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), stream=stream), iters)
+    hits = d_out.cpu().numpy().view(api.SHELL_HIT_DTYPE)[:n]
+    d_cnt = torch.zeros(4, dtype=torch.int64, device="cuda")
+    sh.trace(api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), d_cnt.data_ptr(), stream=stream)
+    torch.cuda.synchronize()
+    cnt = d_cnt.cpu().numpy()
+    shell_hit = hits["primIndex"] != api.GFX_INVALID_SLOT
+    out = {"tiles": tiles, "shell_triangles": int(len(geom[1])), "rays": n,
+           "shell": {"us": round(secs * 1e6, 1), "Mrays_per_s": round(n / secs / 1e6, 1), "hit_share": round(float(shell_hit.mean()), 4),
+                     "box_tests_per_ray": round(float(cnt[0]) / n, 2), "leaf_tests_per_ray": round(float(cnt[1]) / n, 2),
+                     "base_triangles_per_ray": round(float(cnt[3]) / n, 2), "device_bytes": sh.device_bytes()}}
+    sh.close()
+    mv, mt = K.instantiated_shell_on_quad(geom, tiles, h_scale)
+    s = api.HostScene()
+    g = s.add_geom(mv, mt, s.add_material_traditional((0.5, 0.5, 0.5), (0, 0, 0), 0.3))
+    s.add_instance(s.add_group([g]), api.make_transform())
+    s.upload(ctx)
+    accel = ctx.accel_build()
+    st = ctx.accel_stats(accel)
+    d_hit = torch.zeros(n * 8, dtype=torch.int32, device="cuda")
+    secs = timed(lambda: ctx.trace(accel, api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_hit.data_ptr(), stream=stream), iters)
+    mesh_hit = d_hit.cpu().numpy().view(api.HIT_DTYPE)[:n]["triIndex"] != api.GFX_INVALID_SLOT
+    out["mesh"] = {"triangles": int(len(mt)), "us": round(secs * 1e6, 1), "Mrays_per_s": round(n / secs / 1e6, 1), "hit_share": round(float(mesh_hit.mean()), 4),
+                   "bvh_bytes": int(st["nodes"] * (64 + 16) + st["triRecords"] * (64 + 12)), "scene_geometry_bytes": int(mv.nbytes + mt.nbytes)}
+    out["hit_or_miss_differs_share"] = round(float((mesh_hit != shell_hit).mean()), 6)
+    out["memory_ratio_mesh_over_shell"] = round((out["mesh"]["bvh_bytes"] + out["mesh"]["scene_geometry_bytes"]) / out["shell"]["device_bytes"], 1)
+    out["time_ratio_shell_over_mesh"] = round(out["shell"]["us"] / out["mesh"]["us"], 2)
+    return out
+
+
+def step(name, size, iters, w, h, only=None, tiles=64):
+    import torch
+    from gfxexp_amd import api
+    import tfdm_common as K
+    if name.startswith("shell_"):
+        return shell_step(name, tiles, iters, w, h)
     heights = K.procedural_map(size)
     mesh = "teapot" if name == "tfdm_teapot" else "quad"
     v, t, pos, target, up = K.base_mesh(mesh)
@@ -124,14 +174,15 @@ def main(argv):
     size, iters = _arg(argv, "--size", 1024), _arg(argv, "--iters", 20)
     w, h = _arg(argv, "--width", 1920), _arg(argv, "--height", 1080)
     only = _arg(argv, "--variants", "")
+    tiles, steps = _arg(argv, "--tiles", 64), _arg(argv, "--steps", "")
     if "--step" in argv:
-        print("STEP_RESULT " + json.dumps(step(argv[argv.index("--step") + 1], size, iters, w, h, only.split(",") if only else None)))
+        print("STEP_RESULT " + json.dumps(step(argv[argv.index("--step") + 1], size, iters, w, h, only.split(",") if only else None, tiles)))
         return 0
     limit = _arg(argv, "--step-timeout", 300)
     result = {"metric": "tfdm_trace", "size": size, "iters": iters, "width": w, "height": h}
-    for name in STEPS:
+    for name in (steps.split(",") if steps else STEPS):
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name, "--size", str(size), "--iters", str(iters),
-               "--width", str(w), "--height", str(h)] + (["--variants", only] if only else [])
+               "--width", str(w), "--height", str(h), "--tiles", str(tiles)] + (["--variants", only] if only else [])
         r = subprocess.run(cmd, capture_output=True, text=True)
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("STEP_RESULT ")]
         if r.returncode != 0 or not line:
@@ -139,8 +190,8 @@ def main(argv):
             print(json.dumps(result))
             return 1
         result[name] = json.loads(line[-1][len("STEP_RESULT "):])
-    q, m = result["tfdm_quad"], result["mesh_quad"]
-    if "device_bytes" in q:
+    q, m = result.get("tfdm_quad", {}), result.get("mesh_quad", {})
+    if "device_bytes" in q and m:
         result["memory_ratio_mesh_over_tfdm"] = round((m["bvh_bytes"] + m["scene_geometry_bytes"]) / q["device_bytes"], 2)
     print(json.dumps(result))
     return 0

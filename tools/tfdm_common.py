@@ -88,6 +88,31 @@ def tessellated_quad(heights, h_scale):
     return v, t
 
 
+def shell_geom(name):
+    """A shell mesh for api.Shell: (positions [n, 3] as (u, v, h), triangles [m, 3]); "box" (gfxh_shell_box) or "bunny" (the
+    309-face bunny through gfxh_shell_fit, Y up)."""
+    if name == "box":
+        return api.shell_box()
+    v, t = obj_mesh("stanford_bunny_309_faces.obj")
+    return api.shell_fit(v["position"], y_up=True), t
+
+
+def instantiated_shell_on_quad(geom, tiles, h_scale):
+    """The shell mesh `geom` repeated tiles x tiles times over quad_mesh() as ordinary triangles (indexed: one copy of the shell's
+    vertices per tile), in float64: what gfx_shell_trace intersects there with tex_scale = (tiles, tiles), since the map is affine on
+    the quad.  A shell height h lies at z = h_scale / tiles * h."""
+    pos, tri = np.asarray(geom[0], np.float64), np.asarray(geom[1], np.int64)
+    j, i = np.mgrid[0:tiles, 0:tiles]
+    shift = np.stack([i.ravel(), j.ravel(), np.zeros(tiles * tiles)], 1)                      # [tiles^2, 3]
+    p = (pos[None] + shift[:, None]) * np.array([1.0 / tiles, 1.0 / tiles, h_scale / tiles])
+    v = np.zeros(len(shift) * len(pos), api.VERTEX_DTYPE)
+    v["position"] = p.reshape(-1, 3)
+    v["normal"] = (0, 0, 1)
+    v["texCoord0Dir"] = (1, 0, 0)
+    t = (tri[None] + (np.arange(len(shift)) * len(pos))[:, None, None]).reshape(-1, 3).astype(np.uint32)
+    return v, t
+
+
 def affine(linear, translation):
     """Row-major 3 x 4 float32 from a 3 x 3 linear part and a translation."""
     m = np.zeros((3, 4), np.float64)

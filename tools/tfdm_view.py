@@ -14,6 +14,13 @@ prints the hit share and the traversal counters per ray.
 --nrtdsm: the same images through gfx_nrtdsm_trace, the crack-free query that displaces along the interpolated, not renormalised normals
 (csrc/nrtdsm/); the teapot unless --mesh says otherwise.  Map values must lie in [0, 1].
 
+    python tools/tfdm_view.py --shell [box|bunny] [--mesh quad|bunny|teapot] [--tiles 16] [--scale 0.5] [--out tfdm_view]
+
+--shell: a shell mesh (the "One Box", or the 309-face bunny placed by gfxh_shell_fit) repeated --tiles times per unit of texture
+coordinate over the base mesh, through gfx_shell_trace (csrc/nrtdsm/shell*).  --scale: the height of one unit of shell height in
+tiles.  Writes <out>_normal.png, <out>_depth.png and <out>_geom.png (the shell geometry index as a colour, tiles alternating in
+brightness like a checkerboard).
+
     python tools/tfdm_view.py --scene [--size 256] [--width 960] [--height-px 540] [--out tfdm_view]
 
 --scene: a plain teapot on a displaced ground quad with a second displaced quad as a tilted wall (tfdm_common.mixed_scene), through
@@ -174,6 +181,43 @@ def scene_view(a):
     return 0
 
 
+def shell_view(a):
+    v, t, pos, target, up = K.base_mesh(a.mesh)
+    geom = K.shell_geom(a.shell)
+    # one unit of shell height is --scale tiles high: s = hScale / tiles
+    gp = api.shell_params(h_scale=a.scale * K.extent(v), tex_scale=(a.tiles, a.tiles), tex_rotation=a.rotation)
+    ctx = api.Context(0)
+    sh = api.Shell(ctx, v, t, [geom], gp)
+    w, h = a.width, a.height_px
+    n = w * h
+    org, dirs = api.camera_rays(K.look_at_camera(w, h, pos, target, up=up), w, h)
+    d_org, d_dir = torch.from_numpy(org).cuda(), torch.from_numpy(dirs).cuda()
+    d_out = torch.zeros(n * 12, dtype=torch.int32, device="cuda")
+    d_cnt = torch.zeros(4, dtype=torch.int64, device="cuda")
+    sh.trace(api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), d_cnt.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    hits = d_out.cpu().numpy().view(api.SHELL_HIT_DTYPE)
+    cnt = d_cnt.cpu().numpy()
+    hit = hits["primIndex"] != api.GFX_INVALID_SLOT
+    sdr = api.sdr_config(brightness=1.0, tone_map=False, gamma=False)
+    img = np.zeros((n, 4), np.float32)
+    img[:, 3] = 1
+    img[hit, :3] = hits["normal"][hit] * 0.5 + 0.5
+    api.save_image_sdr(a.out + "_normal.png", img, w, h, sdr)
+    api.save_image_sdr(a.out + "_depth.png", _depth_image(hits["dist"], hit, n), w, h, sdr)
+    palette = np.array([(0.9, 0.3, 0.2), (0.2, 0.6, 0.9), (0.3, 0.8, 0.3), (0.9, 0.8, 0.2), (0.7, 0.3, 0.8), (0.2, 0.8, 0.8), (0.8, 0.5, 0.2), (0.5, 0.5, 0.9)], np.float32)
+    ids = np.zeros((n, 4), np.float32)
+    ids[:, 3] = 1
+    checker = 0.6 + 0.4 * ((hits["tile"][hit, 0] + hits["tile"][hit, 1]) & 1)
+    ids[hit, :3] = palette[hits["shellGeom"][hit] % len(palette)] * checker[:, None]
+    api.save_image_sdr(a.out + "_geom.png", ids, w, h, sdr)
+    print(json.dumps({"query": "shell", "shell": a.shell, "mesh": a.mesh, "tiles": a.tiles, "shell_triangles": int(len(geom[1])), "triangles": int(len(t)), "rays": n,
+                      "hit_share": round(float(hit.mean()), 4), "box_tests_per_ray": round(float(cnt[0]) / n, 2), "leaf_tests_per_ray": round(float(cnt[1]) / n, 2),
+                      "base_triangles_per_ray": round(float(cnt[3]) / n, 2), "device_bytes": sh.device_bytes(),
+                      "images": [a.out + "_normal.png", a.out + "_depth.png", a.out + "_geom.png"]}))
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mesh", default=None, choices=["quad", "bunny", "teapot"])      # the quad; with --nrtdsm the teapot
@@ -190,6 +234,8 @@ def main():
     ap.add_argument("--height-px", type=int, default=540)
     ap.add_argument("--out", default="tfdm_view")
     ap.add_argument("--nrtdsm", action="store_true")
+    ap.add_argument("--shell", nargs="?", const="box", default=None, choices=["box", "bunny"])
+    ap.add_argument("--tiles", type=float, default=16.0)
     ap.add_argument("--scene", action="store_true")
     ap.add_argument("--render", action="store_true")
     ap.add_argument("--restir", action="store_true")
@@ -205,6 +251,10 @@ def main():
         return scene_render(a)
     if a.scene:
         return scene_view(a)
+    if a.shell:
+        if "--scale" not in sys.argv:
+            a.scale = 0.5
+        return shell_view(a)
     heights = api.tfdm_load_height(a.height) if a.height else K.procedural_map(a.size)
     v, t, pos, target, up = K.base_mesh(a.mesh)
     gp = api.tfdm_params(h_scale=a.scale * K.extent(v), tex_scale=(a.tex_scale, a.tex_scale), tex_rotation=a.rotation, target_mip_level=a.level,
