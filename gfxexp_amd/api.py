@@ -1304,69 +1304,63 @@ def tfdm_load_height(path):
         lib().gfxh_tfdm_free_height(ptr)
 
 
-class Tfdm:
-    """gfx_tfdm: a base mesh displaced by a height map, queried by rays without tessellation (csrc/tfdm/).  vertices: VERTEX_DTYPE
-    array; triangles: [n, 3] uint32; heights: one float32 [size, size] array (the library makes the mips) or the list of all
-    log2(size) + 1 levels.  Rays and results are device pointers (ints), in the layout of Context.trace."""
+class _DisplacedObject:
+    """What Tfdm, Nrtdsm and Shell share: the handle and its lifetime, and the calls every displaced-surface query of the library
+    has under its own prefix (csrc/tfdm/displaced_object.h is the same layer on the C++ side)."""
 
-    def __init__(self, ctx, vertices, triangles, heights, params=None, stream=0):
+    _PREFIX = None      # of the C functions: "gfx_tfdm_", "gfx_nrtdsm_", "gfx_shell_"
+
+    def _call(self, name, *args):
+        self.ctx._check(getattr(self.L, self._PREFIX + name)(*args))
+
+    def _create(self, ctx, vertices, triangles, surface, params, stream):
+        """surface: the arguments of gfx_*_create between the base mesh and the parameters"""
         self.L = lib()
         self.ctx = ctx
         v = np.ascontiguousarray(vertices, VERTEX_DTYPE)
         t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
-        levels = [heights] if isinstance(heights, np.ndarray) else list(heights)
-        levels = [np.ascontiguousarray(a, np.float32) for a in levels]
-        if not levels or levels[0].ndim != 2 or levels[0].shape[0] != levels[0].shape[1]:
-            raise GfxError("Tfdm: the height map must be square (gfx_tfdm_create takes one size)")
-        self.size = int(levels[0].shape[0])
-        ptrs = (C.POINTER(C.c_float) * len(levels))(*[a.ctypes.data_as(C.POINTER(C.c_float)) for a in levels])
         h = C.c_void_p()
-        ctx._check(self.L.gfx_tfdm_create(ctx.h, C.c_void_p(stream), _p(v), C.c_uint32(v.itemsize), C.c_uint32(len(v)), _p(t), C.c_uint32(len(t)),
-                                          ptrs, C.c_uint32(len(levels)), C.c_uint32(self.size), C.byref(params) if params is not None else None, C.byref(h)))
+        self._call("create", ctx.h, C.c_void_p(stream), _p(v), C.c_uint32(v.itemsize), C.c_uint32(len(v)), _p(t), C.c_uint32(len(t)),
+                   *surface, C.byref(params) if params is not None else None, C.byref(h))
         self.h = h
         self.num_triangles = len(t)
 
     def set_params(self, params, stream=0):
-        self.ctx._check(self.L.gfx_tfdm_set_params(self.ctx.h, C.c_void_p(stream), self.h, C.byref(params)))
+        self._call("set_params", self.ctx.h, C.c_void_p(stream), self.h, C.byref(params))
 
     def trace(self, mode, d_ray_org, d_ray_dir, num_rays, d_out, d_counters=0, stream=0):
-        """CLOSEST: d_out = TFDM_HIT_DTYPE[num_rays]; ANY: uint32[num_rays].  d_counters: device u64[4], added to."""
-        self.ctx._check(self.L.gfx_tfdm_trace(self.ctx.h, C.c_void_p(stream), self.h, C.c_int(mode), C.c_void_p(d_ray_org), C.c_void_p(d_ray_dir),
-                                              C.c_uint32(num_rays), C.c_void_p(d_out), C.c_void_p(d_counters or None)))
+        """CLOSEST: d_out = TFDM_HIT_DTYPE[num_rays] (a Shell's: SHELL_HIT_DTYPE); ANY: uint32[num_rays].  d_counters: device u64[4], added to."""
+        self._call("trace", self.ctx.h, C.c_void_p(stream), self.h, C.c_int(mode), C.c_void_p(d_ray_org), C.c_void_p(d_ray_dir),
+                   C.c_uint32(num_rays), C.c_void_p(d_out), C.c_void_p(d_counters or None))
 
-    def size_of(self, what, level=0):
+    def _level(self, level):
+        return ()       # the level argument of gfx_*_size and gfx_*_read: only an object with a height map has one
+
+    def _size(self, what, level=0):
         n = C.c_size_t()
-        self.ctx._check(self.L.gfx_tfdm_size(self.ctx.h, self.h, C.c_int(what), C.c_uint32(level), C.byref(n)))
+        self._call("size", self.ctx.h, self.h, C.c_int(what), *self._level(level), C.byref(n))
         return n.value
+
+    def size_of(self, what):
+        return self._size(what)
 
     def device_bytes(self):
         return self.size_of(-1)
 
-    def _read(self, what, level, dtype):
-        out = np.zeros(self.size_of(what, level), np.uint8)
-        self.ctx._check(self.L.gfx_tfdm_read(self.ctx.h, self.h, C.c_int(what), C.c_uint32(level), _p(out), C.c_size_t(out.nbytes)))
+    def _read(self, what, dtype, level=0):
+        out = np.zeros(self._size(what, level), np.uint8)
+        self._call("read", self.ctx.h, self.h, C.c_int(what), *self._level(level), _p(out), C.c_size_t(out.nbytes))
         return out.view(dtype)
 
-    def read_pyramid(self, level):
-        w = self.size >> level
-        return self._read(TFDM_READ_PYRAMID, level, np.float32).reshape(w, w, 2)
-
-    def read_heights(self, level):
-        w = self.size >> level
-        return self._read(TFDM_READ_HEIGHTS, level, np.float32).reshape(w, w)
-
     def read_aabbs(self):
-        return self._read(TFDM_READ_AABBS, 0, np.float32).reshape(-1, 6)
-
-    def read_records(self):
-        return self._read(TFDM_READ_RECORDS, 0, np.uint8).reshape(-1, TFDM_RECORD_BYTES)
+        return self._read(TFDM_READ_AABBS, np.float32).reshape(-1, 6)
 
     def read_nodes(self):
-        return self._read(TFDM_READ_NODES, 0, TFDM_NODE_DTYPE)
+        return self._read(TFDM_READ_NODES, TFDM_NODE_DTYPE)
 
     def close(self):
         if self.h:
-            self.L.gfx_tfdm_destroy(self.h)
+            getattr(self.L, self._PREFIX + "destroy")(self.h)
             self.h = None
 
     def __del__(self):
@@ -1374,6 +1368,44 @@ class Tfdm:
             self.close()
         except Exception:
             pass
+
+
+class _HeightMapObject(_DisplacedObject):
+    """... displaced by a height map: Tfdm and Nrtdsm."""
+
+    def __init__(self, ctx, vertices, triangles, heights, params=None, stream=0):
+        levels = [heights] if isinstance(heights, np.ndarray) else list(heights)
+        levels = [np.ascontiguousarray(a, np.float32) for a in levels]
+        if not levels or levels[0].ndim != 2 or levels[0].shape[0] != levels[0].shape[1]:
+            raise GfxError("%s: the height map must be square (%screate takes one size)" % (type(self).__name__, self._PREFIX))
+        self.size = int(levels[0].shape[0])
+        ptrs = (C.POINTER(C.c_float) * len(levels))(*[a.ctypes.data_as(C.POINTER(C.c_float)) for a in levels])
+        self._create(ctx, vertices, triangles, (ptrs, C.c_uint32(len(levels)), C.c_uint32(self.size)), params, stream)
+
+    def _level(self, level):
+        return (C.c_uint32(level),)
+
+    def size_of(self, what, level=0):
+        return self._size(what, level)
+
+    def read_pyramid(self, level):
+        w = self.size >> level
+        return self._read(TFDM_READ_PYRAMID, np.float32, level).reshape(w, w, 2)
+
+    def read_heights(self, level):
+        w = self.size >> level
+        return self._read(TFDM_READ_HEIGHTS, np.float32, level).reshape(w, w)
+
+
+class Tfdm(_HeightMapObject):
+    """gfx_tfdm: a base mesh displaced by a height map, queried by rays without tessellation (csrc/tfdm/).  vertices: VERTEX_DTYPE
+    array; triangles: [n, 3] uint32; heights: one float32 [size, size] array (the library makes the mips) or the list of all
+    log2(size) + 1 levels.  Rays and results are device pointers (ints), in the layout of Context.trace."""
+
+    _PREFIX = "gfx_tfdm_"
+
+    def read_records(self):
+        return self._read(TFDM_READ_RECORDS, np.uint8).reshape(-1, TFDM_RECORD_BYTES)
 
 
 NRTDSM_RECORD_DTYPE = np.dtype([("pos", "<f4", 9), ("nrm", "<f4", 9), ("tc", "<f4", 6), ("minHeight", "<f4"), ("amplitude", "<f4"),
@@ -1382,76 +1414,15 @@ NRTDSM_RECORD_DTYPE = np.dtype([("pos", "<f4", 9), ("nrm", "<f4", 9), ("tc", "<f
 assert NRTDSM_RECORD_DTYPE.itemsize == 144
 
 
-class Nrtdsm:
+class Nrtdsm(_HeightMapObject):
     """gfx_nrtdsm: a base mesh displaced by a height map along its interpolated, not renormalised normals, queried by rays
     without tessellation and without cracks across shared base edges (csrc/nrtdsm/).  Arguments, ray and result layouts as Tfdm;
     params: tfdm_params with target_mip_level 0 and the default local intersection; map values in [0, 1]."""
 
-    def __init__(self, ctx, vertices, triangles, heights, params=None, stream=0):
-        self.L = lib()
-        self.ctx = ctx
-        v = np.ascontiguousarray(vertices, VERTEX_DTYPE)
-        t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
-        levels = [heights] if isinstance(heights, np.ndarray) else list(heights)
-        levels = [np.ascontiguousarray(a, np.float32) for a in levels]
-        if not levels or levels[0].ndim != 2 or levels[0].shape[0] != levels[0].shape[1]:
-            raise GfxError("Nrtdsm: the height map must be square (gfx_nrtdsm_create takes one size)")
-        self.size = int(levels[0].shape[0])
-        ptrs = (C.POINTER(C.c_float) * len(levels))(*[a.ctypes.data_as(C.POINTER(C.c_float)) for a in levels])
-        h = C.c_void_p()
-        ctx._check(self.L.gfx_nrtdsm_create(ctx.h, C.c_void_p(stream), _p(v), C.c_uint32(v.itemsize), C.c_uint32(len(v)), _p(t), C.c_uint32(len(t)),
-                                            ptrs, C.c_uint32(len(levels)), C.c_uint32(self.size), C.byref(params) if params is not None else None, C.byref(h)))
-        self.h = h
-        self.num_triangles = len(t)
-
-    def set_params(self, params, stream=0):
-        self.ctx._check(self.L.gfx_nrtdsm_set_params(self.ctx.h, C.c_void_p(stream), self.h, C.byref(params)))
-
-    def trace(self, mode, d_ray_org, d_ray_dir, num_rays, d_out, d_counters=0, stream=0):
-        """CLOSEST: d_out = TFDM_HIT_DTYPE[num_rays]; ANY: uint32[num_rays].  d_counters: device u64[4], added to."""
-        self.ctx._check(self.L.gfx_nrtdsm_trace(self.ctx.h, C.c_void_p(stream), self.h, C.c_int(mode), C.c_void_p(d_ray_org), C.c_void_p(d_ray_dir),
-                                                C.c_uint32(num_rays), C.c_void_p(d_out), C.c_void_p(d_counters or None)))
-
-    def size_of(self, what, level=0):
-        n = C.c_size_t()
-        self.ctx._check(self.L.gfx_nrtdsm_size(self.ctx.h, self.h, C.c_int(what), C.c_uint32(level), C.byref(n)))
-        return n.value
-
-    def device_bytes(self):
-        return self.size_of(-1)
-
-    def _read(self, what, level, dtype):
-        out = np.zeros(self.size_of(what, level), np.uint8)
-        self.ctx._check(self.L.gfx_nrtdsm_read(self.ctx.h, self.h, C.c_int(what), C.c_uint32(level), _p(out), C.c_size_t(out.nbytes)))
-        return out.view(dtype)
-
-    def read_pyramid(self, level):
-        w = self.size >> level
-        return self._read(TFDM_READ_PYRAMID, level, np.float32).reshape(w, w, 2)
-
-    def read_heights(self, level):
-        w = self.size >> level
-        return self._read(TFDM_READ_HEIGHTS, level, np.float32).reshape(w, w)
-
-    def read_aabbs(self):
-        return self._read(TFDM_READ_AABBS, 0, np.float32).reshape(-1, 6)
+    _PREFIX = "gfx_nrtdsm_"
 
     def read_records(self):
-        return self._read(TFDM_READ_RECORDS, 0, NRTDSM_RECORD_DTYPE)
-
-    def read_nodes(self):
-        return self._read(TFDM_READ_NODES, 0, TFDM_NODE_DTYPE)
-
-    def close(self):
-        if self.h:
-            self.L.gfx_nrtdsm_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._read(TFDM_READ_RECORDS, NRTDSM_RECORD_DTYPE)
 
 
 SCENE_PLAIN = 0x80000000
@@ -1702,72 +1673,28 @@ def _shell_geoms(geoms):
     return arr, keep
 
 
-class Shell:
+class Shell(_DisplacedObject):
     """gfx_shell: a small triangle mesh in the unit tile of shell space (u, v, h), repeated over a base mesh like a texture and
     queried by rays without being instantiated (csrc/nrtdsm/shell*).  vertices / triangles: the base mesh as for Nrtdsm; geoms: a
     list of (positions [n, 3] as (u, v, h), triangles [m, 3]), at most 8; params: shell_params().  Rays as Context.trace; a closest
     hit is SHELL_HIT_DTYPE."""
 
-    def __init__(self, ctx, vertices, triangles, geoms, params=None, stream=0):
-        self.L = lib()
-        self.ctx = ctx
-        v = np.ascontiguousarray(vertices, VERTEX_DTYPE)
-        t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
-        arr, keep = _shell_geoms(geoms)
-        h = C.c_void_p()
-        ctx._check(self.L.gfx_shell_create(ctx.h, C.c_void_p(stream), _p(v), C.c_uint32(v.itemsize), C.c_uint32(len(v)), _p(t), C.c_uint32(len(t)),
-                                           arr, C.c_uint32(len(keep)), C.byref(params) if params is not None else None, C.byref(h)))
-        self.h = h
-        self.num_triangles = len(t)
+    _PREFIX = "gfx_shell_"
 
-    def set_params(self, params, stream=0):
-        self.ctx._check(self.L.gfx_shell_set_params(self.ctx.h, C.c_void_p(stream), self.h, C.byref(params)))
+    def __init__(self, ctx, vertices, triangles, geoms, params=None, stream=0):
+        arr, keep = _shell_geoms(geoms)
+        self._create(ctx, vertices, triangles, (arr, C.c_uint32(len(keep))), params, stream)
 
     def set_geometry(self, geoms, stream=0):
         """Another shell mesh over the same base mesh; a refused call leaves the object as it was."""
         arr, keep = _shell_geoms(geoms)
-        self.ctx._check(self.L.gfx_shell_set_geometry(self.ctx.h, C.c_void_p(stream), self.h, arr, C.c_uint32(len(keep))))
-
-    def trace(self, mode, d_ray_org, d_ray_dir, num_rays, d_out, d_counters=0, stream=0):
-        """CLOSEST: d_out = SHELL_HIT_DTYPE[num_rays]; ANY: uint32[num_rays].  d_counters: device u64[4], added to."""
-        self.ctx._check(self.L.gfx_shell_trace(self.ctx.h, C.c_void_p(stream), self.h, C.c_int(mode), C.c_void_p(d_ray_org), C.c_void_p(d_ray_dir),
-                                               C.c_uint32(num_rays), C.c_void_p(d_out), C.c_void_p(d_counters or None)))
-
-    def size_of(self, what):
-        n = C.c_size_t()
-        self.ctx._check(self.L.gfx_shell_size(self.ctx.h, self.h, C.c_int(what), C.byref(n)))
-        return n.value
-
-    def device_bytes(self):
-        return self.size_of(-1)
-
-    def _read(self, what, dtype):
-        out = np.zeros(self.size_of(what), np.uint8)
-        self.ctx._check(self.L.gfx_shell_read(self.ctx.h, self.h, C.c_int(what), _p(out), C.c_size_t(out.nbytes)))
-        return out.view(dtype)
-
-    def read_aabbs(self):
-        return self._read(TFDM_READ_AABBS, np.float32).reshape(-1, 6)
+        self._call("set_geometry", self.ctx.h, C.c_void_p(stream), self.h, arr, C.c_uint32(len(keep)))
 
     def read_records(self):
         return self._read(TFDM_READ_RECORDS, NRTDSM_RECORD_DTYPE)
-
-    def read_nodes(self):
-        return self._read(TFDM_READ_NODES, TFDM_NODE_DTYPE)
 
     def read_shell_nodes(self):
         return self._read(SHELL_READ_SHELL_NODES, TFDM_NODE_DTYPE)
 
     def read_shell_triangles(self):
         return self._read(SHELL_READ_SHELL_TRIANGLES, SHELL_TRI_DTYPE)
-
-    def close(self):
-        if self.h:
-            self.L.gfx_shell_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

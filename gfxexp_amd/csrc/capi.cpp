@@ -48,6 +48,39 @@ int env_int(const char* name, int fallback, int lo, int hi) {
     const int v = atoi(e);
     return (v < lo || v > hi) ? fallback : v;
 }
+
+// ---- the displaced-surface objects (gfx_tfdm, gfx_nrtdsm, gfx_shell; tfdm/displaced_object.h): what their entry points share
+gfx_tfdm_params displaced_defaults(const gfx_tfdm_params* given, bool shell) {
+    gfx_tfdm_params p;
+    if (given) p = *given;
+    else { tfdm_default_params(&p); if (shell) p.localIntersection = 0u; }
+    return p;
+}
+// `init(object)` fills the new object; one that it leaves half made is released
+template <typename Handle, typename Init> void displaced_create(gfx_ctx* ctx, const char* who, Handle** out, Init init) {
+    if (!out) throw HipError(std::string(who) + ": null output handle");
+    *out = nullptr;
+    std::unique_ptr<Handle> t(new Handle());
+    t->o.device = ctx->c.device;
+    try { init(t->o); }
+    catch (...) { displaced_release(t->o); throw; }
+    *out = t.release();
+}
+template <typename Handle> int displaced_destroy(Handle* obj) {
+    if (!obj) return 1;
+    int prev = -1;
+    const bool switched = hipGetDevice(&prev) == hipSuccess && prev != obj->o.device && hipSetDevice(obj->o.device) == hipSuccess;
+    (void)hipDeviceSynchronize();
+    displaced_release(obj->o);
+    if (switched) (void)hipSetDevice(prev);
+    delete obj;
+    return 0;
+}
+// the guard of a call that launches on the object; `alsoGiven`: the other pointer the call needs, named by `also`
+template <typename Handle> void displaced_guard(const gfx_ctx* ctx, const Handle* obj, const char* who, const char* also = "", const void* alsoGiven = "") {
+    if (!obj || !alsoGiven) throw HipError(std::string(who) + ": null object" + also);
+    if (obj->o.device != ctx->c.device) throw HipError(std::string(who) + ": the object belongs to another device");
+}
 }
 #define GFX_TRY(ctx) if (!(ctx)) return 1; try { DeviceGuard deviceGuard__((ctx)->c.device);
 #define GFX_CATCH(ctx) \
@@ -751,39 +784,20 @@ int gfx_tfdm_default_params(gfx_tfdm_params* out) {
 int gfx_tfdm_create(gfx_ctx* ctx, void* stream, const void* vertices, uint32_t stride, uint32_t numVertices, const uint32_t* triangles, uint32_t numTriangles,
                     const float* const* heightLevels, uint32_t numLevels, uint32_t size, const gfx_tfdm_params* params, gfx_tfdm** out) {
     GFX_TRY(ctx)
-    if (!out) throw HipError("gfx_tfdm_create: null output handle");
-    *out = nullptr;
-    gfx_tfdm_params p;
-    if (params) p = *params;
-    else tfdm_default_params(&p);
-    std::unique_ptr<gfx_tfdm> t(new gfx_tfdm());
-    t->o.device = ctx->c.device;
-    try { tfdm_init(t->o, static_cast<hipStream_t>(stream), vertices, stride, numVertices, triangles, numTriangles, heightLevels, numLevels, size, p); }
-    catch (...) { tfdm_release(t->o); throw; }
-    *out = t.release();
+    displaced_create(ctx, "gfx_tfdm_create", out, [&](TfdmObject& o) {
+        tfdm_init(o, static_cast<hipStream_t>(stream), vertices, stride, numVertices, triangles, numTriangles, heightLevels, numLevels, size, displaced_defaults(params, false)); });
     GFX_CATCH(ctx)
 }
 int gfx_tfdm_set_params(gfx_ctx* ctx, void* stream, gfx_tfdm* obj, const gfx_tfdm_params* params) {
     GFX_TRY(ctx)
-    if (!obj || !params) throw HipError("gfx_tfdm_set_params: null object or parameters");
-    if (obj->o.device != ctx->c.device) throw HipError("gfx_tfdm_set_params: the object belongs to another device");
+    displaced_guard(ctx, obj, "gfx_tfdm_set_params", " or parameters", params);
     tfdm_set_params(obj->o, static_cast<hipStream_t>(stream), *params);
     GFX_CATCH(ctx)
 }
-int gfx_tfdm_destroy(gfx_tfdm* obj) {
-    if (!obj) return 1;
-    int prev = -1;
-    const bool switched = hipGetDevice(&prev) == hipSuccess && prev != obj->o.device && hipSetDevice(obj->o.device) == hipSuccess;
-    (void)hipDeviceSynchronize();
-    tfdm_release(obj->o);
-    if (switched) (void)hipSetDevice(prev);
-    delete obj;
-    return 0;
-}
+int gfx_tfdm_destroy(gfx_tfdm* obj) { return displaced_destroy(obj); }
 int gfx_tfdm_trace(gfx_ctx* ctx, void* stream, gfx_tfdm* obj, int mode, const void* dRayOrgTmin, const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters) {
     GFX_TRY(ctx)
-    if (!obj) throw HipError("gfx_tfdm_trace: null object");
-    if (obj->o.device != ctx->c.device) throw HipError("gfx_tfdm_trace: the object belongs to another device");
+    displaced_guard(ctx, obj, "gfx_tfdm_trace");
     ScopedKernelTimer timer(ctx->c, static_cast<hipStream_t>(stream), "k_tfdm_trace");
     tfdm_trace(obj->o, static_cast<hipStream_t>(stream), mode, dRayOrgTmin, dRayDirTmax, numRays, dOut, dCounters);
     GFX_CATCH(ctx)
@@ -791,52 +805,33 @@ int gfx_tfdm_trace(gfx_ctx* ctx, void* stream, gfx_tfdm* obj, int mode, const vo
 int gfx_tfdm_read(gfx_ctx* ctx, gfx_tfdm* obj, int what, uint32_t level, void* hostOut, size_t bytes) {
     GFX_TRY(ctx)
     if (!obj) throw HipError("gfx_tfdm_read: null object");
-    tfdm_read(obj->o, what, level, hostOut, bytes);
+    displaced_read(obj->o, what, level, hostOut, bytes);
     GFX_CATCH(ctx)
 }
 int gfx_tfdm_size(gfx_ctx* ctx, gfx_tfdm* obj, int what, uint32_t level, size_t* bytes) {
     GFX_TRY(ctx)
     if (!obj || !bytes) throw HipError("gfx_tfdm_size: null object or output");
-    *bytes = tfdm_size(obj->o, what, level);
+    *bytes = displaced_size(obj->o, what, level);
     GFX_CATCH(ctx)
 }
 
 int gfx_nrtdsm_create(gfx_ctx* ctx, void* stream, const void* vertices, uint32_t stride, uint32_t numVertices, const uint32_t* triangles, uint32_t numTriangles,
                       const float* const* heightLevels, uint32_t numLevels, uint32_t size, const gfx_tfdm_params* params, gfx_nrtdsm** out) {
     GFX_TRY(ctx)
-    if (!out) throw HipError("gfx_nrtdsm_create: null output handle");
-    *out = nullptr;
-    gfx_tfdm_params p;
-    if (params) p = *params;
-    else tfdm_default_params(&p);
-    std::unique_ptr<gfx_nrtdsm> t(new gfx_nrtdsm());
-    t->o.device = ctx->c.device;
-    try { nrtdsm_init(t->o, static_cast<hipStream_t>(stream), vertices, stride, numVertices, triangles, numTriangles, heightLevels, numLevels, size, p); }
-    catch (...) { nrtdsm_release(t->o); throw; }
-    *out = t.release();
+    displaced_create(ctx, "gfx_nrtdsm_create", out, [&](NrtdsmObject& o) {
+        nrtdsm_init(o, static_cast<hipStream_t>(stream), vertices, stride, numVertices, triangles, numTriangles, heightLevels, numLevels, size, displaced_defaults(params, false)); });
     GFX_CATCH(ctx)
 }
 int gfx_nrtdsm_set_params(gfx_ctx* ctx, void* stream, gfx_nrtdsm* obj, const gfx_tfdm_params* params) {
     GFX_TRY(ctx)
-    if (!obj || !params) throw HipError("gfx_nrtdsm_set_params: null object or parameters");
-    if (obj->o.device != ctx->c.device) throw HipError("gfx_nrtdsm_set_params: the object belongs to another device");
+    displaced_guard(ctx, obj, "gfx_nrtdsm_set_params", " or parameters", params);
     nrtdsm_set_params(obj->o, static_cast<hipStream_t>(stream), *params);
     GFX_CATCH(ctx)
 }
-int gfx_nrtdsm_destroy(gfx_nrtdsm* obj) {
-    if (!obj) return 1;
-    int prev = -1;
-    const bool switched = hipGetDevice(&prev) == hipSuccess && prev != obj->o.device && hipSetDevice(obj->o.device) == hipSuccess;
-    (void)hipDeviceSynchronize();
-    nrtdsm_release(obj->o);
-    if (switched) (void)hipSetDevice(prev);
-    delete obj;
-    return 0;
-}
+int gfx_nrtdsm_destroy(gfx_nrtdsm* obj) { return displaced_destroy(obj); }
 int gfx_nrtdsm_trace(gfx_ctx* ctx, void* stream, gfx_nrtdsm* obj, int mode, const void* dRayOrgTmin, const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters) {
     GFX_TRY(ctx)
-    if (!obj) throw HipError("gfx_nrtdsm_trace: null object");
-    if (obj->o.device != ctx->c.device) throw HipError("gfx_nrtdsm_trace: the object belongs to another device");
+    displaced_guard(ctx, obj, "gfx_nrtdsm_trace");
     ScopedKernelTimer timer(ctx->c, static_cast<hipStream_t>(stream), "k_nrtdsm_trace");
     nrtdsm_trace(obj->o, static_cast<hipStream_t>(stream), mode, dRayOrgTmin, dRayDirTmax, numRays, dOut, dCounters);
     GFX_CATCH(ctx)
@@ -844,59 +839,39 @@ int gfx_nrtdsm_trace(gfx_ctx* ctx, void* stream, gfx_nrtdsm* obj, int mode, cons
 int gfx_nrtdsm_read(gfx_ctx* ctx, gfx_nrtdsm* obj, int what, uint32_t level, void* hostOut, size_t bytes) {
     GFX_TRY(ctx)
     if (!obj) throw HipError("gfx_nrtdsm_read: null object");
-    nrtdsm_read(obj->o, what, level, hostOut, bytes);
+    displaced_read(obj->o, what, level, hostOut, bytes);
     GFX_CATCH(ctx)
 }
 int gfx_nrtdsm_size(gfx_ctx* ctx, gfx_nrtdsm* obj, int what, uint32_t level, size_t* bytes) {
     GFX_TRY(ctx)
     if (!obj || !bytes) throw HipError("gfx_nrtdsm_size: null object or output");
-    *bytes = nrtdsm_size(obj->o, what, level);
+    *bytes = displaced_size(obj->o, what, level);
     GFX_CATCH(ctx)
 }
 
 int gfx_shell_create(gfx_ctx* ctx, void* stream, const void* vertices, uint32_t stride, uint32_t numVertices, const uint32_t* triangles, uint32_t numTriangles,
                      const gfx_shell_geom* geoms, uint32_t numGeoms, const gfx_tfdm_params* params, gfx_shell** out) {
     GFX_TRY(ctx)
-    if (!out) throw HipError("gfx_shell_create: null output handle");
-    *out = nullptr;
-    gfx_tfdm_params p;
-    if (params) p = *params;
-    else { tfdm_default_params(&p); p.localIntersection = 0u; }
-    std::unique_ptr<gfx_shell> t(new gfx_shell());
-    t->o.device = ctx->c.device;
-    try { shell_init(t->o, static_cast<hipStream_t>(stream), vertices, stride, numVertices, triangles, numTriangles, geoms, numGeoms, p); }
-    catch (...) { shell_release(t->o); throw; }
-    *out = t.release();
+    displaced_create(ctx, "gfx_shell_create", out, [&](ShellObject& o) {
+        shell_init(o, static_cast<hipStream_t>(stream), vertices, stride, numVertices, triangles, numTriangles, geoms, numGeoms, displaced_defaults(params, true)); });
     GFX_CATCH(ctx)
 }
 int gfx_shell_set_params(gfx_ctx* ctx, void* stream, gfx_shell* obj, const gfx_tfdm_params* params) {
     GFX_TRY(ctx)
-    if (!obj || !params) throw HipError("gfx_shell_set_params: null object or parameters");
-    if (obj->o.device != ctx->c.device) throw HipError("gfx_shell_set_params: the object belongs to another device");
+    displaced_guard(ctx, obj, "gfx_shell_set_params", " or parameters", params);
     shell_set_params(obj->o, static_cast<hipStream_t>(stream), *params);
     GFX_CATCH(ctx)
 }
 int gfx_shell_set_geometry(gfx_ctx* ctx, void* stream, gfx_shell* obj, const gfx_shell_geom* geoms, uint32_t numGeoms) {
     GFX_TRY(ctx)
-    if (!obj) throw HipError("gfx_shell_set_geometry: null object");
-    if (obj->o.device != ctx->c.device) throw HipError("gfx_shell_set_geometry: the object belongs to another device");
+    displaced_guard(ctx, obj, "gfx_shell_set_geometry");
     shell_set_geometry(obj->o, static_cast<hipStream_t>(stream), geoms, numGeoms);
     GFX_CATCH(ctx)
 }
-int gfx_shell_destroy(gfx_shell* obj) {
-    if (!obj) return 1;
-    int prev = -1;
-    const bool switched = hipGetDevice(&prev) == hipSuccess && prev != obj->o.device && hipSetDevice(obj->o.device) == hipSuccess;
-    (void)hipDeviceSynchronize();
-    shell_release(obj->o);
-    if (switched) (void)hipSetDevice(prev);
-    delete obj;
-    return 0;
-}
+int gfx_shell_destroy(gfx_shell* obj) { return displaced_destroy(obj); }
 int gfx_shell_trace(gfx_ctx* ctx, void* stream, gfx_shell* obj, int mode, const void* dRayOrgTmin, const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters) {
     GFX_TRY(ctx)
-    if (!obj) throw HipError("gfx_shell_trace: null object");
-    if (obj->o.device != ctx->c.device) throw HipError("gfx_shell_trace: the object belongs to another device");
+    displaced_guard(ctx, obj, "gfx_shell_trace");
     ScopedKernelTimer timer(ctx->c, static_cast<hipStream_t>(stream), "k_shell_trace");
     shell_trace(obj->o, static_cast<hipStream_t>(stream), mode, dRayOrgTmin, dRayDirTmax, numRays, dOut, dCounters);
     GFX_CATCH(ctx)
@@ -904,13 +879,13 @@ int gfx_shell_trace(gfx_ctx* ctx, void* stream, gfx_shell* obj, int mode, const 
 int gfx_shell_read(gfx_ctx* ctx, gfx_shell* obj, int what, void* hostOut, size_t bytes) {
     GFX_TRY(ctx)
     if (!obj) throw HipError("gfx_shell_read: null object");
-    shell_read(obj->o, what, hostOut, bytes);
+    displaced_read(obj->o, what, hostOut, bytes);
     GFX_CATCH(ctx)
 }
 int gfx_shell_size(gfx_ctx* ctx, gfx_shell* obj, int what, size_t* bytes) {
     GFX_TRY(ctx)
     if (!obj || !bytes) throw HipError("gfx_shell_size: null object or output");
-    *bytes = shell_size(obj->o, what);
+    *bytes = displaced_size(obj->o, what);
     GFX_CATCH(ctx)
 }
 

@@ -89,29 +89,11 @@ std::vector<nrtdsm::PrismRecord> make_records(const NrtdsmObject& o, const gfx_t
     return recs;
 }
 
-// records -> device, heights and boxes on the device, boxes back, tree -> device; into fresh buffers, swapped in only when all of it worked
 void build_geometry(NrtdsmObject& o, hipStream_t stream, const gfx_tfdm_params& g, const std::vector<nrtdsm::PrismRecord>& recs) {
     const Params p = make_params(g, o.size);
-    DevBuf records, aabbs, nodes;
-    try {
-        records.reserve(sizeof(nrtdsm::PrismRecord) * o.numTriangles);
-        aabbs.reserve(sizeof(Box) * o.numTriangles);
-        GFX_HIP(hipMemcpyAsync(records.p, recs.data(), sizeof(nrtdsm::PrismRecord) * o.numTriangles, hipMemcpyHostToDevice, stream));
+    rebuild(o, stream, recs.data(), g, p, [&](const DevBuf& records, const DevBuf& aabbs) {
         k_nrtdsm_prim<<<(o.numTriangles + 63u) / 64u, 64, 0, stream>>>(records.as<nrtdsm::PrismRecord>(), o.pyramid.as<F2>(), p, o.numTriangles, aabbs.as<Box>());
-        GFX_HIP(hipGetLastError());
-        std::vector<float> boxes(6 * static_cast<size_t>(o.numTriangles));
-        GFX_HIP(hipMemcpyAsync(boxes.data(), aabbs.p, sizeof(Box) * o.numTriangles, hipMemcpyDeviceToHost, stream));
-        GFX_HIP(hipStreamSynchronize(stream));       // also keeps `recs` alive until its copy is done
-        const std::vector<Node> tree = build_tree(boxes.data(), o.numTriangles);
-        nodes.reserve(sizeof(Node) * tree.size());
-        GFX_HIP(hipMemcpy(nodes.p, tree.data(), sizeof(Node) * tree.size(), hipMemcpyHostToDevice));
-        o.records.release(); o.aabbs.release(); o.nodes.release();
-        o.records = records; o.aabbs = aabbs; o.nodes = nodes;
-        o.numNodes = static_cast<uint32_t>(tree.size());
-        o.pub = g;
-        o.params = p;
-    }
-    catch (...) { records.release(); aabbs.release(); nodes.release(); throw; }
+    });
 }
 
 } // namespace
@@ -119,42 +101,16 @@ void build_geometry(NrtdsmObject& o, hipStream_t stream, const gfx_tfdm_params& 
 void nrtdsm_init(NrtdsmObject& o, hipStream_t stream, const void* vertices, uint32_t stride, uint32_t numVertices, const uint32_t* triangles, uint32_t numTriangles,
                  const float* const* heightLevels, uint32_t numLevels, uint32_t size, const gfx_tfdm_params& g) {
     if (!vertices || !triangles || !heightLevels) throw HipError("gfx_nrtdsm_create: null vertices, triangles or height levels");
-    if (stride < sizeof(gfx_vertex)) throw HipError("gfx_nrtdsm_create: the vertex stride is smaller than gfx_vertex");
-    if (numTriangles == 0 || numVertices == 0) throw HipError("gfx_nrtdsm_create: the base mesh has no triangles");
-    if (numTriangles > kMaxTriangles) throw HipError("gfx_nrtdsm_create: more than 2^20 base triangles");
-    if (size == 0 || (size & (size - 1u)) != 0u) throw HipError("gfx_nrtdsm_create: the height map's size must be a power of two (and the map square)");
-    if (size > (1u << kMaxDepth)) throw HipError("gfx_nrtdsm_create: height maps beyond 8192 x 8192 are not supported");
-    const int maxDepth = floor_log2(size);
-    if (numLevels != 1u && numLevels != static_cast<uint32_t>(maxDepth) + 1u)
-        throw HipError("gfx_nrtdsm_create: numLevels must be 1 (the library makes the mips) or log2(size) + 1; a map that is not square has neither");
-    for (uint32_t l = 0; l < numLevels; ++l) if (!heightLevels[l]) throw HipError("gfx_nrtdsm_create: a height level is null");
+    check_base_mesh(o, stride, numVertices, numTriangles);
+    check_height_map(o, heightLevels, numLevels, size);
     check_params(g);
-    for (uint32_t t = 0; t < 3u * numTriangles; ++t) if (triangles[t] >= numVertices) throw HipError("gfx_nrtdsm_create: a triangle refers to a vertex that does not exist");
+    fill_mirror(o, vertices, stride, numVertices, triangles, numTriangles);
     const std::vector<float> levels = make_levels(heightLevels, numLevels, size);
     if (!nrtdsm::heights_in_unit_range(levels))
         throw HipError("gfx_nrtdsm_create: a height map value lies outside [0, 1] (the descent clips the map value to that range)");
-
-    o.size = size; o.numTriangles = numTriangles;
-    o.positions.resize(9 * static_cast<size_t>(numTriangles)); o.normals.resize(9 * static_cast<size_t>(numTriangles)); o.texCoords.resize(6 * static_cast<size_t>(numTriangles));
-    for (uint32_t t = 0; t < 3u * numTriangles; ++t) {
-        gfx_vertex v;
-        std::memcpy(&v, static_cast<const uint8_t*>(vertices) + static_cast<size_t>(stride) * triangles[t], sizeof(v));
-        for (int k = 0; k < 3; ++k) { o.positions[3 * t + k] = v.position[k]; o.normals[3 * t + k] = v.normal[k]; }
-        o.texCoords[2 * t] = v.texCoord[0]; o.texCoords[2 * t + 1] = v.texCoord[1];
-    }
+    o.size = size;
     const std::vector<nrtdsm::PrismRecord> recs = make_records(o, g, make_params(g, size));      // every refusal comes before the first launch
-    o.heights.reserve(sizeof(float) * levels.size());
-    o.pyramid.reserve(sizeof(F2) * levels.size());
-    GFX_HIP(hipMemcpyAsync(o.heights.p, levels.data(), sizeof(float) * levels.size(), hipMemcpyHostToDevice, stream));
-    const uint32_t b0 = (size + 15u) / 16u;
-    k_tfdm_minmax_first<<<dim3(b0, b0), 256, 0, stream>>>(o.heights.as<float>(), o.pyramid.as<F2>(), maxDepth);
-    GFX_HIP(hipGetLastError());
-    for (int l = 1; l <= maxDepth; ++l) {
-        const uint32_t b = ((size >> l) + 15u) / 16u;
-        k_tfdm_minmax_level<<<dim3(b, b), 256, 0, stream>>>(o.heights.as<float>(), o.pyramid.as<F2>(), maxDepth, l);
-        GFX_HIP(hipGetLastError());
-    }
-    GFX_HIP(hipStreamSynchronize(stream));           // `levels` goes out of scope
+    upload_height_map(o, stream, levels);
     build_geometry(o, stream, g, recs);
 }
 
@@ -163,60 +119,15 @@ void nrtdsm_set_params(NrtdsmObject& o, hipStream_t stream, const gfx_tfdm_param
     build_geometry(o, stream, g, make_records(o, g, make_params(g, o.size)));
 }
 
-void nrtdsm_release(NrtdsmObject& o) {
-    o.heights.release(); o.pyramid.release(); o.records.release(); o.aabbs.release(); o.nodes.release();
-}
-
 void nrtdsm_trace(NrtdsmObject& o, hipStream_t stream, int mode, const void* dRayOrgTmin, const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters) {
-    if (mode != GFX_TRACE_CLOSEST && mode != GFX_TRACE_ANY) throw HipError("gfx_nrtdsm_trace: unknown mode");
-    if (numRays == 0) return;
-    if (!dRayOrgTmin || !dRayDirTmax || !dOut) throw HipError("gfx_nrtdsm_trace: null ray or output buffer");
-    const uintptr_t outMask = mode == GFX_TRACE_ANY ? 3u : 15u;
-    if ((reinterpret_cast<uintptr_t>(dRayOrgTmin) & 15u) || (reinterpret_cast<uintptr_t>(dRayDirTmax) & 15u) || (reinterpret_cast<uintptr_t>(dOut) & outMask))
-        throw HipError("gfx_nrtdsm_trace: the ray buffers and a closest-hit output must be 16-byte aligned (an any-hit output 4-byte)");
-    if (reinterpret_cast<uintptr_t>(dCounters) & 7u) throw HipError("gfx_nrtdsm_trace: the counters must be 8-byte aligned");
-    const uint32_t blocks = (numRays + kTraceBlock - 1u) / kTraceBlock;
-    const float4* org = static_cast<const float4*>(dRayOrgTmin);
-    const float4* dir = static_cast<const float4*>(dRayDirTmax);
-    unsigned long long* cnt = static_cast<unsigned long long*>(dCounters);
+    const TraceArgs a = trace_args(o, mode, dRayOrgTmin, dRayDirTmax, numRays, dOut, dCounters, kTraceBlock);
+    if (a.blocks == 0) return;
     auto launch = [&](auto kernel) {
-        kernel<<<blocks, kTraceBlock, 0, stream>>>(o.nodes.as<Node>(), o.records.as<nrtdsm::PrismRecord>(), o.heights.as<float>(), o.pyramid.as<F2>(), o.params, org, dir, numRays, dOut, cnt);
+        kernel<<<a.blocks, kTraceBlock, 0, stream>>>(o.nodes.as<Node>(), o.records.as<nrtdsm::PrismRecord>(), o.heights.as<float>(), o.pyramid.as<F2>(), o.params, a.org, a.dir,
+                                                     numRays, dOut, a.counters);
     };
     launch(mode == GFX_TRACE_ANY ? k_nrtdsm_trace<true> : k_nrtdsm_trace<false>);
     GFX_HIP(hipGetLastError());
-}
-
-size_t nrtdsm_size(const NrtdsmObject& o, int what, uint32_t level) {
-    const int maxDepth = o.params.maxDepth;
-    switch (what) {
-    case -1: return o.heights.bytes + o.pyramid.bytes + o.records.bytes + o.aabbs.bytes + o.nodes.bytes;
-    case GFX_TFDM_READ_PYRAMID:
-    case GFX_TFDM_READ_HEIGHTS: {
-        if (level > static_cast<uint32_t>(maxDepth)) throw HipError("gfx_nrtdsm_read: no such level");
-        const size_t w = o.size >> level;
-        return w * w * (what == GFX_TFDM_READ_PYRAMID ? sizeof(F2) : sizeof(float));
-    }
-    case GFX_TFDM_READ_AABBS: return sizeof(Box) * o.numTriangles;
-    case GFX_TFDM_READ_RECORDS: return sizeof(nrtdsm::PrismRecord) * o.numTriangles;
-    case GFX_TFDM_READ_NODES: return sizeof(Node) * o.numNodes;
-    default: throw HipError("gfx_nrtdsm_read: unknown item");
-    }
-}
-
-void nrtdsm_read(NrtdsmObject& o, int what, uint32_t level, void* hostOut, size_t bytes) {
-    if (what < 0) throw HipError("gfx_nrtdsm_read: unknown item");
-    const size_t need = nrtdsm_size(o, what, level);
-    if (!hostOut || bytes != need) throw HipError("gfx_nrtdsm_read: the buffer must have exactly the item's size (gfx_nrtdsm_size)");
-    const void* src = nullptr;
-    switch (what) {
-    case GFX_TFDM_READ_PYRAMID: src = o.pyramid.as<F2>() + level_offset(o.params.maxDepth, static_cast<int>(level)); break;
-    case GFX_TFDM_READ_HEIGHTS: src = o.heights.as<float>() + level_offset(o.params.maxDepth, static_cast<int>(level)); break;
-    case GFX_TFDM_READ_AABBS: src = o.aabbs.p; break;
-    case GFX_TFDM_READ_RECORDS: src = o.records.p; break;
-    default: src = o.nodes.p; break;
-    }
-    GFX_HIP(hipDeviceSynchronize());
-    GFX_HIP(hipMemcpy(hostOut, src, bytes, hipMemcpyDeviceToHost));
 }
 
 } // namespace gfx

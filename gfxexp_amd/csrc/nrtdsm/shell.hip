@@ -94,38 +94,21 @@ std::vector<nrtdsm::PrismRecord> make_records(const ShellObject& o, const gfx_tf
 
 struct ShellDev { DevBuf nodes, tris; uint32_t numNodes = 0, numTris = 0; };
 
-// records -> device, heights and boxes on the device, boxes back, tree -> device; into fresh buffers, swapped in only when all of
-// it worked.  `fresh`: a new shell BVH that takes the place of the object's own with them (null: the object's own is used).
+// `fresh`: a new shell BVH that takes the place of the object's own together with the new records, boxes and tree (null: the
+// object's own is used)
 void build_geometry(ShellObject& o, hipStream_t stream, const gfx_tfdm_params& g, const std::vector<nrtdsm::PrismRecord>& recs, ShellDev* fresh) {
     const Params p = shell::make_shell_params(g);
-    DevBuf records, aabbs, nodes;
-    try {
-        records.reserve(sizeof(nrtdsm::PrismRecord) * o.numTriangles);
-        aabbs.reserve(sizeof(Box) * o.numTriangles);
-        GFX_HIP(hipMemcpyAsync(records.p, recs.data(), sizeof(nrtdsm::PrismRecord) * o.numTriangles, hipMemcpyHostToDevice, stream));
-        const DevBuf& sn = fresh ? fresh->nodes : o.shellNodes;
-        const DevBuf& st = fresh ? fresh->tris : o.shellTris;
+    const DevBuf& sn = fresh ? fresh->nodes : o.shellNodes;
+    const DevBuf& st = fresh ? fresh->tris : o.shellTris;
+    rebuild(o, stream, recs.data(), g, p, [&](const DevBuf& records, const DevBuf& aabbs) {
         k_shell_prim<<<(o.numTriangles + 63u) / 64u, kTraceBlock, 0, stream>>>(records.as<nrtdsm::PrismRecord>(), sn.as<Node>(), st.as<shell::ShellTri>(), p, o.numTriangles, aabbs.as<Box>());
-        GFX_HIP(hipGetLastError());
-        std::vector<float> boxes(6 * static_cast<size_t>(o.numTriangles));
-        GFX_HIP(hipMemcpyAsync(boxes.data(), aabbs.p, sizeof(Box) * o.numTriangles, hipMemcpyDeviceToHost, stream));
-        GFX_HIP(hipStreamSynchronize(stream));       // also keeps `recs` alive until its copy is done
-        const std::vector<Node> tree = build_tree(boxes.data(), o.numTriangles);
-        nodes.reserve(sizeof(Node) * tree.size());
-        GFX_HIP(hipMemcpy(nodes.p, tree.data(), sizeof(Node) * tree.size(), hipMemcpyHostToDevice));
-        o.records.release(); o.aabbs.release(); o.nodes.release();
-        o.records = records; o.aabbs = aabbs; o.nodes = nodes;
-        o.numNodes = static_cast<uint32_t>(tree.size());
-        if (fresh) {
-            o.shellNodes.release(); o.shellTris.release();
-            o.shellNodes = fresh->nodes; o.shellTris = fresh->tris;
-            o.numShellNodes = fresh->numNodes; o.numShellTriangles = fresh->numTris;
-            fresh->nodes = DevBuf(); fresh->tris = DevBuf();
-        }
-        o.pub = g;
-        o.params = p;
+    });
+    if (fresh) {
+        o.shellNodes.release(); o.shellTris.release();
+        o.shellNodes = fresh->nodes; o.shellTris = fresh->tris;
+        o.numShellNodes = fresh->numNodes; o.numShellTriangles = fresh->numTris;
+        fresh->nodes = DevBuf(); fresh->tris = DevBuf();
     }
-    catch (...) { records.release(); aabbs.release(); nodes.release(); throw; }
 }
 
 // the shell BVH of the geometries on the device, or the refusal
@@ -146,19 +129,9 @@ void upload_shell(const char* who, hipStream_t stream, const gfx_shell_geom* geo
 void shell_init(ShellObject& o, hipStream_t stream, const void* vertices, uint32_t stride, uint32_t numVertices, const uint32_t* triangles, uint32_t numTriangles,
                 const gfx_shell_geom* geoms, uint32_t numGeoms, const gfx_tfdm_params& g) {
     if (!vertices || !triangles) throw HipError("gfx_shell_create: null vertices or triangles");
-    if (stride < sizeof(gfx_vertex)) throw HipError("gfx_shell_create: the vertex stride is smaller than gfx_vertex");
-    if (numTriangles == 0 || numVertices == 0) throw HipError("gfx_shell_create: the base mesh has no triangles");
-    if (numTriangles > kMaxTriangles) throw HipError("gfx_shell_create: more than 2^20 base triangles");
+    check_base_mesh(o, stride, numVertices, numTriangles);
     check_params(g);
-    for (uint32_t t = 0; t < 3u * numTriangles; ++t) if (triangles[t] >= numVertices) throw HipError("gfx_shell_create: a triangle refers to a vertex that does not exist");
-    o.numTriangles = numTriangles;
-    o.positions.resize(9 * static_cast<size_t>(numTriangles)); o.normals.resize(9 * static_cast<size_t>(numTriangles)); o.texCoords.resize(6 * static_cast<size_t>(numTriangles));
-    for (uint32_t t = 0; t < 3u * numTriangles; ++t) {
-        gfx_vertex v;
-        std::memcpy(&v, static_cast<const uint8_t*>(vertices) + static_cast<size_t>(stride) * triangles[t], sizeof(v));
-        for (int k = 0; k < 3; ++k) { o.positions[3 * t + k] = v.position[k]; o.normals[3 * t + k] = v.normal[k]; }
-        o.texCoords[2 * t] = v.texCoord[0]; o.texCoords[2 * t + 1] = v.texCoord[1];
-    }
+    fill_mirror(o, vertices, stride, numVertices, triangles, numTriangles);
     const std::vector<nrtdsm::PrismRecord> recs = make_records(o, g, shell::make_shell_params(g));      // every refusal comes before the first launch
     ShellDev dev;
     try {
@@ -182,56 +155,15 @@ void shell_set_geometry(ShellObject& o, hipStream_t stream, const gfx_shell_geom
     catch (...) { dev.nodes.release(); dev.tris.release(); throw; }
 }
 
-void shell_release(ShellObject& o) {
-    o.shellNodes.release(); o.shellTris.release(); o.records.release(); o.aabbs.release(); o.nodes.release();
-}
-
 void shell_trace(ShellObject& o, hipStream_t stream, int mode, const void* dRayOrgTmin, const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters) {
-    if (mode != GFX_TRACE_CLOSEST && mode != GFX_TRACE_ANY) throw HipError("gfx_shell_trace: unknown mode");
-    if (numRays == 0) return;
-    if (!dRayOrgTmin || !dRayDirTmax || !dOut) throw HipError("gfx_shell_trace: null ray or output buffer");
-    const uintptr_t outMask = mode == GFX_TRACE_ANY ? 3u : 15u;
-    if ((reinterpret_cast<uintptr_t>(dRayOrgTmin) & 15u) || (reinterpret_cast<uintptr_t>(dRayDirTmax) & 15u) || (reinterpret_cast<uintptr_t>(dOut) & outMask))
-        throw HipError("gfx_shell_trace: the ray buffers and a closest-hit output must be 16-byte aligned (an any-hit output 4-byte)");
-    if (reinterpret_cast<uintptr_t>(dCounters) & 7u) throw HipError("gfx_shell_trace: the counters must be 8-byte aligned");
-    const uint32_t blocks = (numRays + kTraceBlock - 1u) / kTraceBlock;
-    const float4* org = static_cast<const float4*>(dRayOrgTmin);
-    const float4* dir = static_cast<const float4*>(dRayDirTmax);
-    unsigned long long* cnt = static_cast<unsigned long long*>(dCounters);
+    const TraceArgs a = trace_args(o, mode, dRayOrgTmin, dRayDirTmax, numRays, dOut, dCounters, kTraceBlock);
+    if (a.blocks == 0) return;
     auto launch = [&](auto kernel) {
-        kernel<<<blocks, kTraceBlock, 0, stream>>>(o.nodes.as<Node>(), o.records.as<nrtdsm::PrismRecord>(), o.shellNodes.as<Node>(), o.shellTris.as<shell::ShellTri>(), o.params,
-                                                   org, dir, numRays, dOut, cnt);
+        kernel<<<a.blocks, kTraceBlock, 0, stream>>>(o.nodes.as<Node>(), o.records.as<nrtdsm::PrismRecord>(), o.shellNodes.as<Node>(), o.shellTris.as<shell::ShellTri>(), o.params,
+                                                     a.org, a.dir, numRays, dOut, a.counters);
     };
     launch(mode == GFX_TRACE_ANY ? k_shell_trace<true> : k_shell_trace<false>);
     GFX_HIP(hipGetLastError());
-}
-
-size_t shell_size(const ShellObject& o, int what) {
-    switch (what) {
-    case -1: return o.shellNodes.bytes + o.shellTris.bytes + o.records.bytes + o.aabbs.bytes + o.nodes.bytes;
-    case GFX_TFDM_READ_AABBS: return sizeof(Box) * o.numTriangles;
-    case GFX_TFDM_READ_RECORDS: return sizeof(nrtdsm::PrismRecord) * o.numTriangles;
-    case GFX_TFDM_READ_NODES: return sizeof(Node) * o.numNodes;
-    case GFX_SHELL_READ_SHELL_NODES: return sizeof(Node) * o.numShellNodes;
-    case GFX_SHELL_READ_SHELL_TRIANGLES: return sizeof(shell::ShellTri) * o.numShellTriangles;
-    default: throw HipError("gfx_shell_read: unknown item");
-    }
-}
-
-void shell_read(ShellObject& o, int what, void* hostOut, size_t bytes) {
-    if (what < 0) throw HipError("gfx_shell_read: unknown item");
-    const size_t need = shell_size(o, what);
-    if (!hostOut || bytes != need) throw HipError("gfx_shell_read: the buffer must have exactly the item's size (gfx_shell_size)");
-    const void* src = nullptr;
-    switch (what) {
-    case GFX_TFDM_READ_AABBS: src = o.aabbs.p; break;
-    case GFX_TFDM_READ_RECORDS: src = o.records.p; break;
-    case GFX_TFDM_READ_NODES: src = o.nodes.p; break;
-    case GFX_SHELL_READ_SHELL_NODES: src = o.shellNodes.p; break;
-    default: src = o.shellTris.p; break;
-    }
-    GFX_HIP(hipDeviceSynchronize());
-    GFX_HIP(hipMemcpy(hostOut, src, bytes, hipMemcpyDeviceToHost));
 }
 
 } // namespace gfx

@@ -88,9 +88,8 @@ void check_params(const gfx_tfdm_params& g, uint32_t size) {
     if (!(g.texScale[0] > 0.0f) || !(g.texScale[1] > 0.0f)) throw HipError("gfx_tfdm: texScale must be positive");
 }
 
-// records -> device, boxes on the device, boxes back, tree -> device; into fresh buffers, swapped in only when all of it worked
-void build_geometry(TfdmObject& o, hipStream_t stream, const gfx_tfdm_params& g) {
-    const Params p = make_params(g, o.size);
+// The records of every base triangle, or the refusal
+std::vector<TriRecord> make_records(const TfdmObject& o, const gfx_tfdm_params& g, const Params& p) {
     std::vector<TriRecord> recs(o.numTriangles);
     for (uint32_t t = 0; t < o.numTriangles; ++t)
         recs[t] = make_record(&o.positions[9 * t], &o.positions[9 * t + 3], &o.positions[9 * t + 6], &o.normals[9 * t], &o.normals[9 * t + 3], &o.normals[9 * t + 6],
@@ -101,28 +100,16 @@ void build_geometry(TfdmObject& o, hipStream_t stream, const gfx_tfdm_params& g)
         for (float c : r.tc)
             if (std::isfinite(c) && fabsf(c) * static_cast<float>(o.size) >= kMaxTexelCoord)
                 throw HipError("gfx_tfdm: a texture coordinate (after the texture transform) times the map's size reaches 2^24; reduce texOffset modulo 1 or the scale");
-    DevBuf records, aabbs, nodes;
-    try {
-        records.reserve(sizeof(TriRecord) * o.numTriangles);
-        aabbs.reserve(sizeof(Box) * o.numTriangles);
-        GFX_HIP(hipMemcpyAsync(records.p, recs.data(), sizeof(TriRecord) * o.numTriangles, hipMemcpyHostToDevice, stream));
+    return recs;
+}
+
+void build_geometry(TfdmObject& o, hipStream_t stream, const gfx_tfdm_params& g) {
+    const Params p = make_params(g, o.size);
+    const std::vector<TriRecord> recs = make_records(o, g, p);
+    o.root = rebuild(o, stream, recs.data(), g, p, [&](const DevBuf& records, const DevBuf& aabbs) {
         k_tfdm_prim_aabbs<<<(o.numTriangles + 63u) / 64u, 64, 0, stream>>>(records.as<TriRecord>(), o.pyramid.as<F2>(), p, o.numTriangles, aabbs.as<Box>());
-        GFX_HIP(hipGetLastError());
-        std::vector<float> boxes(6 * static_cast<size_t>(o.numTriangles));
-        GFX_HIP(hipMemcpyAsync(boxes.data(), aabbs.p, sizeof(Box) * o.numTriangles, hipMemcpyDeviceToHost, stream));
-        GFX_HIP(hipStreamSynchronize(stream));       // also keeps `recs` alive until its copy is done
-        const std::vector<Node> tree = build_tree(boxes.data(), o.numTriangles);
-        nodes.reserve(sizeof(Node) * tree.size());
-        GFX_HIP(hipMemcpy(nodes.p, tree.data(), sizeof(Node) * tree.size(), hipMemcpyHostToDevice));
-        o.records.release(); o.aabbs.release(); o.nodes.release();
-        o.records = records; o.aabbs = aabbs; o.nodes = nodes;
-        o.numNodes = static_cast<uint32_t>(tree.size());
-        o.root = tree[0];
-        ++o.generation;
-        o.pub = g;
-        o.params = p;
-    }
-    catch (...) { records.release(); aabbs.release(); nodes.release(); throw; }
+    });
+    ++o.generation;
 }
 
 } // namespace
@@ -137,40 +124,12 @@ void tfdm_default_params(gfx_tfdm_params* out) {
 void tfdm_init(TfdmObject& o, hipStream_t stream, const void* vertices, uint32_t stride, uint32_t numVertices, const uint32_t* triangles, uint32_t numTriangles,
                const float* const* heightLevels, uint32_t numLevels, uint32_t size, const gfx_tfdm_params& g) {
     if (!vertices || !triangles || !heightLevels) throw HipError("gfx_tfdm_create: null vertices, triangles or height levels");
-    if (stride < sizeof(gfx_vertex)) throw HipError("gfx_tfdm_create: the vertex stride is smaller than gfx_vertex");
-    if (numTriangles == 0 || numVertices == 0) throw HipError("gfx_tfdm_create: the base mesh has no triangles");
-    if (numTriangles > kMaxTriangles) throw HipError("gfx_tfdm_create: more than 2^20 base triangles");
-    // tfdm_main.cpp:2236-2239: the height map must be square with a power-of-two size
-    if (size == 0 || (size & (size - 1u)) != 0u) throw HipError("gfx_tfdm_create: the height map's size must be a power of two (and the map square)");
-    if (size > (1u << kMaxDepth)) throw HipError("gfx_tfdm_create: height maps beyond 8192 x 8192 are not supported");
-    const int maxDepth = floor_log2(size);
-    if (numLevels != 1u && numLevels != static_cast<uint32_t>(maxDepth) + 1u)
-        throw HipError("gfx_tfdm_create: numLevels must be 1 (the library makes the mips) or log2(size) + 1; a map that is not square has neither");
-    for (uint32_t l = 0; l < numLevels; ++l) if (!heightLevels[l]) throw HipError("gfx_tfdm_create: a height level is null");
+    check_base_mesh(o, stride, numVertices, numTriangles);
+    check_height_map(o, heightLevels, numLevels, size);
     check_params(g, size);
-    for (uint32_t t = 0; t < 3u * numTriangles; ++t) if (triangles[t] >= numVertices) throw HipError("gfx_tfdm_create: a triangle refers to a vertex that does not exist");
-
-    o.size = size; o.numTriangles = numTriangles;
-    o.positions.resize(9 * static_cast<size_t>(numTriangles)); o.normals.resize(9 * static_cast<size_t>(numTriangles)); o.texCoords.resize(6 * static_cast<size_t>(numTriangles));
-    for (uint32_t t = 0; t < 3u * numTriangles; ++t) {
-        gfx_vertex v;
-        std::memcpy(&v, static_cast<const uint8_t*>(vertices) + static_cast<size_t>(stride) * triangles[t], sizeof(v));
-        for (int k = 0; k < 3; ++k) { o.positions[3 * t + k] = v.position[k]; o.normals[3 * t + k] = v.normal[k]; }
-        o.texCoords[2 * t] = v.texCoord[0]; o.texCoords[2 * t + 1] = v.texCoord[1];
-    }
-    const std::vector<float> levels = make_levels(heightLevels, numLevels, size);
-    o.heights.reserve(sizeof(float) * levels.size());
-    o.pyramid.reserve(sizeof(F2) * levels.size());
-    GFX_HIP(hipMemcpyAsync(o.heights.p, levels.data(), sizeof(float) * levels.size(), hipMemcpyHostToDevice, stream));
-    const uint32_t b0 = (size + 15u) / 16u;
-    k_tfdm_minmax_first<<<dim3(b0, b0), 256, 0, stream>>>(o.heights.as<float>(), o.pyramid.as<F2>(), maxDepth);
-    GFX_HIP(hipGetLastError());
-    for (int l = 1; l <= maxDepth; ++l) {
-        const uint32_t b = ((size >> l) + 15u) / 16u;
-        k_tfdm_minmax_level<<<dim3(b, b), 256, 0, stream>>>(o.heights.as<float>(), o.pyramid.as<F2>(), maxDepth, l);
-        GFX_HIP(hipGetLastError());
-    }
-    GFX_HIP(hipStreamSynchronize(stream));           // `levels` goes out of scope
+    fill_mirror(o, vertices, stride, numVertices, triangles, numTriangles);
+    o.size = size;
+    upload_height_map(o, stream, make_levels(heightLevels, numLevels, size));
     build_geometry(o, stream, g);
 }
 
@@ -179,64 +138,18 @@ void tfdm_set_params(TfdmObject& o, hipStream_t stream, const gfx_tfdm_params& g
     build_geometry(o, stream, g);
 }
 
-void tfdm_release(TfdmObject& o) {
-    o.heights.release(); o.pyramid.release(); o.records.release(); o.aabbs.release(); o.nodes.release();
-}
-
 void tfdm_trace(TfdmObject& o, hipStream_t stream, int mode, const void* dRayOrgTmin, const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters) {
-    if (mode != GFX_TRACE_CLOSEST && mode != GFX_TRACE_ANY) throw HipError("gfx_tfdm_trace: unknown mode");
-    if (numRays == 0) return;
-    if (!dRayOrgTmin || !dRayDirTmax || !dOut) throw HipError("gfx_tfdm_trace: null ray or output buffer");
-    // rays are read as float4 and a closest hit is written as two float4; an any-hit answer is one uint32
-    const uintptr_t outMask = mode == GFX_TRACE_ANY ? 3u : 15u;
-    if ((reinterpret_cast<uintptr_t>(dRayOrgTmin) & 15u) || (reinterpret_cast<uintptr_t>(dRayDirTmax) & 15u) || (reinterpret_cast<uintptr_t>(dOut) & outMask))
-        throw HipError("gfx_tfdm_trace: the ray buffers and a closest-hit output must be 16-byte aligned (an any-hit output 4-byte)");
-    if (reinterpret_cast<uintptr_t>(dCounters) & 7u) throw HipError("gfx_tfdm_trace: the counters must be 8-byte aligned");
-    const uint32_t blocks = (numRays + kTraceBlock - 1u) / kTraceBlock;
-    const float4* org = static_cast<const float4*>(dRayOrgTmin);
-    const float4* dir = static_cast<const float4*>(dRayDirTmax);
-    unsigned long long* cnt = static_cast<unsigned long long*>(dCounters);
+    const TraceArgs a = trace_args(o, mode, dRayOrgTmin, dRayDirTmax, numRays, dOut, dCounters, kTraceBlock);
+    if (a.blocks == 0) return;
     auto launch = [&](auto kernel) {
-        kernel<<<blocks, kTraceBlock, 0, stream>>>(o.nodes.as<Node>(), o.records.as<TriRecord>(), o.heights.as<float>(), o.pyramid.as<F2>(), o.params, org, dir, numRays, dOut, cnt);
+        kernel<<<a.blocks, kTraceBlock, 0, stream>>>(o.nodes.as<Node>(), o.records.as<TriRecord>(), o.heights.as<float>(), o.pyramid.as<F2>(), o.params, a.org, a.dir, numRays, dOut,
+                                                     a.counters);
     };
     const bool any = mode == GFX_TRACE_ANY;
     // (named in this order so that the instantiations without the Newton loop keep their place at the front of the code object)
     if (o.params.local != kBilinear) launch(any ? k_tfdm_trace<true, false> : k_tfdm_trace<false, false>);
     else launch(any ? k_tfdm_trace<true, true> : k_tfdm_trace<false, true>);
     GFX_HIP(hipGetLastError());
-}
-
-size_t tfdm_size(const TfdmObject& o, int what, uint32_t level) {
-    const int maxDepth = o.params.maxDepth;
-    switch (what) {
-    case -1: return o.heights.bytes + o.pyramid.bytes + o.records.bytes + o.aabbs.bytes + o.nodes.bytes;
-    case GFX_TFDM_READ_PYRAMID:
-    case GFX_TFDM_READ_HEIGHTS: {
-        if (level > static_cast<uint32_t>(maxDepth)) throw HipError("gfx_tfdm_read: no such level");
-        const size_t w = o.size >> level;
-        return w * w * (what == GFX_TFDM_READ_PYRAMID ? sizeof(F2) : sizeof(float));
-    }
-    case GFX_TFDM_READ_AABBS: return sizeof(Box) * o.numTriangles;
-    case GFX_TFDM_READ_RECORDS: return sizeof(TriRecord) * o.numTriangles;
-    case GFX_TFDM_READ_NODES: return sizeof(Node) * o.numNodes;
-    default: throw HipError("gfx_tfdm_read: unknown item");
-    }
-}
-
-void tfdm_read(TfdmObject& o, int what, uint32_t level, void* hostOut, size_t bytes) {
-    if (what < 0) throw HipError("gfx_tfdm_read: unknown item");
-    const size_t need = tfdm_size(o, what, level);
-    if (!hostOut || bytes != need) throw HipError("gfx_tfdm_read: the buffer must have exactly the item's size (gfx_tfdm_size)");
-    const void* src = nullptr;
-    switch (what) {
-    case GFX_TFDM_READ_PYRAMID: src = o.pyramid.as<F2>() + level_offset(o.params.maxDepth, static_cast<int>(level)); break;
-    case GFX_TFDM_READ_HEIGHTS: src = o.heights.as<float>() + level_offset(o.params.maxDepth, static_cast<int>(level)); break;
-    case GFX_TFDM_READ_AABBS: src = o.aabbs.p; break;
-    case GFX_TFDM_READ_RECORDS: src = o.records.p; break;
-    default: src = o.nodes.p; break;
-    }
-    GFX_HIP(hipDeviceSynchronize());
-    GFX_HIP(hipMemcpy(hostOut, src, bytes, hipMemcpyDeviceToHost));
 }
 
 } // namespace gfx

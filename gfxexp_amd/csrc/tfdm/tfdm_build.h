@@ -1,4 +1,4 @@
-// tfdm_build.h -- host-only set-up of a displaced object (csrc/tfdm/tfdm.hip and tests/tfdm_host.cpp include it): the derived
+// tfdm_build.h -- host-only set-up of a displaced object (csrc/tfdm/displaced_object.h and tests/tfdm_host.cpp include it): the derived
 // parameters, the height mips, the per-triangle records and the tree over the per-triangle boxes.
 //
 // The records follow tfdm/tfdm_main.cpp:780-843 (matObjToTcTang, matTcToBc, matTcToNInObj in double, stored as float) and then
