@@ -340,7 +340,7 @@ C_ABI_SYMBOLS = [
     "gfx_tfdm_default_params", "gfx_tfdm_create", "gfx_tfdm_set_params", "gfx_tfdm_destroy", "gfx_tfdm_trace", "gfx_tfdm_read", "gfx_tfdm_size",
     "gfx_tfdm_set_create", "gfx_tfdm_set_add", "gfx_tfdm_set_transform", "gfx_tfdm_set_commit", "gfx_tfdm_set_read", "gfx_tfdm_set_destroy", "gfx_trace_scene",
     "gfx_scene_bind_displaced", "gfx_restir_primary_rays", "gfx_scene_bind_displaced_passes", "gfx_restir_last_rays",
-    "gfx_tfdm_set_move", "gfx_tfdm_set_read_motion",
+    "gfx_tfdm_set_move", "gfx_tfdm_set_read_motion", "gfx_tfdm_set_add_nrtdsm",
     "gfx_nrtdsm_create", "gfx_nrtdsm_set_params", "gfx_nrtdsm_destroy", "gfx_nrtdsm_trace", "gfx_nrtdsm_read", "gfx_nrtdsm_size",
     "gfx_shell_create", "gfx_shell_set_params", "gfx_shell_set_geometry", "gfx_shell_destroy", "gfx_shell_trace", "gfx_shell_read", "gfx_shell_size",
 ]
@@ -1433,6 +1433,7 @@ TFDM_INSTANCE_DTYPE = np.dtype([("objToWorld", "<f4", 12), ("worldToObj", "<f4",
                                 ("nodes", "<u8"), ("records", "<u8"), ("heights", "<u8"), ("pyramid", "<u8"), ("params", "<u4", 8)])
 TFDM_MOTION_DTYPE = np.dtype([("curToPrev", "<f4", 12)])      # the motion table of a set: row-major 3 x 4, previous * inverse(current)
 TFDM_SET_MAX_INSTANCES = 1024
+INSTANCE_TFDM, INSTANCE_NRTDSM = 0, 1      # GFX_INSTANCE_*: the kind of a set member, the "pad0" word of its record
 
 
 class GfxSceneHit(C.Structure):
@@ -1449,9 +1450,10 @@ def _xfm12(m):
 
 
 class TfdmSet:
-    """gfx_tfdm_set: Tfdm objects under object-to-world transforms (row-major 3 x 4, or a 4 x 4 whose last row is dropped), the
-    displaced instances of trace_scene.  commit() before the first query, and again after add / set_transform / move / a member's
-    Tfdm.set_params.  move() is the per-frame update of a moving instance (previous <- current, current <- the new transform: its
+    """gfx_tfdm_set: Tfdm and Nrtdsm objects, in any order, under object-to-world transforms (row-major 3 x 4, or a 4 x 4 whose last
+    row is dropped), the displaced instances of trace_scene.  A set with an Nrtdsm member is traced but not rendered
+    (Context.bind_displaced refuses it).  commit() before the first query, and again after add / set_transform / move / a member's
+    set_params.  move() is the per-frame update of a moving instance (previous <- current, current <- the new transform: its
     pixels get its motion vector); set_transform() is the teleport (previous <- current <- the new transform, no motion).  The set
     keeps its members alive."""
 
@@ -1469,7 +1471,8 @@ class TfdmSet:
     def add(self, obj, obj_to_world, user_id=0):
         x = _xfm12(obj_to_world)
         index = C.c_uint32()
-        self.ctx._check(self.L.gfx_tfdm_set_add(self.h, obj.h, _p(x), C.c_uint32(user_id), C.byref(index)))
+        entry = self.L.gfx_tfdm_set_add_nrtdsm if isinstance(obj, Nrtdsm) else self.L.gfx_tfdm_set_add
+        self.ctx._check(entry(self.h, obj.h, _p(x), C.c_uint32(user_id), C.byref(index)))
         self.objects.append(obj)
         return index.value
 

@@ -904,6 +904,13 @@ int gfx_tfdm_set_add(gfx_tfdm_set* set, gfx_tfdm* obj, const float objToWorld[12
     if (index) *index = k;
     GFX_CATCH(set->ctx)
 }
+int gfx_tfdm_set_add_nrtdsm(gfx_tfdm_set* set, gfx_nrtdsm* obj, const float objToWorld[12], uint32_t userId, uint32_t* index) {
+    if (!set) return 1;
+    GFX_TRY(set->ctx)
+    const uint32_t k = tfdm_set_add_nrtdsm(set->s, obj ? &obj->o : nullptr, objToWorld, userId);
+    if (index) *index = k;
+    GFX_CATCH(set->ctx)
+}
 int gfx_tfdm_set_transform(gfx_tfdm_set* set, uint32_t index, const float objToWorld[12]) {
     if (!set) return 1;
     GFX_TRY(set->ctx)

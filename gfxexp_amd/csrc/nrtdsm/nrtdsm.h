@@ -6,6 +6,8 @@
 namespace gfx {
 
 struct NrtdsmObject : HeightMapObject {
+    tfdm::Node root;                    // nodes[0] on the host and the generation of the buffers, as TfdmObject keeps them: what a
+    uint64_t generation = 0;            // member of an instance set needs (tfdm/tfdm_set.hip)
     NrtdsmObject() : HeightMapObject("gfx_nrtdsm", sizeof(nrtdsm::PrismRecord)) {}
 };
 

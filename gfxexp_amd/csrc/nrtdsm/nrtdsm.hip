@@ -91,9 +91,10 @@ std::vector<nrtdsm::PrismRecord> make_records(const NrtdsmObject& o, const gfx_t
 
 void build_geometry(NrtdsmObject& o, hipStream_t stream, const gfx_tfdm_params& g, const std::vector<nrtdsm::PrismRecord>& recs) {
     const Params p = make_params(g, o.size);
-    rebuild(o, stream, recs.data(), g, p, [&](const DevBuf& records, const DevBuf& aabbs) {
+    o.root = rebuild(o, stream, recs.data(), g, p, [&](const DevBuf& records, const DevBuf& aabbs) {
         k_nrtdsm_prim<<<(o.numTriangles + 63u) / 64u, 64, 0, stream>>>(records.as<nrtdsm::PrismRecord>(), o.pyramid.as<F2>(), p, o.numTriangles, aabbs.as<Box>());
     });
+    ++o.generation;
 }
 
 } // namespace

@@ -2,14 +2,16 @@
 // gfx_tfdm_set_* and gfx_trace_scene.
 #pragma once
 #include "tfdm.h"
-#include "tfdm_instance.hip.h"
+#include "../nrtdsm/nrtdsm.h"
+#include "../nrtdsm/nrtdsm_instance.hip.h"
 
 namespace gfx {
 
 struct TfdmSet {
     int device = 0;
     struct Member {
-        TfdmObject* obj;            // not owned: objects outlive the set
+        HeightMapObject* obj;       // not owned: objects outlive the set.  A TfdmObject or an NrtdsmObject, by `kind`
+        uint32_t kind;              // GFX_INSTANCE_TFDM / GFX_INSTANCE_NRTDSM: the kind word of the member's record (nrtdsm_instance.hip.h)
         float objToWorld[12];
         float prevObjToWorld[12];   // where the instance was: the transform tfdm_set_move replaced (add and tfdm_set_transform: objToWorld)
         uint32_t userId;
@@ -20,12 +22,14 @@ struct TfdmSet {
     std::vector<tfdm::InstanceRecord> host;   // the committed table
     std::vector<float> hostMotion;  // the committed motion table: curToPrev[12] per member (tfdm_instance.hip.h make_cur_to_prev)
     bool anyBilinear = false;       // ... has a member of GFX_TFDM_BILINEAR: the instance phase launches the instantiation that can run it
+    bool anyNrtdsm = false;         // ... has an NRTDSM member: the instance phase is k_scene_instances_mixed
     DevBuf table;                   // InstanceRecord[members]
     DevBuf motion;                  // float4[3 * members], the motion table: committed together with `table`
     DevBuf plain;                   // gfx_hit[numRays] of the plain phase of a closest-hit query; grows on demand
 };
 
 uint32_t tfdm_set_add(TfdmSet& s, TfdmObject* obj, const float objToWorld[12], uint32_t userId);
+uint32_t tfdm_set_add_nrtdsm(TfdmSet& s, NrtdsmObject* obj, const float objToWorld[12], uint32_t userId);   // indices count both kinds
 void tfdm_set_transform(TfdmSet& s, uint32_t index, const float objToWorld[12]);   // the teleport: prev <- cur <- objToWorld
 void tfdm_set_move(TfdmSet& s, uint32_t index, const float objToWorld[12]);        // prev <- cur, cur <- objToWorld
 void tfdm_set_commit(TfdmSet& s, hipStream_t stream);

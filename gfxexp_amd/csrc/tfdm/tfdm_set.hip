@@ -11,8 +11,14 @@
 //                    instance no lane of the wave enters is skipped by ballot.  BILINEAR: the instantiation that can run a member of
 //                    GFX_TFDM_BILINEAR (its mode is read through the same wave-uniform record); launched only for a set that has
 //                    one, so a set of Box and TwoTriangle members runs the code it ran before that mode existed.
+//   ... mixed        k_scene_instances_mixed<ANY_HIT, BILINEAR>: the same phase for a set that has an NRTDSM member (gfx_tfdm_set_add_nrtdsm).
+//                    Same launch shape, same walk over all members in index order; after the box test and the ballot skip a lane
+//                    branches on the record's kind word, which is wave-uniform like the rest of the record, to tfdm::trace_ray or
+//                    nrtdsm::trace_ray (nrtdsm/nrtdsm_instance.hip.h).  One walk, not one per kind: a later phase accepts only
+//                    t < tmax, so on equal distance a higher-index member of the first phase would beat a lower-index one of the
+//                    second.  Launched only for a set with such a member: a set of TFDM members launches what it always did.
 //
-// Register count, scratch and occupancy: DESIGN.md sections 15 and 18.
+// Register count, scratch and occupancy: DESIGN.md sections 15, 18 and 22.
 #include <algorithm>
 #include <cstring>
 #include "tfdm_set.h"
@@ -93,24 +99,117 @@ __global__ void __launch_bounds__(kSceneBlock) k_scene_instances(const InstanceR
     }
 }
 
-void check_member(const TfdmSet& s, const TfdmObject* obj) {
+// The instance phase over members of both kinds.  k_scene_instances above stays as it is for sets without an NRTDSM member, so
+// their instruction stream does not change; this is its text with the branch on the kind and the second set of counters.
+template <bool ANY_HIT, bool BILINEAR>
+__global__ void __launch_bounds__(kSceneBlock) k_scene_instances_mixed(const InstanceRecord* __restrict__ table, uint32_t numInstances, const float4* __restrict__ rayOrgTmin,
+                                                                       const float4* __restrict__ rayDirTmax, uint32_t numRays, const uint32_t* __restrict__ numRaysPtr,
+                                                                       const void* plain, void* out, unsigned long long* __restrict__ counters) {
+    __shared__ uint2 s_stack[kStackDepth * kSceneBlock];
+    if (numRaysPtr) {                            // a device-side count: the launch covers the queue capacity
+        const uint32_t count = *numRaysPtr;
+        numRays = count < numRays ? count : numRays;
+        if (blockIdx.x * kSceneBlock >= numRays) return;
+    }
+    const uint32_t i = blockIdx.x * kSceneBlock + threadIdx.x;
+    const bool live = i < numRays;
+    TraceStats ts;                               // of the TFDM members
+    ts.aabbTests = 0u; ts.leafTests = 0u; ts.primTests = 0u;
+    nrtdsm::TraceStats ns;                       // of the NRTDSM members
+    ns.aabbTests = 0u; ns.leafTests = 0u; ns.primTests = 0u; ns.maxIterations = 0u;
+    uint32_t boxTests = 0u, traversals = 0u;
+    V3 org = v3(0.0f, 0.0f, 0.0f), dir = v3(0.0f, 0.0f, 1.0f);
+    float tmin = 0.0f;
+    SceneHit best = scene_miss(0.0f);
+    bool occluded = false;
+    if (live) {
+        const float4 o = rayOrgTmin[i], d = rayDirTmax[i];
+        org = v3(o.x, o.y, o.z); dir = v3(d.x, d.y, d.z); tmin = o.w;
+        best = scene_miss(d.w);
+        if (plain) {
+            if (ANY_HIT) occluded = static_cast<const uint32_t*>(plain)[i] != 0u;
+            else {
+                const float4 h = static_cast<const float4*>(plain)[i];          // a gfx_hit
+                best = scene_start(d.w, h.x, h.y, h.z, f2b(h.w));
+            }
+        }
+    }
+    const V3 inv = v3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
+    SceneStack stack;
+    stack.col = s_stack + threadIdx.x;
+    stack.sp = 0;
+    bool open = live && !occluded && (!ANY_HIT || best.dist > tmin);       // as k_scene_instances
+    for (uint32_t k = 0; k < numInstances; ++k) {
+        const InstanceRecord& r = table[k];
+        bool enter = false;
+        if (open) { ++boxTests; enter = world_box_hit(r, org, inv, tmin, best.dist); }
+        if (__ballot(enter) == 0ull) continue;
+        if (enter) {
+            ++traversals;
+            bool hit;
+            if (nrtdsm::instance_kind(r) == nrtdsm::kKindNrtdsm) hit = nrtdsm::scene_instance_nrtdsm<ANY_HIT>(r, k, org, dir, tmin, stack, best, ns);
+            else hit = scene_instance_local<ANY_HIT, BILINEAR>(r, k, org, dir, tmin, stack, best, ts);
+            if (hit && ANY_HIT) { occluded = true; open = false; }
+        }
+    }
+    if (live) {
+        if (ANY_HIT) static_cast<uint32_t*>(out)[i] = occluded ? 1u : 0u;
+        else {
+            float4* h = static_cast<float4*>(out) + 2u * i;
+            h[0] = make_float4(best.dist, best.bcB, best.bcC, b2f(best.index));
+            h[1] = make_float4(best.normal.x, best.normal.y, best.normal.z, b2f(best.where));
+        }
+    }
+    if (counters) {                      // per wave, one atomic each; [0..3] sum over both kinds
+        const uint32_t a = wave_sum(ts.aabbTests + ns.aabbTests), l = wave_sum(ts.leafTests + ns.leafTests), n = wave_sum(live ? 1u : 0u);
+        const uint32_t t = wave_sum(ts.primTests + ns.primTests), b = wave_sum(boxTests), v = wave_sum(traversals);
+        if ((threadIdx.x & 63u) == 0) {
+            atomicAdd(counters + 0, a); atomicAdd(counters + 1, l); atomicAdd(counters + 2, n); atomicAdd(counters + 3, t);
+            atomicAdd(counters + 4, b); atomicAdd(counters + 5, v);
+        }
+    }
+}
+
+void check_member(const TfdmSet& s, const DisplacedObject* obj) {
     if (!obj) throw HipError("gfx_tfdm_set: null object");
     if (obj->device != s.device) throw HipError("gfx_tfdm_set: the object belongs to another device");
 }
 
-} // namespace
-
-uint32_t tfdm_set_add(TfdmSet& s, TfdmObject* obj, const float objToWorld[12], uint32_t userId) {
+uint32_t add_member(TfdmSet& s, HeightMapObject* obj, uint32_t kind, const float objToWorld[12], uint32_t userId, const char* who) {
     check_member(s, obj);
-    if (!objToWorld) throw HipError("gfx_tfdm_set_add: null transform");
-    if (s.members.size() >= kMaxInstances) throw HipError("gfx_tfdm_set_add: a set holds at most 1024 instances");
+    if (!objToWorld) throw HipError(std::string(who) + ": null transform");
+    if (s.members.size() >= kMaxInstances) throw HipError(std::string(who) + ": a set holds at most 1024 instances");
     TfdmSet::Member m;
-    m.obj = obj; m.userId = userId; m.generation = 0;
+    m.obj = obj; m.kind = kind; m.userId = userId; m.generation = 0;
     std::memcpy(m.objToWorld, objToWorld, sizeof(m.objToWorld));
     std::memcpy(m.prevObjToWorld, objToWorld, sizeof(m.prevObjToWorld));
     s.members.push_back(m);
     s.dirty = true;
     return static_cast<uint32_t>(s.members.size() - 1);
+}
+
+// root and generation live in the two derived objects; the kind says which one `obj` is
+bool is_nrtdsm(const TfdmSet::Member& m) { return m.kind == GFX_INSTANCE_NRTDSM; }
+uint64_t generation_of(const TfdmSet::Member& m) {
+    return is_nrtdsm(m) ? static_cast<const NrtdsmObject*>(m.obj)->generation : static_cast<const TfdmObject*>(m.obj)->generation;
+}
+const Node& root_of(const TfdmSet::Member& m) {
+    return is_nrtdsm(m) ? static_cast<const NrtdsmObject*>(m.obj)->root : static_cast<const TfdmObject*>(m.obj)->root;
+}
+bool has_nrtdsm(const TfdmSet& s) {
+    for (const TfdmSet::Member& m : s.members) if (is_nrtdsm(m)) return true;
+    return false;
+}
+const char* const kNotRendered = "the set has an NRTDSM instance; NRTDSM instances are traced (gfx_trace_scene) but not rendered";
+
+} // namespace
+
+uint32_t tfdm_set_add(TfdmSet& s, TfdmObject* obj, const float objToWorld[12], uint32_t userId) {
+    return add_member(s, obj, GFX_INSTANCE_TFDM, objToWorld, userId, "gfx_tfdm_set_add");
+}
+
+uint32_t tfdm_set_add_nrtdsm(TfdmSet& s, NrtdsmObject* obj, const float objToWorld[12], uint32_t userId) {
+    return add_member(s, obj, GFX_INSTANCE_NRTDSM, objToWorld, userId, "gfx_tfdm_set_add_nrtdsm");
 }
 
 void tfdm_set_transform(TfdmSet& s, uint32_t index, const float objToWorld[12]) {
@@ -137,9 +236,9 @@ void tfdm_set_commit(TfdmSet& s, hipStream_t stream) {
     std::vector<float> motion(12 * s.members.size());
     for (size_t k = 0; k < s.members.size(); ++k) {
         const TfdmSet::Member& m = s.members[k];
-        const TfdmObject& o = *m.obj;
-        const char* err = make_instance(m.objToWorld, o.root, o.nodes.as<Node>(), o.records.as<TriRecord>(), o.heights.as<float>(), o.pyramid.as<F2>(), o.params,
-                                        m.userId, recs[k]);
+        const HeightMapObject& o = *m.obj;
+        const char* err = nrtdsm::make_instance_of_kind(m.kind, m.objToWorld, root_of(m), o.nodes.as<Node>(), o.records.p, o.heights.as<float>(), o.pyramid.as<F2>(),
+                                                        o.params, m.userId, recs[k]);
         if (!err) err = make_cur_to_prev(m.prevObjToWorld, m.objToWorld, motion.data() + 12 * k);
         if (err) throw HipError("gfx_tfdm_set_commit: instance " + std::to_string(k) + ": " + err);
     }
@@ -153,8 +252,12 @@ void tfdm_set_commit(TfdmSet& s, hipStream_t stream) {
     s.host.swap(recs);
     s.hostMotion.swap(motion);
     s.anyBilinear = false;
-    for (const InstanceRecord& r : s.host) s.anyBilinear = s.anyBilinear || r.params.local == kBilinear;
-    for (TfdmSet::Member& m : s.members) m.generation = m.obj->generation;
+    s.anyNrtdsm = false;
+    for (const InstanceRecord& r : s.host) {
+        s.anyBilinear = s.anyBilinear || r.params.local == kBilinear;
+        s.anyNrtdsm = s.anyNrtdsm || nrtdsm::instance_kind(r) == nrtdsm::kKindNrtdsm;
+    }
+    for (TfdmSet::Member& m : s.members) m.generation = generation_of(m);
     s.dirty = false;
 }
 
@@ -183,8 +286,9 @@ void trace_scene_check_set(const TfdmSet& set, int device, const char* who) {
     if (set.device != device) throw HipError(w + ": the instance set belongs to another device");
     if (set.dirty) throw HipError(w + ": the instance set has an add or a transform that is not committed (gfx_tfdm_set_commit)");
     for (size_t k = 0; k < set.members.size(); ++k)
-        if (set.members[k].generation != set.members[k].obj->generation)
-            throw HipError(w + ": instance " + std::to_string(k) + "'s object had gfx_tfdm_set_params after the set was committed; commit the set again");
+        if (set.members[k].generation != generation_of(set.members[k]))
+            throw HipError(w + ": instance " + std::to_string(k) + "'s object had " + (is_nrtdsm(set.members[k]) ? "gfx_nrtdsm_set_params" : "gfx_tfdm_set_params") +
+                           " after the set was committed; commit the set again");
 }
 
 void trace_scene_launch(Context& ctx, hipStream_t stream, const SceneTrace& s) {
@@ -218,7 +322,11 @@ void trace_scene_launch(Context& ctx, hipStream_t stream, const SceneTrace& s) {
     auto launch = [&](auto kernel) {
         kernel<<<blocks, kSceneBlock, 0, stream>>>(table, numInstances, s.rayOrgTmin, s.rayDirTmax, s.numRays, s.numRaysPtr, plain, s.out, cnt);
     };
-    if (!(numInstances && s.set->anyBilinear)) launch(any ? k_scene_instances<true, false> : k_scene_instances<false, false>);
+    if (numInstances && s.set->anyNrtdsm) {
+        if (!s.set->anyBilinear) launch(any ? k_scene_instances_mixed<true, false> : k_scene_instances_mixed<false, false>);
+        else launch(any ? k_scene_instances_mixed<true, true> : k_scene_instances_mixed<false, true>);
+    }
+    else if (!(numInstances && s.set->anyBilinear)) launch(any ? k_scene_instances<true, false> : k_scene_instances<false, false>);
     else launch(any ? k_scene_instances<true, true> : k_scene_instances<false, true>);
     GFX_HIP(hipGetLastError());
 }
@@ -229,6 +337,7 @@ void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint3
         throw HipError("gfx_scene_bind_displaced_passes: unknown bit in the pass mask " + std::to_string(passMask));
     if (!set) { b.set = nullptr; b.geomSlots.clear(); b.passMask = 0u; return; }
     if (set->device != ctx.device) throw HipError("gfx_scene_bind_displaced: the instance set belongs to another device");
+    if (has_nrtdsm(*set)) throw HipError(std::string("gfx_scene_bind_displaced: ") + kNotRendered);
     if (n != set->members.size())
         throw HipError("gfx_scene_bind_displaced: " + std::to_string(n) + " geometry slots for a set of " + std::to_string(set->members.size()) + " instances");
     if (n && !geomSlots) throw HipError("gfx_scene_bind_displaced: null geometry slots");
@@ -254,6 +363,7 @@ void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint3
 void displaced_check(Context& ctx, const char* who) {
     const DisplacedBinding& b = ctx.displaced;
     trace_scene_check_set(*b.set, ctx.device, who);
+    if (has_nrtdsm(*b.set)) throw HipError(std::string(who) + ": " + kNotRendered);      // a member added after the bind
     if (b.geomSlots.size() != b.set->members.size())
         throw HipError(std::string(who) + ": the bound instance set has grown since gfx_scene_bind_displaced; bind it again");
     for (size_t k = 0; k < b.geomSlots.size(); ++k) {

@@ -928,6 +928,14 @@ int gfx_shell_size(gfx_ctx* ctx, gfx_shell* obj, int what, size_t* bytes);
 typedef struct gfx_tfdm_set gfx_tfdm_set;
 int gfx_tfdm_set_create(gfx_ctx* ctx, gfx_tfdm_set** out);
 int gfx_tfdm_set_add(gfx_tfdm_set* set, gfx_tfdm* obj, const float objToWorld[12], uint32_t userId, uint32_t* index);
+/* A gfx_nrtdsm object as a member of the set, next to gfx_tfdm members in any order: the same rules as
+ * gfx_tfdm_set_add (a null object, an object of another device and a 1025th member are refused), and *index counts all members in
+ * add order, whatever their kind.  Transform, move, commit, both reads and gfx_trace_scene treat it as any member; gfx_nrtdsm_set_params
+ * on it asks for a new commit as gfx_tfdm_set_params does.  The kind of a member is the word after boxHi of its record.  Such a set is
+ * traced but not rendered: gfx_scene_bind_displaced and gfx_scene_bind_displaced_passes refuse it. */
+#define GFX_INSTANCE_TFDM 0u
+#define GFX_INSTANCE_NRTDSM 1u
+int gfx_tfdm_set_add_nrtdsm(gfx_tfdm_set* set, gfx_nrtdsm* obj, const float objToWorld[12], uint32_t userId, uint32_t* index);
 int gfx_tfdm_set_transform(gfx_tfdm_set* set, uint32_t index, const float objToWorld[12]);
 int gfx_tfdm_set_move(gfx_tfdm_set* set, uint32_t index, const float objToWorld[12]);
 int gfx_tfdm_set_commit(gfx_ctx* ctx, void* stream, gfx_tfdm_set* set);
@@ -951,7 +959,8 @@ typedef struct gfx_scene_hit { float dist, bcB, bcC; uint32_t index; float norma
  * GFX_TRACE_CLOSEST: dOut = gfx_scene_hit[numRays]; GFX_TRACE_ANY: dOut = uint32_t[numRays] (1 = occluded).  Distances are the
  * world ray's parameter (object-space directions are not renormalised).  dCounters (optional, device u64[8], added to): [0..3]
  * as gfx_tfdm_trace, [4] world-box tests, [5] object-space traversals started.  Alignment as gfx_tfdm_trace.  A set with an
- * uncommitted add or transform, or with a member whose gfx_tfdm_set_params ran after the commit, is refused with a message. */
+ * uncommitted add or transform, or with a member whose gfx_tfdm_set_params (gfx_nrtdsm_set_params) ran after the commit, is refused
+ * with a message.  Members of both kinds are walked in one index order, so the rule above holds across kinds; [0..3] sum over both. */
 int gfx_trace_scene(gfx_ctx* ctx, void* stream, uint64_t accel, gfx_tfdm_set* set, int mode, const void* dRayOrgTmin, const void* dRayDirTmax,
                     uint32_t numRays, void* dOut, void* dCounters);
 

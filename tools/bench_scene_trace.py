@@ -1,6 +1,6 @@
 """gfx_trace_scene against the chain of calls it replaces.
 
-    python tools/bench_scene_trace.py [--size 1024] [--iters 20] [--width 1920] [--height 1080] [--step-timeout 300]
+    python tools/bench_scene_trace.py [--nrtdsm] [--size 1024] [--iters 20] [--width 1920] [--height 1080] [--step-timeout 300]
 
 1920 x 1080 primary rays on the scene of tfdm_common.mixed_scene (a plain teapot on a displaced ground quad, a displaced wall behind
 it, one size x size height map):
@@ -10,6 +10,15 @@ it, one size x size height map):
           TwoTriangle): the set then runs the Bilinear-capable instance phase
   chain   gfx_trace, then per instance a ray transform on the user's side (torch), gfx_tfdm_trace with tmax = the best distance so
           far, and a merge (torch): what a caller had to do before
+
+With --nrtdsm the steps are
+
+  call_nrtdsm    one gfx_trace_scene on the set whose wall is an NRTDSM member (gfx_tfdm_set_add_nrtdsm) of the same mesh and map:
+                 the mixed instance phase, k_scene_instances_mixed
+  chain_nrtdsm   the chain that call replaces: gfx_trace, then per member the torch ray transform, gfx_tfdm_trace (the ground) or
+                 gfx_nrtdsm_trace (the wall) with tmax = the best distance so far, and the torch merge
+
+both in the same run, and the result has "chain_nrtdsm_over_call_nrtdsm".
 
 Per step: microseconds per launch (HIP events around --iters launches after 3 warm-up launches), Mrays/s; for the call the
 traversal counters per ray from a counting launch of its own; and whether both agree on hit or miss and on the distance (the
@@ -32,6 +41,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
 STEPS = ["call", "call_bilinear", "chain"]
+NRTDSM_STEPS = ["call_nrtdsm", "chain_nrtdsm"]
 
 
 def _arg(argv, name, default):
@@ -65,8 +75,11 @@ def step(name, size, iters, w, h):
     if name == "call_bilinear":
         gp_smooth = api.tfdm_params(h_scale=gp.hScale, tex_scale=(gp.texScale[0], gp.texScale[1]), local_intersection=api.TFDM_BILINEAR)
         smooth = api.Tfdm(ctx, v, t, heights, gp_smooth)
-    for k, (m, uid) in enumerate(instances):
-        tset.add(smooth if smooth is not None and k == len(instances) - 1 else tf, m, uid)
+    if name in NRTDSM_STEPS:
+        smooth = api.Nrtdsm(ctx, v, t, heights, api.tfdm_params(h_scale=gp.hScale, tex_scale=(gp.texScale[0], gp.texScale[1])))
+    objects = [smooth if smooth is not None and k == len(instances) - 1 else tf for k in range(len(instances))]
+    for obj, (m, uid) in zip(objects, instances):
+        tset.add(obj, m, uid)
     tset.commit()
     n = w * h
     org, dirs = api.camera_rays(K.look_at_camera(w, h, pos, target), w, h)
@@ -78,7 +91,7 @@ def step(name, size, iters, w, h):
     def call():
         api.trace_scene(ctx, accel, tset, api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_scene.data_ptr(), stream=stream)
 
-    if name in ("call", "call_bilinear"):
+    if name in ("call", "call_bilinear", "call_nrtdsm"):
         secs = timed(call, iters)
         d_cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
         api.trace_scene(ctx, accel, tset, api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_scene.data_ptr(), d_cnt.data_ptr(), stream=stream)
@@ -111,7 +124,7 @@ def step(name, size, iters, w, h):
             d_oo[:, 3] = d_org[:, 3]
             d_od[:, :3] = d_dir[:, :3] @ m[:, :3].T
             d_od[:, 3] = best
-            tf.trace(api.TRACE_CLOSEST, d_oo.data_ptr(), d_od.data_ptr(), n, d_hit.data_ptr(), stream=stream)
+            objects[k].trace(api.TRACE_CLOSEST, d_oo.data_ptr(), d_od.data_ptr(), n, d_hit.data_ptr(), stream=stream)
             th = d_hit.view(n, 8)
             win = th[:, 3] != -1
             torch.where(win, th[:, 0].view(torch.float32), best, out=best)
@@ -138,7 +151,8 @@ def main(argv):
         return 0
     limit = _arg(argv, "--step-timeout", 300)
     result = {"metric": "scene_trace", "size": size, "iters": iters, "width": w, "height": h}
-    for name in STEPS:
+    steps = NRTDSM_STEPS if "--nrtdsm" in argv else STEPS
+    for name in steps:
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name, "--size", str(size), "--iters", str(iters),
                "--width", str(w), "--height", str(h)]
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -148,7 +162,10 @@ def main(argv):
             print(json.dumps(result))
             return 1
         result[name] = json.loads(line[-1][len("STEP_RESULT "):])
-    result["chain_over_call"] = round(result["chain"]["us"] / result["call"]["us"], 3)
+    if steps is NRTDSM_STEPS:
+        result["chain_nrtdsm_over_call_nrtdsm"] = round(result["chain_nrtdsm"]["us"] / result["call_nrtdsm"]["us"], 3)
+    else:
+        result["chain_over_call"] = round(result["chain"]["us"] / result["call"]["us"], 3)
     print(json.dumps(result))
     return 0
 

@@ -3,12 +3,16 @@
 // Python).  A 3 x 3-quad spherical cap with shared radial normals under a 16 x 16 two-sine map, plain and under a wrapped and
 // rotated texture transform: 1500 rays toward the cap, rays from far away, rays along base edges, rays that are NaN, infinite
 // or of zero direction.  Checks what needs no reference: any-hit answers where closest-hit does, nothing in a hit is not finite,
-// a miss reports tmax, the descent stays below its ceiling.  Exit status 0 and "ok" = clean.
+// a miss reports tmax, the descent stays below its ceiling.  Then the same object as two NRTDSM instances of a scene (the host
+// compilation of csrc/nrtdsm/nrtdsm_instance.hip.h, tests/scene_nrtdsm_host.cpp), as it is and under a mirrored, non-uniformly
+// scaled transform, over the same rays: the walk with the world-box cull equals the walk without it, and any-hit answers where
+// closest-hit does.  Exit status 0 and "ok" = clean.
 #include <cmath>
 #include <cstdio>
 #include <limits>
 #include "../tests/tfdm_host.cpp"
 #include "../tests/nrtdsm_host.cpp"
+#include "../tests/scene_nrtdsm_host.cpp"
 
 namespace {
 struct Rng { uint64_t s; double next() { s = s * 6364136223846793005ull + 1442695040888963407ull; return static_cast<double>(s >> 11) * (1.0 / 9007199254740992.0); } };
@@ -108,6 +112,26 @@ int main() {
         std::printf("transform %d: %u of %u rays hit, %.2f box tests and %.2f leaf tests per ray, at most %u descent iterations\n", xf, numHits, n,
                     static_cast<double>(counters[0]) / n, static_cast<double>(counters[1]) / n, worst);
         if (numHits < n / 4 || worst >= nrtdsm_host_max_descent()) { std::printf("transform %d: the ray set barely hits, or the descent reached its ceiling\n", xf); return 1; }
+        // ... as two instances of a scene
+        const float ident[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 }, mirrored[12] = { -0.5f, 0, 0, 0.25f, 0, 0, 2, -1.5f, 0, 1, 0, 0.125f };
+        const uint64_t ptrs[4] = { reinterpret_cast<uint64_t>(nodes.data()), reinterpret_cast<uint64_t>(rec.data()), reinterpret_cast<uint64_t>(levels.data()),
+                                   reinterpret_cast<uint64_t>(pyramid.data()) };
+        InstanceRecord table[2];
+        if (scene_nrtdsm_host_make_instance(nr::kKindNrtdsm, ident, &nodes[0], ptrs, &p, 1, &table[0], msg, sizeof(msg)) ||
+            scene_nrtdsm_host_make_instance(nr::kKindNrtdsm, mirrored, &nodes[0], ptrs, &p, 2, &table[1], msg, sizeof(msg))) { std::printf("make_instance: %s\n", msg); return 1; }
+        std::vector<gfx_scene_hit> culled(n), full(n);
+        std::vector<uint32_t> occluded(n);
+        scene_nrtdsm_host_trace(table, 2, nullptr, 0, org.data(), dir.data(), n, culled.data(), nullptr, 1);
+        scene_nrtdsm_host_trace(table, 2, nullptr, 0, org.data(), dir.data(), n, full.data(), nullptr, 0);
+        scene_nrtdsm_host_trace(table, 2, nullptr, 1, org.data(), dir.data(), n, occluded.data(), nullptr, 1);
+        uint32_t sceneHits = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            const bool hit = culled[i].where != 0xFFFFFFFFu;
+            sceneHits += hit ? 1u : 0u;
+            if (std::memcmp(&culled[i], &full[i], sizeof(gfx_scene_hit)) != 0 || (occluded[i] != 0u) != hit || (hit && (culled[i].where >> 1) > 1u)) { std::printf("transform %d: scene ray %u is wrong\n", xf, i); return 1; }
+        }
+        std::printf("transform %d: %u of %u rays hit one of the two instances\n", xf, sceneHits, n);
+        if (sceneHits < numHits) { std::printf("transform %d: the scene of two instances is hit less often than the object alone\n", xf); return 1; }
     }
     std::printf("ok\n");
     return 0;

@@ -27,6 +27,11 @@ brightness like a checkerboard).
 ONE gfx_trace_scene call.  Writes <out>_normal.png (world-space normals of the displaced hits; plain hits grey), <out>_depth.png
 and <out>_instance.png (plain geometry grey, every displaced instance a colour of its own, misses black).
 
+    python tools/tfdm_view.py --scene --nrtdsm [--size 256] [--width 960] [--height-px 540] [--out tfdm_view]
+
+--scene --nrtdsm: the same scene with the wall an NRTDSM member of the set (gfx_tfdm_set_add_nrtdsm; the ground stays TFDM), the same
+three images through the same ONE gfx_trace_scene call.  Such a set is traced, not rendered: --render and --restir refuse it.
+
     python tools/tfdm_view.py --scene --render [--frames 64] [--size 256] [--width 960] [--height-px 540] [--out tfdm_view]
 
 --render: the same scene under an emissive rectangle, path traced through the bound instance set (gfx_scene_bind_displaced: the
@@ -141,9 +146,11 @@ def scene_view(a):
     plain.upload(ctx)
     accel = ctx.accel_build()
     tf = api.Tfdm(ctx, v, t, heights, gp)
+    # --nrtdsm: the last instance (the wall) is an NRTDSM object of the same mesh, map and height scale
+    wall = api.Nrtdsm(ctx, v, t, heights, api.tfdm_params(h_scale=gp.hScale, tex_scale=(gp.texScale[0], gp.texScale[1]))) if a.nrtdsm else None
     tset = api.TfdmSet(ctx)
-    for m, uid in instances:
-        tset.add(tf, m, uid)
+    for k, (m, uid) in enumerate(instances):
+        tset.add(wall if wall is not None and k == len(instances) - 1 else tf, m, uid)
     tset.commit()
     w, h = a.width, a.height_px
     n = w * h
@@ -171,7 +178,7 @@ def scene_view(a):
     ids[is_plain, :3] = 0.5
     ids[disp, :3] = palette[(where[disp] >> 1) % len(palette)]
     api.save_image_sdr(a.out + "_instance.png", ids, w, h, sdr)
-    print(json.dumps({"scene": "teapot on displaced ground, displaced wall", "size": int(heights.shape[0]), "instances": len(tset), "rays": n,
+    print(json.dumps({"scene": "teapot on displaced ground, displaced wall", "kinds": [int(k) for k in tset.read()["pad0"]], "size": int(heights.shape[0]), "instances": len(tset), "rays": n,
                       "plain_share": round(float(is_plain.mean()), 4),
                       "instance_shares": [round(float((disp & (where >> 1 == k)).mean()), 4) for k in range(len(tset))],
                       "miss_share": round(float(miss.mean()), 4), "aabb_tests_per_ray": round(float(cnt[0]) / n, 2),
@@ -248,6 +255,8 @@ def main():
     if a.move and not (a.scene and a.restir):
         ap.error("--move goes with --scene --restir")
     if a.render or a.restir:
+        if a.nrtdsm:
+            ap.error("--nrtdsm with --scene is traced, not rendered: a set with an NRTDSM instance cannot be bound")
         return scene_render(a)
     if a.scene:
         return scene_view(a)
