@@ -190,12 +190,15 @@ def encode_hashgrid(x3, grid_bf16):
 class NrcNet:
     """fp32 master parameters + Adam/EMA state; forward/backward with the bf16 rounding contract."""
 
-    def __init__(self, pos_enc=POS_HASHGRID, num_hidden_layers=2, learning_rate=1e-2, params=None, bf16=True, grid_grad_f16=True):
+    def __init__(self, pos_enc=POS_HASHGRID, num_hidden_layers=2, learning_rate=1e-2, params=None, bf16=True, grid_grad_f16=True, grid_chunk=None):
         # grid_grad_f16: the hash-grid gradient is summed as fp16 pairs (tiny-cuda-nn scatters __half2; nrc.hip k_nrc_grid_scatter
         # sums a level table per chunk of records in LDS with ds_pk_add_f16): contributions are rounded to fp16, and so is the
         # per-entry sum of a chunk.  The order of the additions inside a chunk is not defined on the device, so the restatement
         # sums a chunk in fp32 and rounds once; the chunks are added in fp32 (gradients()).
+        # grid_chunk: records per fp16-summed chunk instead of the k_nrc_grid_scatter rule (GFX_NRC_GRID_GRAD=f16atomic sums the whole
+        # batch in fp16: grid_chunk = the batch size); None = the rule.
         self.grid_grad_f16 = grid_grad_f16 and bf16
+        self.grid_chunk = grid_chunk
         self.pos_enc, self.n_hidden, self.lr = pos_enc, num_hidden_layers, np.float32(learning_rate)
         self.rnd = bf16_round if bf16 else (lambda a: np.ascontiguousarray(a, np.float32))   # bf16=False: plain fp32 (gradient checks)
         self.table, self.grid_off, self.total = layout(pos_enc, num_hidden_layers)
@@ -250,7 +253,7 @@ class NrcNet:
         grad = np.float32(loss_scale) * np.float32(2) * diff / denom / n_total
         return loss.astype(np.float32), grad.astype(np.float32)
 
-    def gradients(self, x, target, loss_scale=128.0):
+    def gradients(self, x, target, loss_scale=128.0, grid_chunk=None):
         """(mean loss, dL/dparams * loss_scale) for the TRAINING parameters."""
         p = self.params
         pred, acts, mats = self.forward(x, p, keep=True)
@@ -276,6 +279,9 @@ class NrcNet:
             # a chunk's contributions are summed in fp16 (LDS atomics, order undefined -- restated as an fp32 sum rounded once), the
             # chunks' sums are added in fp32 in chunk order
             chunk = max(256, ((n_rec + 15) // 16 + 63) // 64 * 64) if self.grid_grad_f16 else n_rec
+            grid_chunk = self.grid_chunk if grid_chunk is None else grid_chunk
+            if grid_chunk is not None and self.grid_grad_f16:
+                chunk = int(grid_chunk)
             corners = hash_corners(np.ascontiguousarray(x[:, 0:3], np.float32))
             total = np.zeros((entries, HASH_FEATURES), np.float32)
             for begin in range(0, n_rec, chunk):
