@@ -213,7 +213,7 @@ def abi_mirrors():
             "gfx_denoiser_settings": GfxDenoiserSettings, "gfx_denoiser_inputs": GfxDenoiserInputs,
             "gfx_denoiser_history_buffers": GfxDenoiserHistoryBuffers, "gfx_taa_inputs": GfxTaaInputs, "gfxh_dds_info": GfxhDdsInfo,
             "gfxh_image_desc": GfxhImageDesc, "gfx_tfdm_params": GfxTfdmParams, "gfx_tfdm_hit": GfxTfdmHit, "gfx_scene_hit": GfxSceneHit,
-            "gfx_shell_hit": GfxShellHit, "gfx_shell_geom": GfxShellGeom}
+            "gfx_shell_hit": GfxShellHit, "gfx_shell_geom": GfxShellGeom, "gfx_scene_shell_part": GfxSceneShellPart}
 
 
 class RcclExchange:
@@ -340,7 +340,7 @@ C_ABI_SYMBOLS = [
     "gfx_tfdm_default_params", "gfx_tfdm_create", "gfx_tfdm_set_params", "gfx_tfdm_destroy", "gfx_tfdm_trace", "gfx_tfdm_read", "gfx_tfdm_size",
     "gfx_tfdm_set_create", "gfx_tfdm_set_add", "gfx_tfdm_set_transform", "gfx_tfdm_set_commit", "gfx_tfdm_set_read", "gfx_tfdm_set_destroy", "gfx_trace_scene",
     "gfx_scene_bind_displaced", "gfx_restir_primary_rays", "gfx_scene_bind_displaced_passes", "gfx_restir_last_rays",
-    "gfx_tfdm_set_move", "gfx_tfdm_set_read_motion", "gfx_tfdm_set_add_nrtdsm",
+    "gfx_tfdm_set_move", "gfx_tfdm_set_read_motion", "gfx_tfdm_set_add_nrtdsm", "gfx_tfdm_set_add_shell", "gfx_trace_scene_ex",
     "gfx_nrtdsm_create", "gfx_nrtdsm_set_params", "gfx_nrtdsm_destroy", "gfx_nrtdsm_trace", "gfx_nrtdsm_read", "gfx_nrtdsm_size",
     "gfx_shell_create", "gfx_shell_set_params", "gfx_shell_set_geometry", "gfx_shell_destroy", "gfx_shell_trace", "gfx_shell_read", "gfx_shell_size",
 ]
@@ -1433,11 +1433,17 @@ TFDM_INSTANCE_DTYPE = np.dtype([("objToWorld", "<f4", 12), ("worldToObj", "<f4",
                                 ("nodes", "<u8"), ("records", "<u8"), ("heights", "<u8"), ("pyramid", "<u8"), ("params", "<u4", 8)])
 TFDM_MOTION_DTYPE = np.dtype([("curToPrev", "<f4", 12)])      # the motion table of a set: row-major 3 x 4, previous * inverse(current)
 TFDM_SET_MAX_INSTANCES = 1024
-INSTANCE_TFDM, INSTANCE_NRTDSM = 0, 1      # GFX_INSTANCE_*: the kind of a set member, the "pad0" word of its record
+INSTANCE_TFDM, INSTANCE_NRTDSM, INSTANCE_SHELL = 0, 1, 2      # GFX_INSTANCE_*: the kind of a set member, the "pad0" word of its record
+# gfx_scene_shell_part: what only a shell member's closest hit has, the side output of trace_scene(d_shell_part=...); zeros otherwise
+SCENE_SHELL_PART_DTYPE = np.dtype([("shellTriangle", "<u4"), ("shellGeom", "<u4"), ("tile", "<i4", 2)])
 
 
 class GfxSceneHit(C.Structure):
     _fields_ = [("dist", C.c_float), ("bcB", C.c_float), ("bcC", C.c_float), ("index", C.c_uint32), ("normal", C.c_float * 3), ("where", C.c_uint32)]
+
+
+class GfxSceneShellPart(C.Structure):
+    _fields_ = [("shellTriangle", C.c_uint32), ("shellGeom", C.c_uint32), ("tile", C.c_int32 * 2)]
 
 
 def _xfm12(m):
@@ -1450,10 +1456,10 @@ def _xfm12(m):
 
 
 class TfdmSet:
-    """gfx_tfdm_set: Tfdm and Nrtdsm objects, in any order, under object-to-world transforms (row-major 3 x 4, or a 4 x 4 whose last
-    row is dropped), the displaced instances of trace_scene.  A set with an Nrtdsm member is traced but not rendered
+    """gfx_tfdm_set: Tfdm, Nrtdsm and Shell objects, in any order, under object-to-world transforms (row-major 3 x 4, or a 4 x 4 whose
+    last row is dropped), the displaced instances of trace_scene.  A set with an Nrtdsm or a Shell member is traced but not rendered
     (Context.bind_displaced refuses it).  commit() before the first query, and again after add / set_transform / move / a member's
-    set_params.  move() is the per-frame update of a moving instance (previous <- current, current <- the new transform: its
+    set_params (a Shell's set_geometry).  move() is the per-frame update of a moving instance (previous <- current, current <- the new transform: its
     pixels get its motion vector); set_transform() is the teleport (previous <- current <- the new transform, no motion).  The set
     keeps its members alive."""
 
@@ -1471,7 +1477,7 @@ class TfdmSet:
     def add(self, obj, obj_to_world, user_id=0):
         x = _xfm12(obj_to_world)
         index = C.c_uint32()
-        entry = self.L.gfx_tfdm_set_add_nrtdsm if isinstance(obj, Nrtdsm) else self.L.gfx_tfdm_set_add
+        entry = self.L.gfx_tfdm_set_add_shell if isinstance(obj, Shell) else self.L.gfx_tfdm_set_add_nrtdsm if isinstance(obj, Nrtdsm) else self.L.gfx_tfdm_set_add
         self.ctx._check(entry(self.h, obj.h, _p(x), C.c_uint32(user_id), C.byref(index)))
         self.objects.append(obj)
         return index.value
@@ -1512,11 +1518,16 @@ class TfdmSet:
             pass
 
 
-def trace_scene(ctx, accel, tfdm_set, mode, d_ray_org, d_ray_dir, num_rays, d_out, d_counters=0, stream=0):
+def trace_scene(ctx, accel, tfdm_set, mode, d_ray_org, d_ray_dir, num_rays, d_out, d_counters=0, stream=0, d_shell_part=0):
     """gfx_trace_scene: world rays against the BVH8 `accel` (0: none) and the displaced instances of `tfdm_set` (None: none).
-    CLOSEST: d_out = SCENE_HIT_DTYPE[num_rays]; ANY: uint32[num_rays].  d_counters: device u64[8], added to."""
-    ctx._check(lib().gfx_trace_scene(ctx.h, C.c_void_p(stream), C.c_uint64(accel or 0), tfdm_set.h if tfdm_set is not None else None, C.c_int(mode),
-                                     C.c_void_p(d_ray_org), C.c_void_p(d_ray_dir), C.c_uint32(num_rays), C.c_void_p(d_out), C.c_void_p(d_counters or None)))
+    CLOSEST: d_out = SCENE_HIT_DTYPE[num_rays]; ANY: uint32[num_rays].  d_counters: device u64[8], added to.  d_shell_part (CLOSEST,
+    gfx_trace_scene_ex): SCENE_SHELL_PART_DTYPE[num_rays], the shell triangle, geometry and tile where a Shell member wins, zeros else."""
+    args = (ctx.h, C.c_void_p(stream), C.c_uint64(accel or 0), tfdm_set.h if tfdm_set is not None else None, C.c_int(mode), C.c_void_p(d_ray_org),
+            C.c_void_p(d_ray_dir), C.c_uint32(num_rays), C.c_void_p(d_out), C.c_void_p(d_counters or None))
+    if d_shell_part:
+        ctx._check(lib().gfx_trace_scene_ex(*args, C.c_void_p(d_shell_part)))
+    else:
+        ctx._check(lib().gfx_trace_scene(*args))
 
 
 class RestirRenderer:

@@ -911,6 +911,13 @@ int gfx_tfdm_set_add_nrtdsm(gfx_tfdm_set* set, gfx_nrtdsm* obj, const float objT
     if (index) *index = k;
     GFX_CATCH(set->ctx)
 }
+int gfx_tfdm_set_add_shell(gfx_tfdm_set* set, gfx_shell* obj, const float objToWorld[12], uint32_t userId, uint32_t* index) {
+    if (!set) return 1;
+    GFX_TRY(set->ctx)
+    const uint32_t k = tfdm_set_add_shell(set->s, obj ? &obj->o : nullptr, objToWorld, userId);
+    if (index) *index = k;
+    GFX_CATCH(set->ctx)
+}
 int gfx_tfdm_set_transform(gfx_tfdm_set* set, uint32_t index, const float objToWorld[12]) {
     if (!set) return 1;
     GFX_TRY(set->ctx)
@@ -955,14 +962,18 @@ int gfx_tfdm_set_destroy(gfx_tfdm_set* set) {
     delete set;
     return 0;
 }
-int gfx_trace_scene(gfx_ctx* ctx, void* stream, uint64_t accel, gfx_tfdm_set* set, int mode, const void* dRayOrgTmin, const void* dRayDirTmax,
-                    uint32_t numRays, void* dOut, void* dCounters) {
+int gfx_trace_scene_ex(gfx_ctx* ctx, void* stream, uint64_t accel, gfx_tfdm_set* set, int mode, const void* dRayOrgTmin, const void* dRayDirTmax,
+                       uint32_t numRays, void* dOut, void* dCounters, void* dShellPart) {
     GFX_TRY(ctx)
     DevAccel dev;
     if (accel) dev = find_accel(ctx, accel)->dev();
     trace_scene(ctx->c, static_cast<hipStream_t>(stream), accel ? &dev : nullptr, set ? &set->s : nullptr, ctx->scenePlain, mode, dRayOrgTmin, dRayDirTmax,
-                numRays, dOut, dCounters);
+                numRays, dOut, dCounters, dShellPart);
     GFX_CATCH(ctx)
+}
+int gfx_trace_scene(gfx_ctx* ctx, void* stream, uint64_t accel, gfx_tfdm_set* set, int mode, const void* dRayOrgTmin, const void* dRayDirTmax,
+                    uint32_t numRays, void* dOut, void* dCounters) {
+    return gfx_trace_scene_ex(ctx, stream, accel, set, mode, dRayOrgTmin, dRayDirTmax, numRays, dOut, dCounters, nullptr);
 }
 
 int gfx_scene_bind_displaced(gfx_ctx* ctx, gfx_tfdm_set* set, const uint32_t* geomInstSlots, uint32_t n) {

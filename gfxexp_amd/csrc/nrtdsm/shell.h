@@ -8,6 +8,9 @@ namespace gfx {
 struct ShellObject : DisplacedObject {
     uint32_t numShellNodes = 0, numShellTriangles = 0;
     DevBuf shellNodes, shellTris;       // Node[numShellNodes], ShellTri[numShellTriangles]
+    tfdm::Node root;                    // nodes[0] on the host and the generation of the buffers, as NrtdsmObject keeps them: what a
+    uint64_t generation = 0;            // member of an instance set needs (tfdm/tfdm_set.hip)
+    const char* lastChange = "gfx_shell_create";    // the call that made the buffers of this generation: a stale member's message names it
     ShellObject() : DisplacedObject("gfx_shell", sizeof(nrtdsm::PrismRecord)) {}
 };
 

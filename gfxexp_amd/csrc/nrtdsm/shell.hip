@@ -100,7 +100,7 @@ void build_geometry(ShellObject& o, hipStream_t stream, const gfx_tfdm_params& g
     const Params p = shell::make_shell_params(g);
     const DevBuf& sn = fresh ? fresh->nodes : o.shellNodes;
     const DevBuf& st = fresh ? fresh->tris : o.shellTris;
-    rebuild(o, stream, recs.data(), g, p, [&](const DevBuf& records, const DevBuf& aabbs) {
+    o.root = rebuild(o, stream, recs.data(), g, p, [&](const DevBuf& records, const DevBuf& aabbs) {
         k_shell_prim<<<(o.numTriangles + 63u) / 64u, kTraceBlock, 0, stream>>>(records.as<nrtdsm::PrismRecord>(), sn.as<Node>(), st.as<shell::ShellTri>(), p, o.numTriangles, aabbs.as<Box>());
     });
     if (fresh) {
@@ -109,6 +109,7 @@ void build_geometry(ShellObject& o, hipStream_t stream, const gfx_tfdm_params& g
         o.numShellNodes = fresh->numNodes; o.numShellTriangles = fresh->numTris;
         fresh->nodes = DevBuf(); fresh->tris = DevBuf();
     }
+    ++o.generation;
 }
 
 // the shell BVH of the geometries on the device, or the refusal
@@ -144,6 +145,7 @@ void shell_init(ShellObject& o, hipStream_t stream, const void* vertices, uint32
 void shell_set_params(ShellObject& o, hipStream_t stream, const gfx_tfdm_params& g) {
     check_params(g);
     build_geometry(o, stream, g, make_records(o, g, shell::make_shell_params(g)), nullptr);
+    o.lastChange = "gfx_shell_set_params";
 }
 
 void shell_set_geometry(ShellObject& o, hipStream_t stream, const gfx_shell_geom* geoms, uint32_t numGeoms) {
@@ -151,6 +153,7 @@ void shell_set_geometry(ShellObject& o, hipStream_t stream, const gfx_shell_geom
     try {
         upload_shell("gfx_shell_set_geometry", stream, geoms, numGeoms, dev);
         build_geometry(o, stream, o.pub, make_records(o, o.pub, shell::make_shell_params(o.pub)), &dev);
+        o.lastChange = "gfx_shell_set_geometry";
     }
     catch (...) { dev.nodes.release(); dev.tris.release(); throw; }
 }

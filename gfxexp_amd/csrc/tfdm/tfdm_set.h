@@ -3,15 +3,16 @@
 #pragma once
 #include "tfdm.h"
 #include "../nrtdsm/nrtdsm.h"
-#include "../nrtdsm/nrtdsm_instance.hip.h"
+#include "../nrtdsm/shell.h"
+#include "../nrtdsm/shell_instance.hip.h"
 
 namespace gfx {
 
 struct TfdmSet {
     int device = 0;
     struct Member {
-        HeightMapObject* obj;       // not owned: objects outlive the set.  A TfdmObject or an NrtdsmObject, by `kind`
-        uint32_t kind;              // GFX_INSTANCE_TFDM / GFX_INSTANCE_NRTDSM: the kind word of the member's record (nrtdsm_instance.hip.h)
+        DisplacedObject* obj;       // not owned: objects outlive the set.  A TfdmObject, an NrtdsmObject or a ShellObject, by `kind`
+        uint32_t kind;              // GFX_INSTANCE_TFDM / _NRTDSM / _SHELL: the kind word of the member's record (nrtdsm_instance.hip.h)
         float objToWorld[12];
         float prevObjToWorld[12];   // where the instance was: the transform tfdm_set_move replaced (add and tfdm_set_transform: objToWorld)
         uint32_t userId;
@@ -23,13 +24,15 @@ struct TfdmSet {
     std::vector<float> hostMotion;  // the committed motion table: curToPrev[12] per member (tfdm_instance.hip.h make_cur_to_prev)
     bool anyBilinear = false;       // ... has a member of GFX_TFDM_BILINEAR: the instance phase launches the instantiation that can run it
     bool anyNrtdsm = false;         // ... has an NRTDSM member: the instance phase is k_scene_instances_mixed
+    bool anyShell = false;          // ... has a shell member: the instance phase is k_scene_instances_shell, whatever else the set holds
     DevBuf table;                   // InstanceRecord[members]
     DevBuf motion;                  // float4[3 * members], the motion table: committed together with `table`
     DevBuf plain;                   // gfx_hit[numRays] of the plain phase of a closest-hit query; grows on demand
 };
 
 uint32_t tfdm_set_add(TfdmSet& s, TfdmObject* obj, const float objToWorld[12], uint32_t userId);
-uint32_t tfdm_set_add_nrtdsm(TfdmSet& s, NrtdsmObject* obj, const float objToWorld[12], uint32_t userId);   // indices count both kinds
+uint32_t tfdm_set_add_nrtdsm(TfdmSet& s, NrtdsmObject* obj, const float objToWorld[12], uint32_t userId);   // indices count all kinds
+uint32_t tfdm_set_add_shell(TfdmSet& s, ShellObject* obj, const float objToWorld[12], uint32_t userId);
 void tfdm_set_transform(TfdmSet& s, uint32_t index, const float objToWorld[12]);   // the teleport: prev <- cur <- objToWorld
 void tfdm_set_move(TfdmSet& s, uint32_t index, const float objToWorld[12]);        // prev <- cur, cur <- objToWorld
 void tfdm_set_commit(TfdmSet& s, hipStream_t stream);
@@ -50,6 +53,7 @@ struct SceneTrace {
     void* out = nullptr;
     void* plainHits = nullptr;
     void* statCounters = nullptr;       // u64[8] of gfx_trace_scene, optional
+    void* shellPart = nullptr;          // gfx_scene_shell_part[numRays] of gfx_trace_scene_ex, optional: closest hits of a set with a shell member
     DevBuf* spill = nullptr; DevBuf* counters = nullptr;
     uint32_t* zeroWords[2] = { nullptr, nullptr };
     bool hintFromOut = false;           // plainHits still holds the previous launch's plain hits for the same rays
@@ -75,6 +79,6 @@ void restir_last_rays(Context& ctx, hipStream_t stream, void* dRayOrgTmin, void*
 // set == nullptr: no displaced instances; accel == nullptr: no plain geometry.  `fallbackPlain`: the plain-phase buffer of a
 // closest-hit query without a set (the context's).
 void trace_scene(Context& ctx, hipStream_t stream, const DevAccel* accel, TfdmSet* set, DevBuf& fallbackPlain, int mode, const void* dRayOrgTmin,
-                 const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters);
+                 const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters, void* dShellPart = nullptr);
 
 } // namespace gfx

@@ -17,8 +17,15 @@
 //                    nrtdsm::trace_ray (nrtdsm/nrtdsm_instance.hip.h).  One walk, not one per kind: a later phase accepts only
 //                    t < tmax, so on equal distance a higher-index member of the first phase would beat a lower-index one of the
 //                    second.  Launched only for a set with such a member: a set of TFDM members launches what it always did.
+//   ... shell        k_scene_instances_shell<ANY_HIT, BILINEAR>: the same phase for a set that has a shell member (gfx_tfdm_set_add_shell),
+//                    whatever else it holds.  The mixed walk with a third wave-uniform branch, to shell::trace_ray
+//                    (nrtdsm/shell_instance.hip.h), a second LDS column per lane for the shell BVH's stack (24 KB per block, as
+//                    k_shell_trace), the world ray and the merged hit parked in LDS during a descent (6 KB more) and, for
+//                    gfx_trace_scene_ex, a third float4 per closest hit: the shell triangle, its geometry and the tile of the
+//                    winning shell member, zeros for any other winner.  Launched only for a set with such a member: every other
+//                    set launches what it always did.
 //
-// Register count, scratch and occupancy: DESIGN.md sections 15, 18 and 22.
+// Register count, scratch and occupancy: DESIGN.md sections 15, 18, 22 and 23.
 #include <algorithm>
 #include <cstring>
 #include "tfdm_set.h"
@@ -170,12 +177,141 @@ __global__ void __launch_bounds__(kSceneBlock) k_scene_instances_mixed(const Ins
     }
 }
 
+// The instance phase over members of all three kinds, for a set that has a shell member.  The two kernels above stay as they are,
+// so sets without one run the instruction stream they ran; this is k_scene_instances_mixed's walk with the third branch and the
+// second LDS column (the shell BVH's stack; the first serves the base tree of whichever kind runs, only one runs at a time:
+// 24 KB per block, as k_shell_trace has).
+//
+// Registers.  shell::trace_ray alone needs 232 VGPRs (k_shell_trace<false>), so what the walk keeps across a
+// descent has to be small for two waves per SIMD.  Nothing but the best distance, the two stacks' pointers and the counters is:
+//   * the world ray and its reciprocal lie in LDS (s_lane, three float4 per lane) and are read back per member, for the box test
+//     and for to_object_ray;
+//   * the merged hit lies there too (three more float4: bcB, bcC, index, where / the normal / the shell part).  A step works on a
+//     hit of its own that starts as a miss at the best distance; where it finds something the lane overwrites its LDS entry,
+//     and a hit of another kind clears the shell part that way;
+//   * all kinds count into one nrtdsm::TraceStats (a TFDM step through a TraceStats of its own, added afterwards).
+// That is 6 KB more LDS, 30 KB per block: five blocks per CU by LDS, where the registers of the plain form allow four.
+// amdgpu_waves_per_eu(2, 2) holds the allocation at 256 registers; without it the closest-hit variants take 257 and 258 and
+// lose the second wave (section 23 has the table, and what the plain form costs).
+// `shellPart` (closest only, optional): one float4 per ray, zero unless the winning hit is a shell member's.
+constexpr int kLaneOrg = 0, kLaneDir = 1, kLaneInv = 2, kLaneHit = 3, kLaneNormal = 4, kLanePart = 5, kLaneSlots = 6;
+
+template <bool ANY_HIT, bool BILINEAR>
+__global__ void __launch_bounds__(kSceneBlock) __attribute__((amdgpu_waves_per_eu(2, 2)))
+k_scene_instances_shell(const InstanceRecord* __restrict__ table, uint32_t numInstances, const float4* __restrict__ rayOrgTmin, const float4* __restrict__ rayDirTmax,
+                        uint32_t numRays, const uint32_t* __restrict__ numRaysPtr, const void* plain, void* out, unsigned long long* __restrict__ counters,
+                        float4* __restrict__ shellPart) {
+    __shared__ uint2 s_stack[kStackDepth * kSceneBlock];
+    __shared__ uint2 s_shellStack[kStackDepth * kSceneBlock];
+    __shared__ float4 s_lane[kLaneSlots * kSceneBlock];          // [slot][lane]: a lane reads and writes only its own column
+    if (numRaysPtr) {                            // a device-side count: the launch covers the queue capacity
+        const uint32_t count = *numRaysPtr;
+        numRays = count < numRays ? count : numRays;
+        if (blockIdx.x * kSceneBlock >= numRays) return;
+    }
+    const uint32_t i = blockIdx.x * kSceneBlock + threadIdx.x;
+    const bool live = i < numRays;
+    nrtdsm::TraceStats ns;                       // of all members
+    ns.aabbTests = 0u; ns.leafTests = 0u; ns.primTests = 0u; ns.maxIterations = 0u;
+    uint32_t boxTests = 0u, traversals = 0u;
+    float4* const mine = s_lane + threadIdx.x;
+    float bestDist = 0.0f;
+    bool occluded = false, open;
+    {
+        V3 org = v3(0.0f, 0.0f, 0.0f), dir = v3(0.0f, 0.0f, 1.0f);
+        float tmin = 0.0f;
+        SceneHit best = scene_miss(0.0f);
+        if (live) {
+            const float4 o = rayOrgTmin[i], d = rayDirTmax[i];
+            org = v3(o.x, o.y, o.z); dir = v3(d.x, d.y, d.z); tmin = o.w;
+            best = scene_miss(d.w);
+            if (plain) {
+                if (ANY_HIT) occluded = static_cast<const uint32_t*>(plain)[i] != 0u;
+                else {
+                    const float4 h = static_cast<const float4*>(plain)[i];          // a gfx_hit
+                    best = scene_start(d.w, h.x, h.y, h.z, f2b(h.w));
+                }
+            }
+        }
+        bestDist = best.dist;
+        open = live && !occluded && (!ANY_HIT || best.dist > tmin);       // as k_scene_instances
+        mine[kLaneOrg * kSceneBlock] = make_float4(org.x, org.y, org.z, tmin);
+        mine[kLaneDir * kSceneBlock] = make_float4(dir.x, dir.y, dir.z, 0.0f);
+        mine[kLaneInv * kSceneBlock] = make_float4(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z, 0.0f);
+        if (!ANY_HIT) {
+            mine[kLaneHit * kSceneBlock] = make_float4(best.bcB, best.bcC, b2f(best.index), b2f(best.where));
+            mine[kLaneNormal * kSceneBlock] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            mine[kLanePart * kSceneBlock] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    }
+    SceneStack stack, shellStack;
+    stack.col = s_stack + threadIdx.x;
+    stack.sp = 0;
+    shellStack.col = s_shellStack + threadIdx.x;
+    shellStack.sp = 0;
+    for (uint32_t k = 0; k < numInstances; ++k) {
+        const InstanceRecord& r = table[k];
+        bool enter = false;
+        if (open) {
+            const float4 o = mine[kLaneOrg * kSceneBlock], iv = mine[kLaneInv * kSceneBlock];
+            ++boxTests;
+            enter = world_box_hit(r, v3(o.x, o.y, o.z), v3(iv.x, iv.y, iv.z), o.w, bestDist);
+        }
+        if (__ballot(enter) == 0ull) continue;
+        if (enter) {
+            const float4 o = mine[kLaneOrg * kSceneBlock], d = mine[kLaneDir * kSceneBlock];
+            const V3 org = v3(o.x, o.y, o.z), dir = v3(d.x, d.y, d.z);
+            ++traversals;
+            const uint32_t kind = nrtdsm::instance_kind(r);
+            SceneHit h = scene_miss(bestDist);                  // the step's own: a step accepts only what is closer than h.dist
+            shell::ShellPart hp = shell::shell_part_none();
+            bool hit;
+            if (kind == shell::kKindShell) hit = shell::scene_instance_shell<ANY_HIT>(r, k, org, dir, o.w, stack, shellStack, h, hp, ns);
+            else if (kind == nrtdsm::kKindNrtdsm) hit = nrtdsm::scene_instance_nrtdsm<ANY_HIT>(r, k, org, dir, o.w, stack, h, ns);
+            else {
+                TraceStats ts;
+                ts.aabbTests = 0u; ts.leafTests = 0u; ts.primTests = 0u;
+                hit = scene_instance_local<ANY_HIT, BILINEAR>(r, k, org, dir, o.w, stack, h, ts);
+                ns.aabbTests += ts.aabbTests; ns.leafTests += ts.leafTests; ns.primTests += ts.primTests;
+            }
+            if (hit) {
+                if (ANY_HIT) { occluded = true; open = false; }
+                else {
+                    bestDist = h.dist;
+                    mine[kLaneHit * kSceneBlock] = make_float4(h.bcB, h.bcC, b2f(h.index), b2f(h.where));
+                    mine[kLaneNormal * kSceneBlock] = make_float4(h.normal.x, h.normal.y, h.normal.z, 0.0f);
+                    // zeros where the winner is no shell member
+                    mine[kLanePart * kSceneBlock] = make_float4(b2f(hp.shellTriangle), b2f(hp.shellGeom), b2f(static_cast<uint32_t>(hp.tileX)), b2f(static_cast<uint32_t>(hp.tileY)));
+                }
+            }
+        }
+    }
+    if (live) {
+        if (ANY_HIT) static_cast<uint32_t*>(out)[i] = occluded ? 1u : 0u;
+        else {
+            float4* h = static_cast<float4*>(out) + 2u * i;
+            const float4 a = mine[kLaneHit * kSceneBlock], n = mine[kLaneNormal * kSceneBlock];
+            h[0] = make_float4(bestDist, a.x, a.y, a.z);
+            h[1] = make_float4(n.x, n.y, n.z, a.w);
+            if (shellPart) shellPart[i] = mine[kLanePart * kSceneBlock];
+        }
+    }
+    if (counters) {                      // per wave, one atomic each; [0..3] sum over all kinds
+        const uint32_t a = wave_sum(ns.aabbTests), l = wave_sum(ns.leafTests), n = wave_sum(live ? 1u : 0u);
+        const uint32_t t = wave_sum(ns.primTests), b = wave_sum(boxTests), v = wave_sum(traversals);
+        if ((threadIdx.x & 63u) == 0) {
+            atomicAdd(counters + 0, a); atomicAdd(counters + 1, l); atomicAdd(counters + 2, n); atomicAdd(counters + 3, t);
+            atomicAdd(counters + 4, b); atomicAdd(counters + 5, v);
+        }
+    }
+}
+
 void check_member(const TfdmSet& s, const DisplacedObject* obj) {
     if (!obj) throw HipError("gfx_tfdm_set: null object");
     if (obj->device != s.device) throw HipError("gfx_tfdm_set: the object belongs to another device");
 }
 
-uint32_t add_member(TfdmSet& s, HeightMapObject* obj, uint32_t kind, const float objToWorld[12], uint32_t userId, const char* who) {
+uint32_t add_member(TfdmSet& s, DisplacedObject* obj, uint32_t kind, const float objToWorld[12], uint32_t userId, const char* who) {
     check_member(s, obj);
     if (!objToWorld) throw HipError(std::string(who) + ": null transform");
     if (s.members.size() >= kMaxInstances) throw HipError(std::string(who) + ": a set holds at most 1024 instances");
@@ -188,19 +324,34 @@ uint32_t add_member(TfdmSet& s, HeightMapObject* obj, uint32_t kind, const float
     return static_cast<uint32_t>(s.members.size() - 1);
 }
 
-// root and generation live in the two derived objects; the kind says which one `obj` is
+// root and generation live in the three derived objects; the kind says which one `obj` is
 bool is_nrtdsm(const TfdmSet::Member& m) { return m.kind == GFX_INSTANCE_NRTDSM; }
+bool is_shell(const TfdmSet::Member& m) { return m.kind == GFX_INSTANCE_SHELL; }
 uint64_t generation_of(const TfdmSet::Member& m) {
+    if (is_shell(m)) return static_cast<const ShellObject*>(m.obj)->generation;
     return is_nrtdsm(m) ? static_cast<const NrtdsmObject*>(m.obj)->generation : static_cast<const TfdmObject*>(m.obj)->generation;
 }
 const Node& root_of(const TfdmSet::Member& m) {
+    if (is_shell(m)) return static_cast<const ShellObject*>(m.obj)->root;
     return is_nrtdsm(m) ? static_cast<const NrtdsmObject*>(m.obj)->root : static_cast<const TfdmObject*>(m.obj)->root;
+}
+// the call after which a member's object has buffers the committed record does not know
+const char* stale_call_of(const TfdmSet::Member& m) {
+    if (is_shell(m)) return static_cast<const ShellObject*>(m.obj)->lastChange;
+    return is_nrtdsm(m) ? "gfx_nrtdsm_set_params" : "gfx_tfdm_set_params";
 }
 bool has_nrtdsm(const TfdmSet& s) {
     for (const TfdmSet::Member& m : s.members) if (is_nrtdsm(m)) return true;
     return false;
 }
+bool has_shell(const TfdmSet& s) {
+    for (const TfdmSet::Member& m : s.members) if (is_shell(m)) return true;
+    return false;
+}
 const char* const kNotRendered = "the set has an NRTDSM instance; NRTDSM instances are traced (gfx_trace_scene) but not rendered";
+const char* const kShellNotRendered = "the set has a shell instance; shell instances are traced (gfx_trace_scene) but not rendered";
+// a set that is traced but cannot be bound: the message, or null
+const char* not_rendered(const TfdmSet& s) { return has_nrtdsm(s) ? kNotRendered : has_shell(s) ? kShellNotRendered : nullptr; }
 
 } // namespace
 
@@ -210,6 +361,10 @@ uint32_t tfdm_set_add(TfdmSet& s, TfdmObject* obj, const float objToWorld[12], u
 
 uint32_t tfdm_set_add_nrtdsm(TfdmSet& s, NrtdsmObject* obj, const float objToWorld[12], uint32_t userId) {
     return add_member(s, obj, GFX_INSTANCE_NRTDSM, objToWorld, userId, "gfx_tfdm_set_add_nrtdsm");
+}
+
+uint32_t tfdm_set_add_shell(TfdmSet& s, ShellObject* obj, const float objToWorld[12], uint32_t userId) {
+    return add_member(s, obj, GFX_INSTANCE_SHELL, objToWorld, userId, "gfx_tfdm_set_add_shell");
 }
 
 void tfdm_set_transform(TfdmSet& s, uint32_t index, const float objToWorld[12]) {
@@ -236,9 +391,17 @@ void tfdm_set_commit(TfdmSet& s, hipStream_t stream) {
     std::vector<float> motion(12 * s.members.size());
     for (size_t k = 0; k < s.members.size(); ++k) {
         const TfdmSet::Member& m = s.members[k];
-        const HeightMapObject& o = *m.obj;
-        const char* err = nrtdsm::make_instance_of_kind(m.kind, m.objToWorld, root_of(m), o.nodes.as<Node>(), o.records.p, o.heights.as<float>(), o.pyramid.as<F2>(),
-                                                        o.params, m.userId, recs[k]);
+        const char* err;
+        if (is_shell(m)) {
+            const ShellObject& o = *static_cast<const ShellObject*>(m.obj);
+            err = shell::make_shell_instance(m.objToWorld, o.root, o.nodes.as<Node>(), o.records.as<nrtdsm::PrismRecord>(), o.shellNodes.as<Node>(),
+                                             o.shellTris.as<shell::ShellTri>(), o.params, m.userId, recs[k]);
+        }
+        else {
+            const HeightMapObject& o = *static_cast<const HeightMapObject*>(m.obj);
+            err = nrtdsm::make_instance_of_kind(m.kind, m.objToWorld, root_of(m), o.nodes.as<Node>(), o.records.p, o.heights.as<float>(), o.pyramid.as<F2>(), o.params,
+                                                m.userId, recs[k]);
+        }
         if (!err) err = make_cur_to_prev(m.prevObjToWorld, m.objToWorld, motion.data() + 12 * k);
         if (err) throw HipError("gfx_tfdm_set_commit: instance " + std::to_string(k) + ": " + err);
     }
@@ -253,9 +416,11 @@ void tfdm_set_commit(TfdmSet& s, hipStream_t stream) {
     s.hostMotion.swap(motion);
     s.anyBilinear = false;
     s.anyNrtdsm = false;
+    s.anyShell = false;
     for (const InstanceRecord& r : s.host) {
         s.anyBilinear = s.anyBilinear || r.params.local == kBilinear;
         s.anyNrtdsm = s.anyNrtdsm || nrtdsm::instance_kind(r) == nrtdsm::kKindNrtdsm;
+        s.anyShell = s.anyShell || nrtdsm::instance_kind(r) == shell::kKindShell;
     }
     for (TfdmSet::Member& m : s.members) m.generation = generation_of(m);
     s.dirty = false;
@@ -287,7 +452,7 @@ void trace_scene_check_set(const TfdmSet& set, int device, const char* who) {
     if (set.dirty) throw HipError(w + ": the instance set has an add or a transform that is not committed (gfx_tfdm_set_commit)");
     for (size_t k = 0; k < set.members.size(); ++k)
         if (set.members[k].generation != generation_of(set.members[k]))
-            throw HipError(w + ": instance " + std::to_string(k) + "'s object had " + (is_nrtdsm(set.members[k]) ? "gfx_nrtdsm_set_params" : "gfx_tfdm_set_params") +
+            throw HipError(w + ": instance " + std::to_string(k) + "'s object had " + stale_call_of(set.members[k]) +
                            " after the set was committed; commit the set again");
 }
 
@@ -322,7 +487,18 @@ void trace_scene_launch(Context& ctx, hipStream_t stream, const SceneTrace& s) {
     auto launch = [&](auto kernel) {
         kernel<<<blocks, kSceneBlock, 0, stream>>>(table, numInstances, s.rayOrgTmin, s.rayDirTmax, s.numRays, s.numRaysPtr, plain, s.out, cnt);
     };
-    if (numInstances && s.set->anyNrtdsm) {
+    const bool shellPhase = numInstances && s.set->anyShell;
+    // the side record of a closest hit is all zeros where no shell member can win: the kernels of such a set do not know it
+    if (s.shellPart && !any && !shellPhase) GFX_HIP(hipMemsetAsync(s.shellPart, 0, sizeof(gfx_scene_shell_part) * static_cast<size_t>(s.numRays), stream));
+    if (shellPhase) {
+        auto launchShell = [&](auto kernel) {
+            kernel<<<blocks, kSceneBlock, 0, stream>>>(table, numInstances, s.rayOrgTmin, s.rayDirTmax, s.numRays, s.numRaysPtr, plain, s.out, cnt,
+                                                       any ? nullptr : static_cast<float4*>(s.shellPart));
+        };
+        if (!s.set->anyBilinear) launchShell(any ? k_scene_instances_shell<true, false> : k_scene_instances_shell<false, false>);
+        else launchShell(any ? k_scene_instances_shell<true, true> : k_scene_instances_shell<false, true>);
+    }
+    else if (numInstances && s.set->anyNrtdsm) {
         if (!s.set->anyBilinear) launch(any ? k_scene_instances_mixed<true, false> : k_scene_instances_mixed<false, false>);
         else launch(any ? k_scene_instances_mixed<true, true> : k_scene_instances_mixed<false, true>);
     }
@@ -337,7 +513,7 @@ void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint3
         throw HipError("gfx_scene_bind_displaced_passes: unknown bit in the pass mask " + std::to_string(passMask));
     if (!set) { b.set = nullptr; b.geomSlots.clear(); b.passMask = 0u; return; }
     if (set->device != ctx.device) throw HipError("gfx_scene_bind_displaced: the instance set belongs to another device");
-    if (has_nrtdsm(*set)) throw HipError(std::string("gfx_scene_bind_displaced: ") + kNotRendered);
+    if (const char* why = not_rendered(*set)) throw HipError(std::string("gfx_scene_bind_displaced: ") + why);
     if (n != set->members.size())
         throw HipError("gfx_scene_bind_displaced: " + std::to_string(n) + " geometry slots for a set of " + std::to_string(set->members.size()) + " instances");
     if (n && !geomSlots) throw HipError("gfx_scene_bind_displaced: null geometry slots");
@@ -363,7 +539,7 @@ void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint3
 void displaced_check(Context& ctx, const char* who) {
     const DisplacedBinding& b = ctx.displaced;
     trace_scene_check_set(*b.set, ctx.device, who);
-    if (has_nrtdsm(*b.set)) throw HipError(std::string(who) + ": " + kNotRendered);      // a member added after the bind
+    if (const char* why = not_rendered(*b.set)) throw HipError(std::string(who) + ": " + why);      // a member added after the bind
     if (b.geomSlots.size() != b.set->members.size())
         throw HipError(std::string(who) + ": the bound instance set has grown since gfx_scene_bind_displaced; bind it again");
     for (size_t k = 0; k < b.geomSlots.size(); ++k) {
@@ -385,7 +561,7 @@ DisplacedArgs displaced_args(const Context& ctx, const void* hits) {
 }
 
 void trace_scene(Context& ctx, hipStream_t stream, const DevAccel* accel, TfdmSet* set, DevBuf& fallbackPlain, int mode, const void* dRayOrgTmin,
-                 const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters) {
+                 const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters, void* dShellPart) {
     if (mode != GFX_TRACE_CLOSEST && mode != GFX_TRACE_ANY) throw HipError("gfx_trace_scene: unknown mode");
     if (set) trace_scene_check_set(*set, ctx.device, "gfx_trace_scene");
     if (numRays == 0) return;
@@ -396,10 +572,12 @@ void trace_scene(Context& ctx, hipStream_t stream, const DevAccel* accel, TfdmSe
     if ((reinterpret_cast<uintptr_t>(dRayOrgTmin) & 15u) || (reinterpret_cast<uintptr_t>(dRayDirTmax) & 15u) || (reinterpret_cast<uintptr_t>(dOut) & outMask))
         throw HipError("gfx_trace_scene: the ray buffers and a closest-hit output must be 16-byte aligned (an any-hit output 4-byte)");
     if (reinterpret_cast<uintptr_t>(dCounters) & 7u) throw HipError("gfx_trace_scene: the counters must be 8-byte aligned");
+    if (!any && (reinterpret_cast<uintptr_t>(dShellPart) & 15u)) throw HipError("gfx_trace_scene_ex: the shell part must be 16-byte aligned");
     SceneTrace s;
     s.accel = accel; s.set = set; s.mode = mode;
     s.rayOrgTmin = static_cast<const float4*>(dRayOrgTmin); s.rayDirTmax = static_cast<const float4*>(dRayDirTmax);
     s.numRays = numRays; s.out = dOut; s.statCounters = dCounters;
+    s.shellPart = any ? nullptr : dShellPart;
     if (accel && !any) {
         DevBuf& buf = set ? set->plain : fallbackPlain;
         buf.reserve(sizeof(gfx_hit) * static_cast<size_t>(numRays));

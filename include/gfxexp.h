@@ -936,6 +936,13 @@ int gfx_tfdm_set_add(gfx_tfdm_set* set, gfx_tfdm* obj, const float objToWorld[12
 #define GFX_INSTANCE_TFDM 0u
 #define GFX_INSTANCE_NRTDSM 1u
 int gfx_tfdm_set_add_nrtdsm(gfx_tfdm_set* set, gfx_nrtdsm* obj, const float objToWorld[12], uint32_t userId, uint32_t* index);
+/* A gfx_shell object as a member of the set, under the rules of gfx_tfdm_set_add_nrtdsm: the same refusals,
+ * *index counts all members in add order whatever their kind, and transform, move, commit, both reads, the motion table and
+ * gfx_trace_scene treat it as any member.  gfx_shell_set_params and gfx_shell_set_geometry on it ask for a new commit.  In its
+ * record the two height-map pointers carry the shell BVH's nodes and triangles (csrc/nrtdsm/shell_instance.hip.h).  Such a set is
+ * traced but not rendered: gfx_scene_bind_displaced and gfx_scene_bind_displaced_passes refuse it. */
+#define GFX_INSTANCE_SHELL 2u
+int gfx_tfdm_set_add_shell(gfx_tfdm_set* set, gfx_shell* obj, const float objToWorld[12], uint32_t userId, uint32_t* index);
 int gfx_tfdm_set_transform(gfx_tfdm_set* set, uint32_t index, const float objToWorld[12]);
 int gfx_tfdm_set_move(gfx_tfdm_set* set, uint32_t index, const float objToWorld[12]);
 int gfx_tfdm_set_commit(gfx_ctx* ctx, void* stream, gfx_tfdm_set* set);
@@ -960,9 +967,19 @@ typedef struct gfx_scene_hit { float dist, bcB, bcC; uint32_t index; float norma
  * world ray's parameter (object-space directions are not renormalised).  dCounters (optional, device u64[8], added to): [0..3]
  * as gfx_tfdm_trace, [4] world-box tests, [5] object-space traversals started.  Alignment as gfx_tfdm_trace.  A set with an
  * uncommitted add or transform, or with a member whose gfx_tfdm_set_params (gfx_nrtdsm_set_params) ran after the commit, is refused
- * with a message.  Members of both kinds are walked in one index order, so the rule above holds across kinds; [0..3] sum over both. */
+ * with a message.  Members of all kinds are walked in one index order, so the rule above holds across kinds; [0..3] sum over them.
+ * A shell member's hit is a displaced hit as above (index = the base primIndex, bcB / bcC on the base triangle, normal = the unit world
+ * normal, where = k << 1 | frontFace); a stale shell member's message names gfx_shell_set_params or gfx_shell_set_geometry. */
 int gfx_trace_scene(gfx_ctx* ctx, void* stream, uint64_t accel, gfx_tfdm_set* set, int mode, const void* dRayOrgTmin, const void* dRayDirTmax,
                     uint32_t numRays, void* dOut, void* dCounters);
+/* What only a shell member's hit has, the last 16 bytes of a gfx_shell_hit: all zeros for a miss, a plain hit and a hit on a member
+ * of another kind. */
+typedef struct gfx_scene_shell_part { uint32_t shellTriangle, shellGeom; int32_t tile[2]; } gfx_scene_shell_part;
+/* gfx_trace_scene with that side output.  GFX_TRACE_CLOSEST: dShellPart is NULL or a 16-byte aligned gfx_scene_shell_part[numRays],
+ * written for every ray (a misaligned one is refused with a message); GFX_TRACE_ANY ignores it.  gfx_trace_scene is this call with
+ * NULL, and gives the same gfx_scene_hit bytes. */
+int gfx_trace_scene_ex(gfx_ctx* ctx, void* stream, uint64_t accel, gfx_tfdm_set* set, int mode, const void* dRayOrgTmin, const void* dRayDirTmax,
+                       uint32_t numRays, void* dOut, void* dCounters, void* dShellPart);
 
 /* Displaced instances in the renderer (DESIGN.md sections 16 and 17).  While a set is bound, GFX_RESTIR_SETUP_GBUFFERS /
  * GFX_PT_SETUP_GBUFFERS and GFX_PT_PATH_TRACE_BASELINE trace plain and displaced geometry together (the scene query above, in their

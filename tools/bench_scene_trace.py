@@ -1,6 +1,6 @@
 """gfx_trace_scene against the chain of calls it replaces.
 
-    python tools/bench_scene_trace.py [--nrtdsm] [--size 1024] [--iters 20] [--width 1920] [--height 1080] [--step-timeout 300]
+    python tools/bench_scene_trace.py [--nrtdsm | --shell] [--size 1024] [--iters 20] [--width 1920] [--height 1080] [--step-timeout 300]
 
 1920 x 1080 primary rays on the scene of tfdm_common.mixed_scene (a plain teapot on a displaced ground quad, a displaced wall behind
 it, one size x size height map):
@@ -18,7 +18,14 @@ With --nrtdsm the steps are
   chain_nrtdsm   the chain that call replaces: gfx_trace, then per member the torch ray transform, gfx_tfdm_trace (the ground) or
                  gfx_nrtdsm_trace (the wall) with tmax = the best distance so far, and the torch merge
 
-both in the same run, and the result has "chain_nrtdsm_over_call_nrtdsm".
+both in the same run, and the result has "chain_nrtdsm_over_call_nrtdsm".  With --shell they are
+
+  call_shell     one gfx_trace_scene on the set whose wall is a shell member (gfx_tfdm_set_add_shell): the "One Box" shell at
+                 64 x 64 tiles over the wall's mesh; the ground stays TFDM.  The instance phase is k_scene_instances_shell
+  chain_shell    the chain that call replaces: gfx_trace, then per member the torch ray transform, gfx_tfdm_trace (the ground) or
+                 gfx_shell_trace (the wall, 48-byte hits) with tmax = the best distance so far, and the torch merge
+
+and the result has "chain_shell_over_call_shell".
 
 Per step: microseconds per launch (HIP events around --iters launches after 3 warm-up launches), Mrays/s; for the call the
 traversal counters per ray from a counting launch of its own; and whether both agree on hit or miss and on the distance (the
@@ -42,6 +49,8 @@ sys.path.insert(0, HERE)
 
 STEPS = ["call", "call_bilinear", "chain"]
 NRTDSM_STEPS = ["call_nrtdsm", "chain_nrtdsm"]
+SHELL_STEPS = ["call_shell", "chain_shell"]
+SHELL_TILES = 64
 
 
 def _arg(argv, name, default):
@@ -77,6 +86,8 @@ def step(name, size, iters, w, h):
         smooth = api.Tfdm(ctx, v, t, heights, gp_smooth)
     if name in NRTDSM_STEPS:
         smooth = api.Nrtdsm(ctx, v, t, heights, api.tfdm_params(h_scale=gp.hScale, tex_scale=(gp.texScale[0], gp.texScale[1])))
+    if name in SHELL_STEPS:         # the box is about as high as a tile is wide (tests/shell_host.py quad_box: 2.0 at 4 tiles)
+        smooth = api.Shell(ctx, v, t, [api.shell_box()], api.shell_params(h_scale=8.0 / SHELL_TILES, tex_scale=(float(SHELL_TILES), float(SHELL_TILES))))
     objects = [smooth if smooth is not None and k == len(instances) - 1 else tf for k in range(len(instances))]
     for obj, (m, uid) in zip(objects, instances):
         tset.add(obj, m, uid)
@@ -91,14 +102,16 @@ def step(name, size, iters, w, h):
     def call():
         api.trace_scene(ctx, accel, tset, api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_scene.data_ptr(), stream=stream)
 
-    if name in ("call", "call_bilinear", "call_nrtdsm"):
+    if name in ("call", "call_bilinear", "call_nrtdsm", "call_shell"):
         secs = timed(call, iters)
         d_cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
         api.trace_scene(ctx, accel, tset, api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_scene.data_ptr(), d_cnt.data_ptr(), stream=stream)
         torch.cuda.synchronize()
         cnt = d_cnt.cpu().numpy()
         where = d_scene.cpu().numpy().view(api.SCENE_HIT_DTYPE)["where"]
+        disp = where < api.SCENE_PLAIN
         out.update({"us": round(secs * 1e6, 1), "Mrays_per_s": round(n / secs / 1e6, 1),
+                    "instance_shares": [round(float((disp & (where >> 1 == k)).mean()), 4) for k in range(len(tset))],
                     "plain_share": round(float((where == api.SCENE_PLAIN).mean()), 4), "miss_share": round(float((where == api.GFX_INVALID_SLOT).mean()), 4),
                     "aabb_tests_per_ray": round(float(cnt[0]) / n, 2), "leaf_tests_per_ray": round(float(cnt[1]) / n, 2),
                     "base_triangles_per_ray": round(float(cnt[3]) / n, 2), "world_box_tests_per_ray": round(float(cnt[4]) / n, 2),
@@ -108,7 +121,8 @@ def step(name, size, iters, w, h):
     table = tset.read()
     w2o = [torch.from_numpy(table[k]["worldToObj"].reshape(3, 4).copy()).cuda() for k in range(len(table))]
     d_plain = torch.zeros(n * 4, dtype=torch.int32, device="cuda")
-    d_hit = torch.zeros(n * 8, dtype=torch.int32, device="cuda")
+    words = [12 if isinstance(o, api.Shell) else 8 for o in objects]       # a gfx_shell_hit is 48 bytes
+    d_hit = torch.zeros(n * max(words), dtype=torch.int32, device="cuda")
     d_oo, d_od = torch.empty_like(d_org), torch.empty_like(d_dir)
     best = torch.empty(n, dtype=torch.float32, device="cuda")
     where = torch.empty(n, dtype=torch.int32, device="cuda")
@@ -125,7 +139,7 @@ def step(name, size, iters, w, h):
             d_od[:, :3] = d_dir[:, :3] @ m[:, :3].T
             d_od[:, 3] = best
             objects[k].trace(api.TRACE_CLOSEST, d_oo.data_ptr(), d_od.data_ptr(), n, d_hit.data_ptr(), stream=stream)
-            th = d_hit.view(n, 8)
+            th = d_hit[:n * words[k]].view(n, words[k])
             win = th[:, 3] != -1
             torch.where(win, th[:, 0].view(torch.float32), best, out=best)
             where.copy_(torch.where(win, torch.full_like(where, k), where))
@@ -151,7 +165,7 @@ def main(argv):
         return 0
     limit = _arg(argv, "--step-timeout", 300)
     result = {"metric": "scene_trace", "size": size, "iters": iters, "width": w, "height": h}
-    steps = NRTDSM_STEPS if "--nrtdsm" in argv else STEPS
+    steps = NRTDSM_STEPS if "--nrtdsm" in argv else SHELL_STEPS if "--shell" in argv else STEPS
     for name in steps:
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name, "--size", str(size), "--iters", str(iters),
                "--width", str(w), "--height", str(h)]
@@ -164,6 +178,8 @@ def main(argv):
         result[name] = json.loads(line[-1][len("STEP_RESULT "):])
     if steps is NRTDSM_STEPS:
         result["chain_nrtdsm_over_call_nrtdsm"] = round(result["chain_nrtdsm"]["us"] / result["call_nrtdsm"]["us"], 3)
+    elif steps is SHELL_STEPS:
+        result["chain_shell_over_call_shell"] = round(result["chain_shell"]["us"] / result["call_shell"]["us"], 3)
     else:
         result["chain_over_call"] = round(result["chain"]["us"] / result["call"]["us"], 3)
     print(json.dumps(result))

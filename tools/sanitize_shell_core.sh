@@ -1,5 +1,5 @@
 #!/bin/bash
-# The host compilation of csrc/nrtdsm/shell_core.hip.h + shell_build.h (the text the device kernels run) under AddressSanitizer
+# The host compilation of csrc/nrtdsm/shell_core.hip.h + shell_build.h + shell_instance.hip.h (the text the device kernels run) under AddressSanitizer
 # and UndefinedBehaviorSanitizer, as a stand-alone program (tools/shell_sanitize_main.cpp): no GPU, nothing loaded into Python.
 #   bash tools/sanitize_shell_core.sh [output directory, default a fresh temporary one]
 set -eu

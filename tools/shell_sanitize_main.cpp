@@ -4,12 +4,18 @@
 // three texture transforms: many small tiles, wrapped and rotated tiles with negative indices, and one tile that holds the whole
 // cap.  1500 rays toward the cap, rays from far away, rays along base edges, rays that are NaN, infinite or of zero direction, and
 // the builder's refusals.  Checks what needs no reference: any-hit answers where closest-hit does, nothing in a hit is not finite,
-// the indices of a hit exist, a miss reports tmax, the iterations stay below their ceiling.  Exit status 0 and "ok" = clean.
+// the indices of a hit exist, a miss reports tmax, the iterations stay below their ceiling.  Then two instances of a scene (the host
+// compilation of csrc/nrtdsm/shell_instance.hip.h, tests/scene_shell_host.cpp) over the same rays: the shell object under a
+// mirrored, non-uniformly scaled transform and an NRTDSM object of the same base mesh under a 16 x 16 map as it is -- the walk with
+// the world-box cull equals the walk without it, shell part included, any-hit answers where closest-hit does, and the shell part is
+// set only where the shell member wins.  Exit status 0 and "ok" = clean.
 #include <cmath>
 #include <cstdio>
 #include <limits>
 #include "../tests/tfdm_host.cpp"
 #include "../tests/shell_host.cpp"
+#include "../tests/nrtdsm_host.cpp"
+#include "../tests/scene_shell_host.cpp"
 
 namespace {
 struct Rng { uint64_t s; double next() { s = s * 6364136223846793005ull + 1442695040888963407ull; return static_cast<double>(s >> 11) * (1.0 / 9007199254740992.0); } };
@@ -97,6 +103,31 @@ int main() {
     ray(0, 0, 2, 0, 0, -1, nan, 3.0e38f);
     const uint32_t n = static_cast<uint32_t>(org.size() / 4), numBad = 6;
 
+    // the NRTDSM member of the scene walk: the same base mesh under a 16 x 16 two-sine map
+    const uint32_t size = 16;
+    std::vector<float> map(size * size);
+    for (uint32_t y = 0; y < size; ++y)
+        for (uint32_t x = 0; x < size; ++x) {
+            const double a = 2.0 * M_PI / size;
+            const double h = 0.5 + 0.25 * std::sin(a * 3 * x) * std::cos(a * 2 * y) + 0.2 * std::sin(a * (5 * x + 7 * y));
+            map[y * size + x] = static_cast<float>(std::round(std::fmin(std::fmax(h, 0.0), 1.0) * 255.0)) / 255.0f;
+        }
+    const float* level0 = map.data();
+    std::vector<float> levels(tfdm_host_total_texels(size));
+    tfdm_host_levels(&level0, 1, size, levels.data());
+    std::vector<F2> pyramid(levels.size());
+    tfdm_host_pyramid(levels.data(), size, pyramid.data());
+    gfx_tfdm_params ng;
+    std::memset(&ng, 0, sizeof(ng));
+    ng.hScale = 0.05f; ng.texScale[0] = ng.texScale[1] = 1.0f; ng.localIntersection = 1u;
+    Params np;
+    tfdm_host_params(&ng, size, &np);
+    std::vector<nr::PrismRecord> nrec(numTris);
+    std::vector<float> nboxes(6 * numTris);
+    nrtdsm_host_records(v, tris.data(), numTris, &ng, size, pyramid.data(), &np, nrec.data(), nboxes.data());
+    std::vector<Node> nnodes(2 * numTris);
+    if (tfdm_host_tree(nboxes.data(), numTris, nnodes.data(), 2 * numTris) > 2 * numTris) { std::printf("tree of the NRTDSM member\n"); return 1; }
+
     for (int xf = 0; xf < 3; ++xf) {
         const uint32_t numGeoms = xf == 1 ? 2u : 1u;
         gfx_tfdm_params g;
@@ -142,6 +173,35 @@ int main() {
         std::printf("transform %d: %u of %u rays hit, %.2f box tests and %.2f leaf tests per ray, at most %u iterations\n", xf, numHits, n,
                     static_cast<double>(counters[0]) / n, static_cast<double>(counters[1]) / n, worst);
         if (numHits < n / 8 || worst >= shell_host_max_descent()) { std::printf("transform %d: the ray set barely hits, or the traversal reached its ceiling\n", xf); return 1; }
+        // ... as two instances of a scene: the shell mirrored and non-uniformly scaled, the NRTDSM object as it is
+        const float ident[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 }, mirrored[12] = { -1.25f, 0, 0, 0.1f, 0, 0.75f, 0, 0.05f, 0, 0, 1.5f, -0.5f };      // the cap stays under the rays
+        const uint64_t shellPtrs[4] = { reinterpret_cast<uint64_t>(nodes.data()), reinterpret_cast<uint64_t>(rec.data()), reinterpret_cast<uint64_t>(shellNodes.data()),
+                                        reinterpret_cast<uint64_t>(shellTris.data()) };
+        const uint64_t nrtdsmPtrs[4] = { reinterpret_cast<uint64_t>(nnodes.data()), reinterpret_cast<uint64_t>(nrec.data()), reinterpret_cast<uint64_t>(levels.data()),
+                                         reinterpret_cast<uint64_t>(pyramid.data()) };
+        InstanceRecord table[2];
+        if (scene_shell_host_make_instance(sh::kKindShell, mirrored, &nodes[0], shellPtrs, &p, 1, &table[0], msg, sizeof(msg)) ||
+            scene_shell_host_make_instance(nr::kKindNrtdsm, ident, &nnodes[0], nrtdsmPtrs, &np, 2, &table[1], msg, sizeof(msg))) { std::printf("make_instance: %s\n", msg); return 1; }
+        std::vector<gfx_scene_hit> culled(n), full(n);
+        std::vector<gfx_scene_shell_part> culledPart(n), fullPart(n);
+        std::vector<uint32_t> occluded(n);
+        scene_shell_host_trace(table, 2, nullptr, 0, org.data(), dir.data(), n, culled.data(), culledPart.data(), nullptr, 1);
+        scene_shell_host_trace(table, 2, nullptr, 0, org.data(), dir.data(), n, full.data(), fullPart.data(), nullptr, 0);
+        scene_shell_host_trace(table, 2, nullptr, 1, org.data(), dir.data(), n, occluded.data(), nullptr, nullptr, 1);
+        uint32_t sceneHits[2] = { 0, 0 };
+        for (uint32_t i = 0; i < n; ++i) {
+            const bool hit = culled[i].where != 0xFFFFFFFFu;
+            const uint32_t member = culled[i].where >> 1;
+            const gfx_scene_shell_part& sp = culledPart[i];
+            const bool onShell = hit && member == 0u;
+            const bool partOk = onShell ? (sp.shellTriangle < numShellTris && sp.shellGeom < numGeoms && shellTris[sp.shellTriangle].geom == sp.shellGeom)
+                                        : (sp.shellTriangle == 0u && sp.shellGeom == 0u && sp.tile[0] == 0 && sp.tile[1] == 0);
+            if (std::memcmp(&culled[i], &full[i], sizeof(gfx_scene_hit)) != 0 || std::memcmp(&sp, &fullPart[i], sizeof(sp)) != 0 || (occluded[i] != 0u) != hit ||
+                (hit && member > 1u) || !partOk) { std::printf("transform %d: scene ray %u is wrong\n", xf, i); return 1; }
+            if (hit) ++sceneHits[member];
+        }
+        std::printf("transform %d: %u rays end on the mirrored shell instance, %u on the NRTDSM instance\n", xf, sceneHits[0], sceneHits[1]);
+        if (sceneHits[0] == 0u || sceneHits[1] < n / 8) { std::printf("transform %d: a member of the scene of two instances is not seen\n", xf); return 1; }
     }
     std::printf("ok\n");
     return 0;

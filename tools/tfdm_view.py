@@ -32,6 +32,13 @@ and <out>_instance.png (plain geometry grey, every displaced instance a colour o
 --scene --nrtdsm: the same scene with the wall an NRTDSM member of the set (gfx_tfdm_set_add_nrtdsm; the ground stays TFDM), the same
 three images through the same ONE gfx_trace_scene call.  Such a set is traced, not rendered: --render and --restir refuse it.
 
+    python tools/tfdm_view.py --scene --shell [box|bunny] [--tiles 16] [--width 960] [--height-px 540] [--out tfdm_view]
+
+--scene --shell: the same scene with the wall a shell member of the set (gfx_tfdm_set_add_shell: the "One Box" shell or the 309-face
+bunny, --tiles x --tiles over the wall's mesh; the ground stays TFDM), through ONE gfx_trace_scene_ex call.  The same three images
+and <out>_geom.png, from the call's side output: the shell geometry of the hit as a colour, its tile as a checkerboard; black where
+the winner is no shell member.  Traced, not rendered, as with --nrtdsm.
+
     python tools/tfdm_view.py --scene --render [--frames 64] [--size 256] [--width 960] [--height-px 540] [--out tfdm_view]
 
 --render: the same scene under an emissive rectangle, path traced through the bound instance set (gfx_scene_bind_displaced: the
@@ -148,6 +155,8 @@ def scene_view(a):
     tf = api.Tfdm(ctx, v, t, heights, gp)
     # --nrtdsm: the last instance (the wall) is an NRTDSM object of the same mesh, map and height scale
     wall = api.Nrtdsm(ctx, v, t, heights, api.tfdm_params(h_scale=gp.hScale, tex_scale=(gp.texScale[0], gp.texScale[1]))) if a.nrtdsm else None
+    if a.shell:         # ... or a shell object over the same mesh; one unit of shell height is half a tile high, as the shell view's default
+        wall = api.Shell(ctx, v, t, [K.shell_geom(a.shell)], api.shell_params(h_scale=0.5 * K.extent(v), tex_scale=(a.tiles, a.tiles)))
     tset = api.TfdmSet(ctx)
     for k, (m, uid) in enumerate(instances):
         tset.add(wall if wall is not None and k == len(instances) - 1 else tf, m, uid)
@@ -158,7 +167,9 @@ def scene_view(a):
     d_org, d_dir = torch.from_numpy(org).cuda(), torch.from_numpy(dirs).cuda()
     d_out = torch.zeros(n * 8, dtype=torch.int32, device="cuda")
     d_cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
-    api.trace_scene(ctx, accel, tset, api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), d_cnt.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    d_part = torch.zeros(n * 4, dtype=torch.int32, device="cuda") if a.shell else None
+    api.trace_scene(ctx, accel, tset, api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), d_cnt.data_ptr(), stream=torch.cuda.current_stream().cuda_stream,
+                    d_shell_part=d_part.data_ptr() if a.shell else 0)
     torch.cuda.synchronize()
     hits = d_out.cpu().numpy().view(api.SCENE_HIT_DTYPE)
     cnt = d_cnt.cpu().numpy()
@@ -178,13 +189,23 @@ def scene_view(a):
     ids[is_plain, :3] = 0.5
     ids[disp, :3] = palette[(where[disp] >> 1) % len(palette)]
     api.save_image_sdr(a.out + "_instance.png", ids, w, h, sdr)
+    images = [a.out + "_normal.png", a.out + "_depth.png", a.out + "_instance.png"]
+    if a.shell:
+        part = d_part.cpu().numpy().view(api.SCENE_SHELL_PART_DTYPE)
+        on_shell = disp & (tset.read()["pad0"][np.where(disp, where >> 1, 0)] == api.INSTANCE_SHELL)
+        geo = np.zeros((n, 4), np.float32)
+        geo[:, 3] = 1
+        checker = 0.6 + 0.4 * ((part["tile"][on_shell, 0] + part["tile"][on_shell, 1]) & 1)
+        geo[on_shell, :3] = palette[part["shellGeom"][on_shell] % len(palette)] * checker[:, None]
+        api.save_image_sdr(a.out + "_geom.png", geo, w, h, sdr)
+        images.append(a.out + "_geom.png")
     print(json.dumps({"scene": "teapot on displaced ground, displaced wall", "kinds": [int(k) for k in tset.read()["pad0"]], "size": int(heights.shape[0]), "instances": len(tset), "rays": n,
                       "plain_share": round(float(is_plain.mean()), 4),
                       "instance_shares": [round(float((disp & (where >> 1 == k)).mean()), 4) for k in range(len(tset))],
                       "miss_share": round(float(miss.mean()), 4), "aabb_tests_per_ray": round(float(cnt[0]) / n, 2),
                       "leaf_tests_per_ray": round(float(cnt[1]) / n, 2), "world_box_tests_per_ray": round(float(cnt[4]) / n, 2),
                       "traversals_per_ray": round(float(cnt[5]) / n, 2),
-                      "images": [a.out + "_normal.png", a.out + "_depth.png", a.out + "_instance.png"]}))
+                      "images": images}))
     return 0
 
 
@@ -257,8 +278,12 @@ def main():
     if a.render or a.restir:
         if a.nrtdsm:
             ap.error("--nrtdsm with --scene is traced, not rendered: a set with an NRTDSM instance cannot be bound")
+        if a.shell:
+            ap.error("--shell with --scene is traced, not rendered: a set with a shell instance cannot be bound")
         return scene_render(a)
     if a.scene:
+        if a.shell and a.nrtdsm:
+            ap.error("--scene takes the wall as --nrtdsm or as --shell, not both")
         return scene_view(a)
     if a.shell:
         if "--scale" not in sys.argv:
