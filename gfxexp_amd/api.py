@@ -213,7 +213,8 @@ def abi_mirrors():
             "gfx_denoiser_settings": GfxDenoiserSettings, "gfx_denoiser_inputs": GfxDenoiserInputs,
             "gfx_denoiser_history_buffers": GfxDenoiserHistoryBuffers, "gfx_taa_inputs": GfxTaaInputs, "gfxh_dds_info": GfxhDdsInfo,
             "gfxh_image_desc": GfxhImageDesc, "gfx_tfdm_params": GfxTfdmParams, "gfx_tfdm_hit": GfxTfdmHit, "gfx_scene_hit": GfxSceneHit,
-            "gfx_shell_hit": GfxShellHit, "gfx_shell_geom": GfxShellGeom, "gfx_scene_shell_part": GfxSceneShellPart}
+            "gfx_shell_hit": GfxShellHit, "gfx_shell_geom": GfxShellGeom, "gfx_scene_shell_part": GfxSceneShellPart,
+            "gfx_displaced_member": GfxDisplacedMember}
 
 
 class RcclExchange:
@@ -341,6 +342,7 @@ C_ABI_SYMBOLS = [
     "gfx_tfdm_set_create", "gfx_tfdm_set_add", "gfx_tfdm_set_transform", "gfx_tfdm_set_commit", "gfx_tfdm_set_read", "gfx_tfdm_set_destroy", "gfx_trace_scene",
     "gfx_scene_bind_displaced", "gfx_restir_primary_rays", "gfx_scene_bind_displaced_passes", "gfx_restir_last_rays",
     "gfx_tfdm_set_move", "gfx_tfdm_set_read_motion", "gfx_tfdm_set_add_nrtdsm", "gfx_tfdm_set_add_shell", "gfx_trace_scene_ex",
+    "gfx_scene_bind_displaced_kinds",
     "gfx_nrtdsm_create", "gfx_nrtdsm_set_params", "gfx_nrtdsm_destroy", "gfx_nrtdsm_trace", "gfx_nrtdsm_read", "gfx_nrtdsm_size",
     "gfx_shell_create", "gfx_shell_set_params", "gfx_shell_set_geometry", "gfx_shell_destroy", "gfx_shell_trace", "gfx_shell_read", "gfx_shell_size",
 ]
@@ -960,6 +962,19 @@ class Context:
             self._check(self.L.gfx_scene_bind_displaced(self.h, tfdm_set.h, _p(slots), C.c_uint32(len(slots))))
         self._displaced = tfdm_set          # the binding does not own the set: keep it alive
 
+    def bind_displaced_kinds(self, tfdm_set, members=(), restir=False, pass_mask=None):
+        """gfx_scene_bind_displaced_kinds: bind_displaced for a set with members of any kind (None: unbind).  members[k] describes member
+        k: a geometry slot (a TFDM or an NRTDSM member), or (geometry slot, [material slot of shell geometry 0, 1, ...]) for a shell
+        member, or a DISPLACED_MEMBER_DTYPE array of all of them.  restir / pass_mask as bind_displaced."""
+        if tfdm_set is None:
+            self._check(self.L.gfx_scene_bind_displaced_kinds(self.h, None, None, C.c_uint32(0), C.c_uint32(0)))
+            self._displaced = None
+            return
+        m = displaced_members(members)
+        mask = pass_mask if pass_mask is not None else DISPLACED_GBUFFER_PT | (DISPLACED_RESTIR if restir else 0)
+        self._check(self.L.gfx_scene_bind_displaced_kinds(self.h, tfdm_set.h, _p(m), C.c_uint32(len(m)), C.c_uint32(mask)))
+        self._displaced = tfdm_set
+
     def restir_last_rays(self, d_ray_org, d_ray_dir, d_occluded, capacity, stream=0):
         """gfx_restir_last_rays: the ray queue (float4 pairs, gfx_trace's layout) and the occlusion words (uint32) of the most recent
         ReSTIR ray pass that ran in its three-kernel form, copied into device buffers of `capacity` entries; returns the number of
@@ -1446,6 +1461,34 @@ class GfxSceneShellPart(C.Structure):
     _fields_ = [("shellTriangle", C.c_uint32), ("shellGeom", C.c_uint32), ("tile", C.c_int32 * 2)]
 
 
+# gfx_displaced_member: one member of a set as gfx_scene_bind_displaced_kinds takes it
+DISPLACED_MEMBER_DTYPE = np.dtype([("geomInstSlot", "<u4"), ("numShellMaterials", "<u4"), ("shellMatSlots", "<u4", 8)])
+GEOM_SLOT_BITS = 28         # gbuffer0.geomInstSlot of a displaced pixel under such a binding: geomInstSlot | shellGeom << 28
+
+
+class GfxDisplacedMember(C.Structure):
+    _fields_ = [("geomInstSlot", C.c_uint32), ("numShellMaterials", C.c_uint32), ("shellMatSlots", C.c_uint32 * 8)]
+
+
+def displaced_members(members):
+    """DISPLACED_MEMBER_DTYPE[n] of a list whose entry k is a geometry slot or (geometry slot, shell material slots); an array of that
+    type passes through."""
+    if isinstance(members, np.ndarray) and members.dtype == DISPLACED_MEMBER_DTYPE:
+        return np.ascontiguousarray(members).reshape(-1)
+    out = np.zeros(len(members), DISPLACED_MEMBER_DTYPE)
+    for k, m in enumerate(members):
+        if isinstance(m, (tuple, list)):
+            slot, mats = m
+            mats = [int(x) for x in mats]
+            if len(mats) > 8:
+                raise GfxError("displaced_members: member %d has more than 8 shell materials" % k)
+            out[k]["geomInstSlot"], out[k]["numShellMaterials"] = int(slot), len(mats)
+            out[k]["shellMatSlots"][:len(mats)] = mats
+        else:
+            out[k]["geomInstSlot"] = int(m)
+    return out
+
+
 def _xfm12(m):
     x = np.ascontiguousarray(m, np.float32).reshape(-1)
     if x.size == 16:
@@ -1457,8 +1500,8 @@ def _xfm12(m):
 
 class TfdmSet:
     """gfx_tfdm_set: Tfdm, Nrtdsm and Shell objects, in any order, under object-to-world transforms (row-major 3 x 4, or a 4 x 4 whose
-    last row is dropped), the displaced instances of trace_scene.  A set with an Nrtdsm or a Shell member is traced but not rendered
-    (Context.bind_displaced refuses it).  commit() before the first query, and again after add / set_transform / move / a member's
+    last row is dropped), the displaced instances of trace_scene.  A set with an Nrtdsm or a Shell member is rendered through
+    Context.bind_displaced_kinds (Context.bind_displaced refuses it).  commit() before the first query, and again after add / set_transform / move / a member's
     set_params (a Shell's set_geometry).  move() is the per-frame update of a moving instance (previous <- current, current <- the new transform: its
     pixels get its motion vector); set_transform() is the teleport (previous <- current <- the new transform, no motion).  The set
     keeps its members alive."""

@@ -986,6 +986,11 @@ int gfx_scene_bind_displaced_passes(gfx_ctx* ctx, gfx_tfdm_set* set, const uint3
     displaced_bind(ctx->c, set ? &set->s : nullptr, geomInstSlots, n, passMask);
     GFX_CATCH(ctx)
 }
+int gfx_scene_bind_displaced_kinds(gfx_ctx* ctx, gfx_tfdm_set* set, const gfx_displaced_member* members, uint32_t n, uint32_t passMask) {
+    GFX_TRY(ctx)
+    displaced_bind_kinds(ctx->c, set ? &set->s : nullptr, members, n, passMask);
+    GFX_CATCH(ctx)
+}
 int gfx_restir_last_rays(gfx_ctx* ctx, void* stream, void* dRayOrgTmin, void* dRayDirTmax, void* dOccluded, uint32_t capacity, uint32_t* count) {
     GFX_TRY(ctx)
     restir_last_rays(ctx->c, static_cast<hipStream_t>(stream), dRayOrgTmin, dRayDirTmax, dOccluded, capacity, count);

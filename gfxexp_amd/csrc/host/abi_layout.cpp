@@ -39,6 +39,7 @@ const Field kFields[] = {
     S(gfx_shell_geom), F(gfx_shell_geom, positions), F(gfx_shell_geom, stride), F(gfx_shell_geom, numVertices), F(gfx_shell_geom, triangles), F(gfx_shell_geom, numTriangles),
     S(gfx_scene_hit), F(gfx_scene_hit, dist), F(gfx_scene_hit, bcB), F(gfx_scene_hit, bcC), F(gfx_scene_hit, index), F(gfx_scene_hit, normal), F(gfx_scene_hit, where),
     S(gfx_scene_shell_part), F(gfx_scene_shell_part, shellTriangle), F(gfx_scene_shell_part, shellGeom), F(gfx_scene_shell_part, tile),
+    S(gfx_displaced_member), F(gfx_displaced_member, geomInstSlot), F(gfx_displaced_member, numShellMaterials), F(gfx_displaced_member, shellMatSlots),
     S(gfx_restir_static_params), F(gfx_restir_static_params, imageSizeX), F(gfx_restir_static_params, imageSizeY), F(gfx_restir_static_params, rngBuffer),
     F(gfx_restir_static_params, gbuffer0), F(gfx_restir_static_params, gbuffer1), F(gfx_restir_static_params, gbuffer2), F(gfx_restir_static_params, gbuffer3),
     F(gfx_restir_static_params, reservoirBuffer), F(gfx_restir_static_params, reservoirInfoBuffer), F(gfx_restir_static_params, sampleVisibilityBuffer),

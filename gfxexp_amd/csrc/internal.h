@@ -95,6 +95,11 @@ struct DisplacedBinding {
     DevBuf dGeomSlots;               // uint32[instances]
     DevBuf gbHits;                   // gfx_scene_hit per launch slot of the G-buffer pass (Context::gbRayHits stays its plain phase and hint store)
     DevBuf ptHits, ptPlain;          // path tracer, extension trace: gfx_scene_hit / gfx_hit per queue entry
+    // a binding made by gfx_scene_bind_displaced_kinds: members of every kind are rendered
+    bool kinds = false;
+    std::vector<gfx_displaced_member> members;      // as bound: the launch check repeats the bind's checks against them
+    DevBuf dShellMats;               // uint32[8 * instances]: material of shell geometry g of member k at [8 k + g] (zeros for another kind)
+    DevBuf gbShellPart, ptShellPart; // gfx_scene_shell_part beside gbHits / ptHits; allocated only while the committed set has a shell member
 };
 
 // Scheduling knobs of a context (none changes a result).  Defaults are the measured best on MI355X; gfx_ctx_create

@@ -7,6 +7,7 @@ namespace gfx {
 
 struct ShellObject : DisplacedObject {
     uint32_t numShellNodes = 0, numShellTriangles = 0;
+    uint32_t numGeoms = 0;              // shell geometries of the current shell BVH: a renderer binds one material to each (tfdm/tfdm_set.hip)
     DevBuf shellNodes, shellTris;       // Node[numShellNodes], ShellTri[numShellTriangles]
     tfdm::Node root;                    // nodes[0] on the host and the generation of the buffers, as NrtdsmObject keeps them: what a
     uint64_t generation = 0;            // member of an instance set needs (tfdm/tfdm_set.hip)

@@ -92,7 +92,7 @@ std::vector<nrtdsm::PrismRecord> make_records(const ShellObject& o, const gfx_tf
     return recs;
 }
 
-struct ShellDev { DevBuf nodes, tris; uint32_t numNodes = 0, numTris = 0; };
+struct ShellDev { DevBuf nodes, tris; uint32_t numNodes = 0, numTris = 0, numGeoms = 0; };
 
 // `fresh`: a new shell BVH that takes the place of the object's own together with the new records, boxes and tree (null: the
 // object's own is used)
@@ -107,6 +107,7 @@ void build_geometry(ShellObject& o, hipStream_t stream, const gfx_tfdm_params& g
         o.shellNodes.release(); o.shellTris.release();
         o.shellNodes = fresh->nodes; o.shellTris = fresh->tris;
         o.numShellNodes = fresh->numNodes; o.numShellTriangles = fresh->numTris;
+        o.numGeoms = fresh->numGeoms;
         fresh->nodes = DevBuf(); fresh->tris = DevBuf();
     }
     ++o.generation;
@@ -123,6 +124,7 @@ void upload_shell(const char* who, hipStream_t stream, const gfx_shell_geom* geo
     GFX_HIP(hipStreamSynchronize(stream));           // `bvh` goes out of scope
     dev.numNodes = static_cast<uint32_t>(bvh.nodes.size());
     dev.numTris = static_cast<uint32_t>(bvh.tris.size());
+    dev.numGeoms = numGeoms;
 }
 
 } // namespace

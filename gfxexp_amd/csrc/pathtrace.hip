@@ -28,6 +28,7 @@
 #include "trace_local.hip.h"
 #include "tfdm/tfdm_set.h"
 #include "tfdm/displaced_surface.hip.h"
+#include "nrtdsm/displaced_kinds.hip.h"
 
 namespace gfx {
 
@@ -587,13 +588,17 @@ GFX_DEV PtBaseTriangle pt_base_triangle(const PtArgs& a, uint32_t geomInstSlot, 
 }
 // The first vertex on a displaced pixel: position and normals restored from G-buffers 2 / 3 (tfdm/gpu_kernels/
 // optix_pathtracing_kernels.cu:119-126), tangent and texture coordinate from the base triangle.
+// SHELL (a binding of gfx_scene_bind_displaced_kinds over a set with a shell member): gbuffer0.geomInstSlot
+// carries the shell geometry in its upper four bits, so the geometry table is indexed with the masked word, and the material is the
+// one the G-buffer pass chose (gbuffer3.matSlot), not the bound geometry's.
+template <bool SHELL>
 GFX_DEV void pt_first_setup_displaced(const PtArgs& a, const DisplacedArgs& d, size_t p, uint4 g0, PtPath& path, PtSetup& su) {
     const uint32_t bufIdx = a.f.bufferIndex;
     reset_vertex_out(path.o);
     path.alpha = f3(1.0f);
     path.dirPDensity = 0.0f;
     const float bcB = decode_bc(g0.w & 0xFFFF), bcC = decode_bc(g0.w >> 16);
-    const PtBaseTriangle t = pt_base_triangle(a, g0.y, g0.z);
+    const PtBaseTriangle t = pt_base_triangle(a, SHELL ? tfdm::geom_word_slot(g0.y) : g0.y, g0.z);
     const float4 g2 = static_cast<const float4*>(a.s.gbuffer2[bufIdx])[p];
     const uint4 g3 = static_cast<const uint4*>(a.s.gbuffer3[bufIdx])[p];
     const tfdm::V3 ngv = tfdm::ds_decode_dir(f2bits(g2.w));
@@ -604,7 +609,7 @@ GFX_DEV void pt_first_setup_displaced(const PtArgs& a, const DisplacedArgs& d, s
     f3 pos(g2.x, g2.y, g2.z);
     const Camera cam = load_camera(a.f.camera);
     path.rng.state = static_cast<const uint64_t*>(a.s.rngBuffer)[p];
-    const gfx_material& mat = a.scene.materials[t.materialSlot];
+    const gfx_material& mat = a.scene.materials[SHELL ? g3.w : t.materialSlot];
     const f3 vOut = unit(cam.pos - pos);
     const float frontHit = dot(vOut, ng) >= 0.0f ? 1.0f : -1.0f;
     path.pos = offset_ray_origin(pos, frontHit * ng);
@@ -614,7 +619,8 @@ GFX_DEV void pt_first_setup_displaced(const PtArgs& a, const DisplacedArgs& d, s
     su.bsdf.setup(a.scene, mat, tu, tv);
     su.shade = true;
 }
-__global__ __launch_bounds__(kPtBlock) void k_pt_first_scene(PtArgs a, DisplacedArgs d) {
+template <bool SHELL>
+GFX_DEV void pt_first_scene(const PtArgs& a, const DisplacedArgs& d) {
     const PixelId px = pixel_of_thread(a.px);
     const size_t p = px.p;
     PtPath path;
@@ -622,7 +628,7 @@ __global__ __launch_bounds__(kPtBlock) void k_pt_first_scene(PtArgs a, Displaced
     uint4 g0 = make_uint4(0xFFFFFFFFu, 0, 0, 0);
     if (px.valid) g0 = static_cast<const uint4*>(a.s.gbuffer0[a.f.bufferIndex])[p];
     bool surface;
-    if (g0.x != 0xFFFFFFFFu && (g0.x & GFX_GBUFFER_DISPLACED)) { pt_first_setup_displaced(a, d, p, g0, path, su); surface = true; }
+    if (g0.x != 0xFFFFFFFFu && (g0.x & GFX_GBUFFER_DISPLACED)) { pt_first_setup_displaced<SHELL>(a, d, p, g0, path, su); surface = true; }
     else surface = pt_first_setup<false>(a, px, path, su);
     const EnvMap env = load_env(a.s);
     const bool envEnabled = env.present() && a.f.enableEnvLight;
@@ -634,15 +640,19 @@ __global__ __launch_bounds__(kPtBlock) void k_pt_first_scene(PtArgs a, Displaced
     }
     push_vertex(a, static_cast<uint32_t>(p), path.pos, path.o);
 }
+__global__ __launch_bounds__(kPtBlock) void k_pt_first_scene(PtArgs a, DisplacedArgs d) { pt_first_scene<false>(a, d); }
+__global__ __launch_bounds__(kPtBlock) void k_pt_first_scene_shell(PtArgs a, DisplacedArgs d) { pt_first_scene<true>(a, d); }
 // A later vertex on a displaced surface: everything from the hit (optix_pathtracing_kernels.cu:289-301).
+// materialSlot: the material the hit is shaded with, where it is not the bound geometry's (a shell member's, by shell geometry);
+// GFX_INVALID_SLOT: the bound geometry's.
 GFX_DEV uint32_t pt_next_setup_displaced(const PtArgs& a, const DisplacedArgs& d, const tfdm::SceneHit& sh, f3 rayOrg, f3 rayDir, const uint64_t* rngBuf, PtPath& path,
-                                         PtSetup& su) {
+                                         PtSetup& su, uint32_t materialSlot = GFX_INVALID_SLOT) {
     reset_vertex_out(path.o);
     const uint32_t k = sh.where >> 1;
     const PtBaseTriangle t = pt_base_triangle(a, d.geomSlots[k], sh.index);
     const tfdm::DisplacedPoint sp = tfdm::displaced_point(d.table[k], sh, tfdm::v3(rayOrg.x, rayOrg.y, rayOrg.z), tfdm::v3(rayDir.x, rayDir.y, rayDir.z), t.a, t.b, t.c);
     const f3 ng(sp.normal.x, sp.normal.y, sp.normal.z), tc0(sp.tangent.x, sp.tangent.y, sp.tangent.z);
-    const gfx_material& mat = a.scene.materials[t.materialSlot];
+    const gfx_material& mat = a.scene.materials[materialSlot != GFX_INVALID_SLOT ? materialSlot : t.materialSlot];
     const f3 vOut = unit(-rayDir);
     const float frontHit = dot(vOut, ng) >= 0.0f ? 1.0f : -1.0f;
     su.frame = Frame(ng, tc0);
@@ -659,7 +669,8 @@ GFX_DEV uint32_t pt_next_setup_displaced(const PtArgs& a, const DisplacedArgs& d
     }
     return kPtHitSurface;
 }
-__global__ __launch_bounds__(kPtBlock) void k_pt_bounce_scene(PtArgs a, DisplacedArgs d) {
+template <bool SHELL>
+GFX_DEV void pt_bounce_scene(const PtArgs& a, const DisplacedArgs& d, const DisplacedShellArgs& e) {
     const uint32_t i = blockIdx.x * kPtBlock + threadIdx.x;
     const uint32_t count = *a.extCountIn;
     PtPath path;
@@ -667,12 +678,14 @@ __global__ __launch_bounds__(kPtBlock) void k_pt_bounce_scene(PtArgs a, Displace
     uint32_t pixel = 0;
     gfx_hit h; h.dist = 0.0f; h.bcB = 0.0f; h.bcC = 0.0f; h.triIndex = GFX_INVALID_SLOT;
     tfdm::SceneHit sh = tfdm::scene_miss(0.0f);
+    uint32_t shellGeom = 0u;
     f3 rayOrg(0.0f), rayDir(0.0f);
     const bool active = i < count;
     if (active) {
         pixel = a.extOwnerIn[i];
         const float4 h0 = d.hits[2ull * i], h1 = d.hits[2ull * i + 1];          // a gfx_scene_hit: two 16-byte loads
         sh.dist = h0.x; sh.bcB = h0.y; sh.bcC = h0.z; sh.index = f2bits(h0.w); sh.normal = tfdm::v3(h1.x, h1.y, h1.z); sh.where = f2bits(h1.w);
+        if (SHELL) shellGeom = f2bits(e.shellPart[i].y);                           // a gfx_scene_shell_part: one more 16-byte load
         h.dist = h0.x; h.bcB = h0.y; h.bcC = h0.z; h.triIndex = sh.index;        // a miss carries GFX_INVALID_SLOT there
         const float4 ro4 = a.extOrgIn[i], rd4 = a.extDirIn[i];
         rayOrg = f3(ro4.x, ro4.y, ro4.z); rayDir = f3(rd4.x, rd4.y, rd4.z);
@@ -684,7 +697,15 @@ __global__ __launch_bounds__(kPtBlock) void k_pt_bounce_scene(PtArgs a, Displace
     const uint64_t* rngBuf = static_cast<const uint64_t*>(a.s.rngBuffer) + pixel;
     PtSetup su;
     uint32_t what;
-    if (active && sh.where != GFX_INVALID_SLOT && sh.where != GFX_SCENE_PLAIN) what = pt_next_setup_displaced(a, d, sh, rayOrg, rayDir, rngBuf, path, su);
+    if (active && sh.where != GFX_INVALID_SLOT && sh.where != GFX_SCENE_PLAIN) {
+        if (SHELL) {
+            // the material of a shell member's hit is its shell geometry's; of another member's, its bound geometry's (the sentinel)
+            const uint32_t k = sh.where >> 1;
+            const uint32_t mat = tfdm::displaced_material(nrtdsm::instance_kind(d.table[k]), k, shellGeom, e.shellMats, GFX_INVALID_SLOT);
+            what = pt_next_setup_displaced(a, d, sh, rayOrg, rayDir, rngBuf, path, su, mat);
+        }
+        else what = pt_next_setup_displaced(a, d, sh, rayOrg, rayDir, rngBuf, path, su);
+    }
     else what = pt_next_setup<false>(a, active, h, rayOrg, rayDir, rngBuf, path, su);
     const EnvMap env = load_env(a.s);
     const bool envEnabled = env.present() && a.f.enableEnvLight;
@@ -696,6 +717,12 @@ __global__ __launch_bounds__(kPtBlock) void k_pt_bounce_scene(PtArgs a, Displace
     if (what & (kPtHitSurface | kPtMissAdded)) a.state[2ull * pixel + 1] = make_float4(path.contribution.x, path.contribution.y, path.contribution.z, 0.0f);
     push_vertex(a, pixel, path.pos, path.o);
 }
+__global__ __launch_bounds__(kPtBlock) void k_pt_bounce_scene(PtArgs a, DisplacedArgs d) {
+    DisplacedShellArgs none;
+    none.shellPart = nullptr; none.shellMats = nullptr;
+    pt_bounce_scene<false>(a, d, none);
+}
+__global__ __launch_bounds__(kPtBlock) void k_pt_bounce_scene_shell(PtArgs a, DisplacedArgs d, DisplacedShellArgs e) { pt_bounce_scene<true>(a, d, e); }
 
 // ---------------------------------------------------------------- ReGIR grid maintenance
 // sampleIntensity, regir/gpu_kernels/build_cell_reservoirs.cu:6-68 (the half-space tests compare lpCos,
@@ -1671,6 +1698,9 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
     ctx.ptState.reserve(32 * numPixels);
     if (nrc) { ctx.nrcState.reserve(32 * numPixels); ctx.neeTrainIdx.reserve(4 * numPixels); }
     if (displaced) { ctx.displaced.ptHits.reserve(sizeof(gfx_scene_hit) * bandPixels); ctx.displaced.ptPlain.reserve(sizeof(gfx_hit) * bandPixels); }
+    // a kinds binding over a set with a shell member: the extension trace hands the shell part of every hit on
+    const bool shellRender = displaced && displaced_shell_render(ctx);
+    if (shellRender) ctx.displaced.ptShellPart.reserve(sizeof(gfx_scene_shell_part) * bandPixels);
     ctx.smallCounters.reserve(kSmallCountersBytes);
     uint32_t* counters = ctx.smallCounters.as<uint32_t>() + 8;   // [0] nee (even bounces), [1] ext ping, [2] ext pong, [3] nee (odd bounces)
     GFX_HIP(hipMemsetAsync(counters, 0, 5 * sizeof(uint32_t), stream));   // [4]: the slot ticket of k_pt_regen
@@ -1726,6 +1756,7 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
             t.accel = &accel; t.set = ctx.displaced.set; t.mode = mode;
             t.rayOrgTmin = org; t.rayDirTmax = dir; t.numRays = static_cast<uint32_t>(bandPixels); t.numRaysPtr = count;
             t.out = out; t.plainHits = ctx.displaced.ptPlain.p;
+            if (shellRender && mode == GFX_TRACE_CLOSEST) t.shellPart = ctx.displaced.ptShellPart.p;
             t.zeroWords[0] = zero0; t.zeroWords[1] = zero1;
             if (auxScratch) { t.spill = &ctx.auxSpill; t.counters = &ctx.auxCounters; }
             trace_scene_launch(ctx, s, t);
@@ -1785,8 +1816,8 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
     }
     void* const extHits = displaced ? ctx.displaced.ptHits.p : ctx.rayHits.p;
     if (displaced) {
-        ScopedKernelTimer timer(ctx, stream, "pt_first_scene");
-        hipLaunchKernelGGL(k_pt_first_scene, dim3(a.px.launchBlocks), dim3(kPtBlock), 0, stream, a, displaced_args(ctx, extHits));
+        ScopedKernelTimer timer(ctx, stream, shellRender ? "pt_first_scene_shell" : "pt_first_scene");
+        hipLaunchKernelGGL(shellRender ? k_pt_first_scene_shell : k_pt_first_scene, dim3(a.px.launchBlocks), dim3(kPtBlock), 0, stream, a, displaced_args(ctx, extHits));
         GFX_HIP(hipGetLastError());
     }
     else if (nrc) launch_pixels("nrc_pt_first", nrcRegir ? k_nrc_pt_first<1> : nrcRestir ? k_nrc_pt_first<2> : k_nrc_pt_first<0>);
@@ -1825,8 +1856,11 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
         a.maxLengthTerminate = (pathLength >= maxPathLength && (!nrc || maxPathLength > 0)) ? 1u : 0u;
         a.nextMaxLengthTerminate = pathLength + 1 >= maxPathLength ? 1u : 0u;
         if (displaced) {
-            ScopedKernelTimer timer(ctx, stream, "pt_bounce_scene");
-            hipLaunchKernelGGL(k_pt_bounce_scene, dim3(grid), dim3(kPtBlock), 0, stream, a, displaced_args(ctx, extHits));
+            ScopedKernelTimer timer(ctx, stream, shellRender ? "pt_bounce_scene_shell" : "pt_bounce_scene");
+            if (shellRender)
+                hipLaunchKernelGGL(k_pt_bounce_scene_shell, dim3(grid), dim3(kPtBlock), 0, stream, a, displaced_args(ctx, extHits),
+                                   displaced_shell_args(ctx, ctx.displaced.ptShellPart.p));
+            else hipLaunchKernelGGL(k_pt_bounce_scene, dim3(grid), dim3(kPtBlock), 0, stream, a, displaced_args(ctx, extHits));
             GFX_HIP(hipGetLastError());
         }
         else if (nrc) launch(stream, "nrc_pt_bounce", nrcRegir ? k_nrc_pt_bounce<1> : nrcRestir ? k_nrc_pt_bounce<2> : k_nrc_pt_bounce<0>);

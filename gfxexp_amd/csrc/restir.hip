@@ -23,6 +23,7 @@
 #include "restir_rearch.hip.h"
 #include "tfdm/tfdm_set.h"
 #include "tfdm/displaced_surface.hip.h"
+#include "nrtdsm/displaced_kinds.hip.h"
 
 namespace gfx {
 
@@ -212,7 +213,10 @@ GFX_DEV tfdm::BaseVertex base_vertex(const DevVertex& v) {
     b.texCoord0Dir = tfdm::v3(v.tx, v.ty, v.tz); b.u = v.u; b.v = v.v;
     return b;
 }
-__global__ __launch_bounds__(kBlock) void k_gbuffer_resolve_scene(RestirArgs a, DisplacedArgs d) {
+// SHELL: the sibling for a binding of gfx_scene_bind_displaced_kinds whose set has a shell member (DESIGN.md section 24,
+// nrtdsm/displaced_kinds.hip.h): the shell part of the pixel's hit picks the material and goes into gbuffer0.geomInstSlot.
+template <bool SHELL>
+GFX_DEV void gbuffer_resolve_scene(const RestirArgs& a, const DisplacedArgs& d, const DisplacedShellArgs& e) {
     const PixelId px = pixel_of_thread(a.px);
     if (!px.valid) return;
     const float4 ro = a.rayOrg[px.slot], rd = a.rayDir[px.slot];
@@ -236,9 +240,17 @@ __global__ __launch_bounds__(kBlock) void k_gbuffer_resolve_scene(RestirArgs a, 
     // the instance's curToPrev (tfdm_set.hip commits it with the table): a load per lane, lanes sit on different instances
     const float4 m0 = d.motion[3u * k], m1 = d.motion[3u * k + 1u], m2 = d.motion[3u * k + 2u];
     const float curToPrev[12] = { m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w };
-    const tfdm::DisplacedGBuffer gb = tfdm::displaced_gbuffer(sp, sh, geomInstSlot, g.materialSlot, a.f.prevCamera, px.x, px.y, a.s.imageSizeX, a.s.imageSizeY,
-                                                              a.f.resetFlowBuffer != 0, curToPrev);
-    const gfx_material& mat = a.scene.materials[g.materialSlot];
+    uint32_t matSlot = g.materialSlot, shellGeom = 0u;
+    if (SHELL) {
+        const float4 part = e.shellPart[px.slot];                 // a gfx_scene_shell_part: one 16-byte load; zeros unless a shell member won
+        shellGeom = f2bits(part.y);
+        matSlot = tfdm::displaced_material(nrtdsm::instance_kind(d.table[k]), k, shellGeom, e.shellMats, g.materialSlot);
+    }
+    const tfdm::DisplacedGBuffer gb = SHELL ? tfdm::displaced_gbuffer_kinds(sp, sh, geomInstSlot, shellGeom, matSlot, a.f.prevCamera, px.x, px.y, a.s.imageSizeX,
+                                                                            a.s.imageSizeY, a.f.resetFlowBuffer != 0, curToPrev)
+                                            : tfdm::displaced_gbuffer(sp, sh, geomInstSlot, matSlot, a.f.prevCamera, px.x, px.y, a.s.imageSizeX, a.s.imageSizeY,
+                                                                      a.f.resetFlowBuffer != 0, curToPrev);
+    const gfx_material& mat = a.scene.materials[matSlot];
     Bsdf bsdf; bsdf.setup(a.scene, mat, sp.u, sp.v);
     const Frame frame(to_f3(sp.normal), to_f3(sp.tangent));
     const f3 albedo = bsdf.dh_reflectance_estimate(frame.to_local(unit(-f3(rd.x, rd.y, rd.z))));
@@ -246,6 +258,12 @@ __global__ __launch_bounds__(kBlock) void k_gbuffer_resolve_scene(RestirArgs a, 
                   make_float4(gb.position[0], gb.position[1], gb.position[2], bits2f(gb.qGeometricNormal)), make_uint4(gb.g3[0], gb.g3[1], gb.g3[2], gb.g3[3]),
                   albedo, to_f3(sp.normal));
 }
+__global__ __launch_bounds__(kBlock) void k_gbuffer_resolve_scene(RestirArgs a, DisplacedArgs d) {
+    DisplacedShellArgs none;
+    none.shellPart = nullptr; none.shellMats = nullptr;
+    gbuffer_resolve_scene<false>(a, d, none);
+}
+__global__ __launch_bounds__(kBlock) void k_gbuffer_resolve_scene_shell(RestirArgs a, DisplacedArgs d, DisplacedShellArgs e) { gbuffer_resolve_scene<true>(a, d, e); }
 
 // ---------------------------------------------------------------- INITIAL (+ TEMPORAL)
 // candidate loop + visibility-ray emission: optix_restir_di_kernels.cu:57-133
@@ -1388,9 +1406,16 @@ void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, u
             t.out = ctx.displaced.gbHits.p; t.plainHits = ctx.gbRayHits.p;
             t.spill = &ctx.gbSpill; t.counters = &ctx.gbCounters;
             t.hintFromOut = true;
+            // a kinds binding over a set with a shell member: the instance phase writes the shell part of every slot it traces
+            const bool shell = displaced_shell_render(ctx);
+            if (shell) { ctx.displaced.gbShellPart.reserve(sizeof(gfx_scene_shell_part) * frameSlots); t.shellPart = ctx.displaced.gbShellPart.p; }
             trace_scene_launch(ctx, stream, t);
-            ScopedKernelTimer timer(ctx, stream, "gbuffer_resolve_scene");
-            hipLaunchKernelGGL(k_gbuffer_resolve_scene, dim3(a.px.launchBlocks), dim3(kBlock), 0, stream, a, displaced_args(ctx, ctx.displaced.gbHits.p));
+            ScopedKernelTimer timer(ctx, stream, shell ? "gbuffer_resolve_scene_shell" : "gbuffer_resolve_scene");
+            if (shell)
+                hipLaunchKernelGGL(k_gbuffer_resolve_scene_shell, dim3(a.px.launchBlocks), dim3(kBlock), 0, stream, a, displaced_args(ctx, ctx.displaced.gbHits.p),
+                                   displaced_shell_args(ctx, ctx.displaced.gbShellPart.p));
+            else
+                hipLaunchKernelGGL(k_gbuffer_resolve_scene, dim3(a.px.launchBlocks), dim3(kBlock), 0, stream, a, displaced_args(ctx, ctx.displaced.gbHits.p));
             GFX_HIP(hipGetLastError());
             break;
         }

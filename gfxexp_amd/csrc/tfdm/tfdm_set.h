@@ -72,6 +72,14 @@ struct DisplacedArgs { const float4* hits; const tfdm::InstanceRecord* table; co
 void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint32_t n, uint32_t passMask);
 void displaced_check(Context& ctx, const char* who);
 DisplacedArgs displaced_args(const Context& ctx, const void* hits);
+// gfx_scene_bind_displaced_kinds: the binding that renders NRTDSM and shell members too.  displaced_check
+// knows which of the two calls made the binding.  The shell-aware siblings of the three set-bound kernels take, next to
+// DisplacedArgs, the shell part of every hit (one 16-byte gfx_scene_shell_part beside each gfx_scene_hit) and the material table;
+// they run only while displaced_shell_render(ctx): a kinds binding whose committed set has a shell member.
+void displaced_bind_kinds(Context& ctx, TfdmSet* set, const gfx_displaced_member* members, uint32_t n, uint32_t passMask);
+struct DisplacedShellArgs { const float4* shellPart; const uint32_t* shellMats; };
+bool displaced_shell_render(const Context& ctx);
+DisplacedShellArgs displaced_shell_args(const Context& ctx, const void* shellPart);
 void restir_primary_rays(Context& ctx, hipStream_t stream, uint32_t width, uint32_t height, void* dRayOrgTmin, void* dRayDirTmax);   // restir.hip
 // gfx_restir_last_rays: the queue and the occlusion words of the last ray pass that ran in its three-kernel form (restir.hip)
 void restir_last_rays(Context& ctx, hipStream_t stream, void* dRayOrgTmin, void* dRayDirTmax, void* dOccluded, uint32_t capacity, uint32_t* count);

@@ -30,6 +30,7 @@
 #include <cstring>
 #include "tfdm_set.h"
 #include "tfdm_lds_stack.hip.h"
+#include "../nrtdsm/displaced_kinds.hip.h"
 
 namespace gfx {
 
@@ -348,10 +349,47 @@ bool has_shell(const TfdmSet& s) {
     for (const TfdmSet::Member& m : s.members) if (is_shell(m)) return true;
     return false;
 }
-const char* const kNotRendered = "the set has an NRTDSM instance; NRTDSM instances are traced (gfx_trace_scene) but not rendered";
-const char* const kShellNotRendered = "the set has a shell instance; shell instances are traced (gfx_trace_scene) but not rendered";
-// a set that is traced but cannot be bound: the message, or null
+const char* const kNotRendered = "the set has an NRTDSM instance; NRTDSM instances are traced (gfx_trace_scene) but not rendered through this binding "
+                                 "(gfx_scene_bind_displaced_kinds renders them)";
+const char* const kShellNotRendered = "the set has a shell instance; shell instances are traced (gfx_trace_scene) but not rendered through this binding "
+                                      "(gfx_scene_bind_displaced_kinds renders them)";
+// a set that is traced but cannot be bound by gfx_scene_bind_displaced / _passes: the message, or null
 const char* not_rendered(const TfdmSet& s) { return has_nrtdsm(s) ? kNotRendered : has_shell(s) ? kShellNotRendered : nullptr; }
+
+// What gfx_scene_bind_displaced_kinds asks of member `m` beyond its geometry, at the bind and again at every launch (the shell
+// object's geometry and the materials may have changed in between): the refusal without the member's index, or empty.
+std::string kinds_member_refusal(const Context& ctx, const TfdmSet::Member& m, const gfx_displaced_member& d) {
+    if (!is_shell(m)) {
+        if (d.numShellMaterials != 0u)
+            return "numShellMaterials is " + std::to_string(d.numShellMaterials) + " for a member that is not a shell member (it must be 0)";
+        return std::string();
+    }
+    const uint32_t numGeoms = static_cast<const ShellObject*>(m.obj)->numGeoms;
+    if (d.numShellMaterials != numGeoms)
+        return std::to_string(d.numShellMaterials) + " shell materials for a shell object of " + std::to_string(numGeoms) + " shell geometries (shell geometry count mismatch)";
+    if (d.geomInstSlot >= (1u << tfdm::kGeomSlotBits))
+        return "geometry slot " + std::to_string(d.geomInstSlot) + " of a shell member must be below 2^28 (the G-buffer keeps the shell geometry in the upper four bits)";
+    for (uint32_t g = 0; g < numGeoms; ++g) {
+        const uint32_t slot = d.shellMatSlots[g];
+        if (slot >= ctx.materials.size()) return "unknown material slot " + std::to_string(slot) + " for shell geometry " + std::to_string(g);
+        if (ctx.materials[slot].hasEmittance)
+            return "the material of shell geometry " + std::to_string(g) + " (slot " + std::to_string(slot) + ") has emittance; displaced emitters are not supported";
+    }
+    return std::string();
+}
+
+// the checks both bind calls make of the geometry member k is shaded with
+void check_bound_geometry(const Context& ctx, const TfdmSet& set, uint32_t k, uint32_t geomSlot, const std::string& who) {
+    if (geomSlot >= ctx.geoms.size()) throw HipError(who + "unknown geometry slot " + std::to_string(geomSlot));
+    const HostGeom& g = ctx.geoms[geomSlot];
+    if (g.triangles.size() / 3 != set.members[k].obj->numTriangles)
+        throw HipError(who + "geometry slot " + std::to_string(geomSlot) + " has " + std::to_string(g.triangles.size() / 3) + " triangles, the displaced object " +
+                       std::to_string(set.members[k].obj->numTriangles) + " (triangle count mismatch)");
+    if (g.materialSlot < ctx.materials.size() && ctx.materials[g.materialSlot].hasEmittance)
+        throw HipError(who + "the material of geometry slot " + std::to_string(geomSlot) + " has emittance; displaced emitters are not supported");
+}
+
+void unbind(DisplacedBinding& b) { b.set = nullptr; b.geomSlots.clear(); b.passMask = 0u; b.kinds = false; b.members.clear(); }
 
 } // namespace
 
@@ -511,21 +549,14 @@ void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint3
     DisplacedBinding& b = ctx.displaced;
     if (passMask & ~(GFX_DISPLACED_GBUFFER_PT | GFX_DISPLACED_RESTIR))
         throw HipError("gfx_scene_bind_displaced_passes: unknown bit in the pass mask " + std::to_string(passMask));
-    if (!set) { b.set = nullptr; b.geomSlots.clear(); b.passMask = 0u; return; }
+    if (!set) { unbind(b); return; }
     if (set->device != ctx.device) throw HipError("gfx_scene_bind_displaced: the instance set belongs to another device");
     if (const char* why = not_rendered(*set)) throw HipError(std::string("gfx_scene_bind_displaced: ") + why);
     if (n != set->members.size())
         throw HipError("gfx_scene_bind_displaced: " + std::to_string(n) + " geometry slots for a set of " + std::to_string(set->members.size()) + " instances");
     if (n && !geomSlots) throw HipError("gfx_scene_bind_displaced: null geometry slots");
     for (uint32_t k = 0; k < n; ++k) {
-        const std::string who = "gfx_scene_bind_displaced: instance " + std::to_string(k) + ": ";
-        if (geomSlots[k] >= ctx.geoms.size()) throw HipError(who + "unknown geometry slot " + std::to_string(geomSlots[k]));
-        const HostGeom& g = ctx.geoms[geomSlots[k]];
-        if (g.triangles.size() / 3 != set->members[k].obj->numTriangles)
-            throw HipError(who + "geometry slot " + std::to_string(geomSlots[k]) + " has " + std::to_string(g.triangles.size() / 3) + " triangles, the displaced object " +
-                           std::to_string(set->members[k].obj->numTriangles) + " (triangle count mismatch)");
-        if (g.materialSlot < ctx.materials.size() && ctx.materials[g.materialSlot].hasEmittance)
-            throw HipError(who + "the material of geometry slot " + std::to_string(geomSlots[k]) + " has emittance; displaced emitters are not supported");
+        check_bound_geometry(ctx, *set, k, geomSlots[k], "gfx_scene_bind_displaced: instance " + std::to_string(k) + ": ");
     }
     // (a reserve() that has to grow frees the old table with hipFree, which waits for the passes that read it)
     std::vector<uint32_t> slots(geomSlots, geomSlots + n);
@@ -534,12 +565,47 @@ void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint3
     b.geomSlots.swap(slots);
     b.set = set;
     b.passMask = passMask | GFX_DISPLACED_GBUFFER_PT;
+    b.kinds = false;
+    b.members.clear();
+}
+
+// The binding of displaced_bind with one more table, and without its refusal of NRTDSM and shell members.  Every check comes before
+// the first change of the binding: a refused call leaves the binding as it was.
+void displaced_bind_kinds(Context& ctx, TfdmSet* set, const gfx_displaced_member* members, uint32_t n, uint32_t passMask) {
+    DisplacedBinding& b = ctx.displaced;
+    const std::string me = "gfx_scene_bind_displaced_kinds: ";
+    if (passMask & ~(GFX_DISPLACED_GBUFFER_PT | GFX_DISPLACED_RESTIR)) throw HipError(me + "unknown bit in the pass mask " + std::to_string(passMask));
+    if (!set) { unbind(b); return; }
+    if (set->device != ctx.device) throw HipError(me + "the instance set belongs to another device");
+    if (n != set->members.size())
+        throw HipError(me + std::to_string(n) + " members for a set of " + std::to_string(set->members.size()) + " instances");
+    if (n && !members) throw HipError(me + "null members");
+    std::vector<uint32_t> slots(n), mats(static_cast<size_t>(tfdm::kShellMatsPerMember) * n, 0u);
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::string who = me + "instance " + std::to_string(k) + ": ";
+        const std::string why = kinds_member_refusal(ctx, set->members[k], members[k]);       // first: a shell member's slot >= 2^28 is named as such
+        if (!why.empty()) throw HipError(who + why);
+        check_bound_geometry(ctx, *set, k, members[k].geomInstSlot, who);
+        slots[k] = members[k].geomInstSlot;
+        for (uint32_t g = 0; g < members[k].numShellMaterials; ++g) mats[tfdm::kShellMatsPerMember * k + g] = members[k].shellMatSlots[g];
+    }
+    b.dGeomSlots.reserve(std::max<size_t>(sizeof(uint32_t) * n, 16));
+    b.dShellMats.reserve(std::max<size_t>(sizeof(uint32_t) * mats.size(), 16));
+    if (n) {
+        GFX_HIP(hipMemcpy(b.dGeomSlots.p, slots.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+        GFX_HIP(hipMemcpy(b.dShellMats.p, mats.data(), sizeof(uint32_t) * mats.size(), hipMemcpyHostToDevice));
+    }
+    b.geomSlots.swap(slots);
+    b.members.assign(members, members + n);
+    b.set = set;
+    b.passMask = passMask | GFX_DISPLACED_GBUFFER_PT;
+    b.kinds = true;
 }
 
 void displaced_check(Context& ctx, const char* who) {
     const DisplacedBinding& b = ctx.displaced;
     trace_scene_check_set(*b.set, ctx.device, who);
-    if (const char* why = not_rendered(*b.set)) throw HipError(std::string(who) + ": " + why);      // a member added after the bind
+    if (!b.kinds) if (const char* why = not_rendered(*b.set)) throw HipError(std::string(who) + ": " + why);      // a member added after the bind
     if (b.geomSlots.size() != b.set->members.size())
         throw HipError(std::string(who) + ": the bound instance set has grown since gfx_scene_bind_displaced; bind it again");
     for (size_t k = 0; k < b.geomSlots.size(); ++k) {
@@ -548,7 +614,20 @@ void displaced_check(Context& ctx, const char* who) {
         const uint32_t m = ctx.geoms[b.geomSlots[k]].materialSlot;
         if (m < ctx.materials.size() && ctx.materials[m].hasEmittance)
             throw HipError(std::string(who) + ": the material of displaced instance " + std::to_string(k) + " has emittance; displaced emitters are not supported");
+        if (b.kinds) {       // gfx_shell_set_geometry (with a new commit) and gfx_material_set may have run since the bind
+            const std::string why = kinds_member_refusal(ctx, b.set->members[k], b.members[k]);
+            if (!why.empty()) throw HipError(std::string(who) + ": displaced instance " + std::to_string(k) + ": " + why + "; bind the set again");
+        }
     }
+}
+
+bool displaced_shell_render(const Context& ctx) { return ctx.displaced.set && ctx.displaced.kinds && ctx.displaced.set->anyShell; }
+
+DisplacedShellArgs displaced_shell_args(const Context& ctx, const void* shellPart) {
+    DisplacedShellArgs e;
+    e.shellPart = static_cast<const float4*>(shellPart);
+    e.shellMats = ctx.displaced.dShellMats.as<uint32_t>();
+    return e;
 }
 
 DisplacedArgs displaced_args(const Context& ctx, const void* hits) {

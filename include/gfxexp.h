@@ -932,7 +932,8 @@ int gfx_tfdm_set_add(gfx_tfdm_set* set, gfx_tfdm* obj, const float objToWorld[12
  * gfx_tfdm_set_add (a null object, an object of another device and a 1025th member are refused), and *index counts all members in
  * add order, whatever their kind.  Transform, move, commit, both reads and gfx_trace_scene treat it as any member; gfx_nrtdsm_set_params
  * on it asks for a new commit as gfx_tfdm_set_params does.  The kind of a member is the word after boxHi of its record.  Such a set is
- * traced but not rendered: gfx_scene_bind_displaced and gfx_scene_bind_displaced_passes refuse it. */
+ * rendered through gfx_scene_bind_displaced_kinds; gfx_scene_bind_displaced and gfx_scene_bind_displaced_passes
+ * refuse it (by them it is traced but not rendered). */
 #define GFX_INSTANCE_TFDM 0u
 #define GFX_INSTANCE_NRTDSM 1u
 int gfx_tfdm_set_add_nrtdsm(gfx_tfdm_set* set, gfx_nrtdsm* obj, const float objToWorld[12], uint32_t userId, uint32_t* index);
@@ -940,7 +941,8 @@ int gfx_tfdm_set_add_nrtdsm(gfx_tfdm_set* set, gfx_nrtdsm* obj, const float objT
  * *index counts all members in add order whatever their kind, and transform, move, commit, both reads, the motion table and
  * gfx_trace_scene treat it as any member.  gfx_shell_set_params and gfx_shell_set_geometry on it ask for a new commit.  In its
  * record the two height-map pointers carry the shell BVH's nodes and triangles (csrc/nrtdsm/shell_instance.hip.h).  Such a set is
- * traced but not rendered: gfx_scene_bind_displaced and gfx_scene_bind_displaced_passes refuse it. */
+ * rendered through gfx_scene_bind_displaced_kinds, one material per shell geometry; gfx_scene_bind_displaced
+ * and gfx_scene_bind_displaced_passes refuse it (by them it is traced but not rendered). */
 #define GFX_INSTANCE_SHELL 2u
 int gfx_tfdm_set_add_shell(gfx_tfdm_set* set, gfx_shell* obj, const float objToWorld[12], uint32_t userId, uint32_t* index);
 int gfx_tfdm_set_transform(gfx_tfdm_set* set, uint32_t index, const float objToWorld[12]);
@@ -1013,6 +1015,22 @@ int gfx_scene_bind_displaced(gfx_ctx* ctx, gfx_tfdm_set* set, const uint32_t* ge
 #define GFX_DISPLACED_GBUFFER_PT 1u   /* the G-buffer passes and the baseline path tracer */
 #define GFX_DISPLACED_RESTIR 2u       /* ... and the ReSTIR passes, the rearchitected set included */
 int gfx_scene_bind_displaced_passes(gfx_ctx* ctx, gfx_tfdm_set* set, const uint32_t* geomInstSlots, uint32_t n, uint32_t passMask);
+/* The binding for a set with members of any kind: the two calls above refuse a set that has an NRTDSM or a
+ * shell member, this one renders it.  members[k] describes member k of the set; passMask as above; set == NULL unbinds.  An NRTDSM
+ * member is shaded as a TFDM member is (its hit has the same fields).  A shell member has one material per shell geometry, as the
+ * reference's materialSlots[shellBvhGeomIndex]: a hit on shell geometry g is shaded with shellMatSlots[g]; texture coordinate and
+ * tangent stay the base triangle's.  In the G-buffers of a set that has a shell member, gbuffer0.geomInstSlot of a displaced pixel
+ * is geomInstSlot | shellGeom << 28 (shellGeom 0 for a member of another kind) and gbuffer3.matSlot the material chosen.
+ * Refused, besides what gfx_scene_bind_displaced_passes refuses, with the member's index in the message: a shell member whose
+ * numShellMaterials is not the object's number of shell geometries, another member with a count other than 0, an unknown material
+ * slot among the first numShellMaterials, one that emits, a shell member's geomInstSlot >= 2^28.  The counts and the materials are
+ * checked again at every launch (gfx_shell_set_geometry and gfx_material_set may have run since). */
+typedef struct gfx_displaced_member {
+    uint32_t geomInstSlot;        /* as geomInstSlots[k] of gfx_scene_bind_displaced */
+    uint32_t numShellMaterials;   /* 0 for a TFDM / NRTDSM member; for a shell member the object's number of shell geometries (1..8) */
+    uint32_t shellMatSlots[8];    /* material of shell geometry g; entries >= numShellMaterials are ignored */
+} gfx_displaced_member;           /* 40 bytes */
+int gfx_scene_bind_displaced_kinds(gfx_ctx* ctx, gfx_tfdm_set* set, const gfx_displaced_member* members, uint32_t n, uint32_t passMask);
 /* The primary rays the G-buffer pass of the current parameters (gfx_restir_set_params) generates, by the device function the pass
  * runs: row-major, one ray per pixel, gfx_trace's layout.  With jittering on it reads rngBuffer and does not write it back. */
 int gfx_restir_primary_rays(gfx_ctx* ctx, void* stream, uint32_t width, uint32_t height, void* dRayOrgTmin, void* dRayDirTmax);

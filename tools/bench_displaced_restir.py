@@ -1,12 +1,16 @@
 """ReSTIR DI over a bound set of displaced instances, for an MI355X.
 
-    python tools/bench_displaced_restir.py [--size 1024] [--frames 20] [--width 1920] [--height 1080] [--step-timeout 300]
+    python tools/bench_displaced_restir.py [--nrtdsm | --shell] [--size 1024] [--frames 20] [--width 1920] [--height 1080] [--step-timeout 300]
 
 The scene of tfdm_common.lit_mixed_scene (tools/tfdm_view.py --scene under its emissive rectangle).  A frame is the G-buffer pass,
 INITIAL_AND_TEMPORAL_BIASED (INITIAL_RIS in frame 0), two SPATIAL_BIASED passes and SHADING.
 
   displaced     the two quads as an instance set bound with GFX_DISPLACED_RESTIR: every shadow ray is the scene's any-hit query
   tessellated   the two quads tessellated into the BVH8 (two triangles per texel), "fuse_passes" 1: the same three-kernel form
+
+With --nrtdsm / --shell one more row, the scene of tools/bench_scene_trace.py --nrtdsm / --shell: "displaced_nrtdsm" (the wall an NRTDSM
+member) or "displaced_shell" (the wall the "One Box" shell at 64 x 64 tiles under a material of its own), the set bound through
+gfx_scene_bind_displaced_kinds with GFX_DISPLACED_RESTIR; the result has "<row>_over_displaced_ms".
 
 displaced / tessellated: milliseconds per frame (HIP events around --frames frames after 3 warm-up frames), per-kernel times of one
 more frame from the context's timers, device bytes of the geometry (as tools/bench_displaced_render.py counts them).  Prints one JSON line.
@@ -31,16 +35,19 @@ sys.path.insert(0, HERE)
 
 STEPS = ["displaced", "tessellated"]
 MOVE_STEPS = ["move", "teleport"]
+KIND_STEPS = {"--nrtdsm": "displaced_nrtdsm", "--shell": "displaced_shell"}
+SHELL_TILES = 64            # tools/bench_scene_trace.py
 
 
 def _arg(argv, name, default):
     return type(default)(argv[argv.index(name) + 1]) if name in argv else default
 
 
-def _setup(size, tess):
+def _setup(size, tess, kind=None):
     from gfxexp_amd import api
     import tfdm_common as K
     hs, (v, t, heights, gp), instances, slot, pos, target = K.lit_mixed_scene(size, tessellate=tess)
+    shell_mat = hs.add_material_traditional((0.8, 0.45, 0.25), (0.0, 0.0, 0.0), 0.0)
     ctx = api.Context(0)
     hs.upload(ctx)
     accel = ctx.accel_build()
@@ -53,12 +60,20 @@ def _setup(size, tess):
         out["device_bytes"] = 64 * (stats["nodes"] + stats["triRecords"]) + 44 * (size + 1) ** 2 + 12 * 2 * size * size
     else:
         tf = api.Tfdm(ctx, v, t, heights, gp)
+        wall = None         # the objects of tools/bench_scene_trace.py
+        if kind == "displaced_nrtdsm":
+            wall = api.Nrtdsm(ctx, v, t, heights, api.tfdm_params(h_scale=gp.hScale, tex_scale=(gp.texScale[0], gp.texScale[1])))
+        if kind == "displaced_shell":
+            wall = api.Shell(ctx, v, t, [api.shell_box()], api.shell_params(h_scale=8.0 / SHELL_TILES, tex_scale=(float(SHELL_TILES), float(SHELL_TILES))))
         tset = api.TfdmSet(ctx)
-        for m, uid in instances:
-            tset.add(tf, m, uid)
+        for k, (m, uid) in enumerate(instances):
+            tset.add(wall if wall is not None and k == len(instances) - 1 else tf, m, uid)
         tset.commit()
-        ctx.bind_displaced(tset, [slot] * len(instances), restir=True)
-        out["device_bytes"] = tf.device_bytes() + api.TFDM_RECORD_BYTES * len(instances)
+        if wall is None:
+            ctx.bind_displaced(tset, [slot] * len(instances), restir=True)
+        else:
+            ctx.bind_displaced_kinds(tset, [slot] * (len(instances) - 1) + [(slot, [shell_mat]) if kind == "displaced_shell" else slot], restir=True)
+        out["device_bytes"] = tf.device_bytes() + (wall.device_bytes() if wall is not None else 0) + api.TFDM_RECORD_BYTES * len(instances)
         keep = (tf, tset, instances)
     return ctx, accel, keep, pos, target, out
 
@@ -66,7 +81,7 @@ def _setup(size, tess):
 def step_frames(name, size, frames, w, h):
     import torch
     import tfdm_common as K
-    ctx, accel, keep, pos, target, out = _setup(size, name == "tessellated")
+    ctx, accel, keep, pos, target, out = _setup(size, name == "tessellated", name if name in KIND_STEPS.values() else None)
     fr = K.RestirFrames(ctx, accel, w, h)
     cam = K.look_at_camera(w, h, pos, target)
     stream = torch.cuda.current_stream().cuda_stream
@@ -100,7 +115,7 @@ def step_frames(name, size, frames, w, h):
     out["kernel_ms"] = {k: round(ms, 4) for k, (ms, calls) in sorted(ctx.timing_collect().items())}
     ctx.timing_enable(False)
     out["mean_radiance"] = round(float(fr.beauty()[:, :3].mean()), 5)
-    ctx.bind_displaced(None)
+    ctx.bind_displaced_kinds(None)
     return out
 
 
@@ -114,7 +129,8 @@ def main(argv):
     limit = _arg(argv, "--step-timeout", 300)
     move = "--move" in argv
     result = {"metric": "displaced_restir_move" if move else "displaced_restir", "size": size, "frames": frames, "width": w, "height": h}
-    for name in (MOVE_STEPS if move else STEPS):
+    steps = MOVE_STEPS if move else STEPS + [KIND_STEPS[f] for f in KIND_STEPS if f in argv]
+    for name in steps:
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name, "--size", str(size), "--frames", str(frames),
                "--width", str(w), "--height", str(h)]
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -130,6 +146,8 @@ def main(argv):
         return 0
     result["tessellated_over_displaced_ms"] = round(result["tessellated"]["ms_per_frame"] / result["displaced"]["ms_per_frame"], 3)
     result["tessellated_over_displaced_bytes"] = round(result["tessellated"]["device_bytes"] / result["displaced"]["device_bytes"], 1)
+    for name in steps[len(STEPS):]:
+        result[name + "_over_displaced_ms"] = round(result[name]["ms_per_frame"] / result["displaced"]["ms_per_frame"], 3)
     print(json.dumps(result))
     return 0
 

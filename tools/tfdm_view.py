@@ -30,14 +30,16 @@ and <out>_instance.png (plain geometry grey, every displaced instance a colour o
     python tools/tfdm_view.py --scene --nrtdsm [--size 256] [--width 960] [--height-px 540] [--out tfdm_view]
 
 --scene --nrtdsm: the same scene with the wall an NRTDSM member of the set (gfx_tfdm_set_add_nrtdsm; the ground stays TFDM), the same
-three images through the same ONE gfx_trace_scene call.  Such a set is traced, not rendered: --render and --restir refuse it.
+three images through the same ONE gfx_trace_scene call.  With --render or --restir the set is bound through
+gfx_scene_bind_displaced_kinds and rendered.
 
     python tools/tfdm_view.py --scene --shell [box|bunny] [--tiles 16] [--width 960] [--height-px 540] [--out tfdm_view]
 
 --scene --shell: the same scene with the wall a shell member of the set (gfx_tfdm_set_add_shell: the "One Box" shell or the 309-face
 bunny, --tiles x --tiles over the wall's mesh; the ground stays TFDM), through ONE gfx_trace_scene_ex call.  The same three images
 and <out>_geom.png, from the call's side output: the shell geometry of the hit as a colour, its tile as a checkerboard; black where
-the winner is no shell member.  Traced, not rendered, as with --nrtdsm.
+the winner is no shell member.  With --render or --restir the set is rendered as with --nrtdsm, the shell geometry under a material
+of its own.
 
     python tools/tfdm_view.py --scene --render [--frames 64] [--size 256] [--width 960] [--height-px 540] [--out tfdm_view]
 
@@ -57,6 +59,7 @@ frame after the first) and the ground fixed; temporal reuse is on and nothing is
 <out>_move.png and its motion vectors as <out>_motion.png (red / green = 0.5 + mv / 16 pixels: grey stands still)."""
 import argparse
 import json
+import ctypes as C
 import os
 import sys
 
@@ -85,16 +88,29 @@ def _depth_image(dist, hit, n):
 def scene_render(a):
     hs, (v, t, heights, gp), instances, slot, pos, target = K.lit_mixed_scene(a.size)
     gp.localIntersection = _local(a)
+    warm = api.GfxMaterial()
+    warm.bsdfType = 0                                       # GFX_BSDF_LAMBERT: the material of the shell geometry of a --shell wall
+    warm.a = (C.c_float * 3)(0.8, 0.45, 0.25)
+    shell_mat = hs.add_material(warm)
     ctx = api.Context(0)
     hs.upload(ctx)
     accel = ctx.accel_build()
     ctx.lights_build_static()
     tf = api.Tfdm(ctx, v, t, heights, gp)
+    # --nrtdsm / --shell: the wall (the last instance) as in scene_view; such a set is bound through gfx_scene_bind_displaced_kinds,
+    # a shell wall with one material per shell geometry
+    wall = api.Nrtdsm(ctx, v, t, heights, api.tfdm_params(h_scale=gp.hScale, tex_scale=(gp.texScale[0], gp.texScale[1]))) if a.nrtdsm else None
+    if a.shell:
+        wall = api.Shell(ctx, v, t, [K.shell_geom(a.shell)], api.shell_params(h_scale=0.5 * K.extent(v), tex_scale=(a.tiles, a.tiles)))
     tset = api.TfdmSet(ctx)
-    for m, uid in instances:
-        tset.add(tf, m, uid)
+    for k, (m, uid) in enumerate(instances):
+        tset.add(wall if wall is not None and k == len(instances) - 1 else tf, m, uid)
     tset.commit()
-    ctx.bind_displaced(tset, [slot] * len(instances), restir=a.restir)
+    if wall is None:
+        ctx.bind_displaced(tset, [slot] * len(instances), restir=a.restir)
+    else:
+        members = [slot] * (len(instances) - 1) + [(slot, [shell_mat]) if a.shell else slot]
+        ctx.bind_displaced_kinds(tset, members, restir=a.restir)
     w, h = a.width, a.height_px
     frames = K.RestirFrames(ctx, accel, w, h) if a.restir else K.PathTraceFrames(ctx, accel, w, h)
     cam = K.look_at_camera(w, h, pos, target)
@@ -104,13 +120,13 @@ def scene_render(a):
     for k in range(a.frames):
         frames.frame(k, cam, stream=stream)
     beauty = frames.beauty()
-    ctx.bind_displaced(None)
+    ctx.bind_displaced_kinds(None)
     image = a.out + ("_restir.png" if a.restir else "_render.png")
     api.save_image_sdr(image, beauty, w, h, api.sdr_config(brightness=1.0, tone_map=True, gamma=True))
     g0 = frames.t["gb0_%d" % ((a.frames - 1) % 2)].cpu().numpy().view(np.uint32).reshape(-1, 4)[:, 0]
     print(json.dumps({"scene": "teapot on displaced ground, displaced wall, emissive rectangle", "size": int(heights.shape[0]), "frames": a.frames,
                       "displaced_pixel_share": round(float(((g0 != api.GFX_INVALID_SLOT) & (g0 >= api.GBUFFER_DISPLACED)).mean()), 4),
-                      "renderer": "restir_di" if a.restir else "path_tracer", "mean_radiance": round(float(beauty[:, :3].mean()), 5), "images": [image]}))
+                      "renderer": "restir_di" if a.restir else "path_tracer", "wall": "nrtdsm" if a.nrtdsm else "shell" if a.shell else "tfdm", "mean_radiance": round(float(beauty[:, :3].mean()), 5), "images": [image]}))
     return 0
 
 
@@ -276,10 +292,8 @@ def main():
     if a.move and not (a.scene and a.restir):
         ap.error("--move goes with --scene --restir")
     if a.render or a.restir:
-        if a.nrtdsm:
-            ap.error("--nrtdsm with --scene is traced, not rendered: a set with an NRTDSM instance cannot be bound")
-        if a.shell:
-            ap.error("--shell with --scene is traced, not rendered: a set with a shell instance cannot be bound")
+        if a.shell and a.nrtdsm:
+            ap.error("--scene takes the wall as --nrtdsm or as --shell, not both")
         return scene_render(a)
     if a.scene:
         if a.shell and a.nrtdsm:
