@@ -345,6 +345,7 @@ C_ABI_SYMBOLS = [
     "gfx_scene_bind_displaced_kinds",
     "gfx_nrtdsm_create", "gfx_nrtdsm_set_params", "gfx_nrtdsm_destroy", "gfx_nrtdsm_trace", "gfx_nrtdsm_read", "gfx_nrtdsm_size",
     "gfx_shell_create", "gfx_shell_set_params", "gfx_shell_set_geometry", "gfx_shell_destroy", "gfx_shell_trace", "gfx_shell_read", "gfx_shell_size",
+    "gfx_tfdm_update_heights", "gfx_nrtdsm_update_heights",
 ]
 HOST_ABI_SYMBOLS = [
     "gfxh_scene_create", "gfxh_scene_destroy", "gfxh_last_error", "gfxh_scene_add_material_traditional",
@@ -1399,6 +1400,12 @@ class _HeightMapObject(_DisplacedObject):
 
     def _level(self, level):
         return (C.c_uint32(level),)
+
+    def update_heights(self, d_src, x0, y0, w, h, pitch=None, stream=0):
+        """gfx_*_update_heights: d_src is a device pointer (int) to float32 heights, row j of the rectangle at d_src + 4 * j * pitch
+        (pitch in floats, default w).  The level-0 rectangle (x0, y0, w, h) of the map takes them, in place; synchronous on `stream`."""
+        self._call("update_heights", self.ctx.h, C.c_void_p(stream), self.h, C.c_void_p(d_src or None), C.c_uint32(w if pitch is None else pitch),
+                   C.c_uint32(x0), C.c_uint32(y0), C.c_uint32(w), C.c_uint32(h))
 
     def size_of(self, what, level=0):
         return self._size(what, level)

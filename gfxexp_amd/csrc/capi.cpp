@@ -794,6 +794,12 @@ int gfx_tfdm_set_params(gfx_ctx* ctx, void* stream, gfx_tfdm* obj, const gfx_tfd
     tfdm_set_params(obj->o, static_cast<hipStream_t>(stream), *params);
     GFX_CATCH(ctx)
 }
+int gfx_tfdm_update_heights(gfx_ctx* ctx, void* stream, gfx_tfdm* obj, const float* dSrc, uint32_t srcPitch, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
+    GFX_TRY(ctx)
+    displaced_guard(ctx, obj, "gfx_tfdm_update_heights");
+    tfdm_update_heights(ctx->c, obj->o, static_cast<hipStream_t>(stream), dSrc, srcPitch, x0, y0, w, h);
+    GFX_CATCH(ctx)
+}
 int gfx_tfdm_destroy(gfx_tfdm* obj) { return displaced_destroy(obj); }
 int gfx_tfdm_trace(gfx_ctx* ctx, void* stream, gfx_tfdm* obj, int mode, const void* dRayOrgTmin, const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters) {
     GFX_TRY(ctx)
@@ -826,6 +832,12 @@ int gfx_nrtdsm_set_params(gfx_ctx* ctx, void* stream, gfx_nrtdsm* obj, const gfx
     GFX_TRY(ctx)
     displaced_guard(ctx, obj, "gfx_nrtdsm_set_params", " or parameters", params);
     nrtdsm_set_params(obj->o, static_cast<hipStream_t>(stream), *params);
+    GFX_CATCH(ctx)
+}
+int gfx_nrtdsm_update_heights(gfx_ctx* ctx, void* stream, gfx_nrtdsm* obj, const float* dSrc, uint32_t srcPitch, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
+    GFX_TRY(ctx)
+    displaced_guard(ctx, obj, "gfx_nrtdsm_update_heights");
+    nrtdsm_update_heights(ctx->c, obj->o, static_cast<hipStream_t>(stream), dSrc, srcPitch, x0, y0, w, h);
     GFX_CATCH(ctx)
 }
 int gfx_nrtdsm_destroy(gfx_nrtdsm* obj) { return displaced_destroy(obj); }

@@ -14,6 +14,7 @@ struct NrtdsmObject : HeightMapObject {
 void nrtdsm_init(NrtdsmObject& o, hipStream_t stream, const void* vertices, uint32_t stride, uint32_t numVertices, const uint32_t* triangles, uint32_t numTriangles,
                  const float* const* heightLevels, uint32_t numLevels, uint32_t size, const gfx_tfdm_params& params);
 void nrtdsm_set_params(NrtdsmObject& o, hipStream_t stream, const gfx_tfdm_params& params);
+void nrtdsm_update_heights(Context& ctx, NrtdsmObject& o, hipStream_t stream, const float* dSrc, uint32_t srcPitch, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h);
 void nrtdsm_trace(NrtdsmObject& o, hipStream_t stream, int mode, const void* dRayOrgTmin, const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters);
 
 } // namespace gfx

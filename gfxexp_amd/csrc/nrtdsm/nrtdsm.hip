@@ -25,6 +25,7 @@ using namespace tfdm;
 namespace {
 
 #include "../tfdm/tfdm_pyramid.hip.h"       // k_tfdm_minmax_first, k_tfdm_minmax_level
+#include "../tfdm/tfdm_update.hip.h"        // k_tfdm_update_*, k_tfdm_refit_*, update_heights
 
 constexpr int kTraceBlock = 64;             // one wave per block
 
@@ -95,6 +96,8 @@ void build_geometry(NrtdsmObject& o, hipStream_t stream, const gfx_tfdm_params& 
         k_nrtdsm_prim<<<(o.numTriangles + 63u) / 64u, 64, 0, stream>>>(records.as<nrtdsm::PrismRecord>(), o.pyramid.as<F2>(), p, o.numTriangles, aabbs.as<Box>());
     });
     ++o.generation;
+    o.levelTableValid = false;
+    o.lastChange = nullptr;
 }
 
 } // namespace
@@ -110,6 +113,7 @@ void nrtdsm_init(NrtdsmObject& o, hipStream_t stream, const void* vertices, uint
     if (!nrtdsm::heights_in_unit_range(levels))
         throw HipError("gfx_nrtdsm_create: a height map value lies outside [0, 1] (the descent clips the map value to that range)");
     o.size = size;
+    o.ownMips = numLevels > 1u;
     const std::vector<nrtdsm::PrismRecord> recs = make_records(o, g, make_params(g, size));      // every refusal comes before the first launch
     upload_height_map(o, stream, levels);
     build_geometry(o, stream, g, recs);
@@ -118,6 +122,21 @@ void nrtdsm_init(NrtdsmObject& o, hipStream_t stream, const void* vertices, uint
 void nrtdsm_set_params(NrtdsmObject& o, hipStream_t stream, const gfx_tfdm_params& g) {
     check_params(g);
     build_geometry(o, stream, g, make_records(o, g, make_params(g, o.size)));
+}
+
+// The map changed in place (tfdm/tfdm_update.hip.h).  k_nrtdsm_prim runs again on the records it wrote before: minHeight and
+// amplitude are outputs it never reads, and the one input it writes, numRoots = 0, it writes only where the two are not finite.
+// With map values in [0, 1] that is decided by the record (no texel under the footprint) unless baseHeight + heightScale h can
+// overflow; for such parameters the box of a primitive is empty or not by the heights, and the records and the tree are made
+// again from the host's records instead, as set_params makes them.
+void nrtdsm_update_heights(Context& ctx, NrtdsmObject& o, hipStream_t stream, const float* dSrc, uint32_t srcPitch, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
+    const bool byRecordAlone = std::fabs(static_cast<double>(o.params.baseHeight)) + std::fabs(static_cast<double>(o.params.heightScale)) < 1.0e38;
+    const bool refitted = update_heights(ctx, o, stream, dSrc, srcPitch, x0, y0, w, h, true, byRecordAlone, [&]() {
+        k_nrtdsm_prim<<<(o.numTriangles + 63u) / 64u, 64, 0, stream>>>(o.records.as<nrtdsm::PrismRecord>(), o.pyramid.as<F2>(), o.params, o.numTriangles, o.aabbs.as<Box>());
+    }, o.root);
+    if (refitted) ++o.generation;
+    else build_geometry(o, stream, o.pub, make_records(o, o.pub, make_params(o.pub, o.size)));
+    o.lastChange = "gfx_nrtdsm_update_heights";
 }
 
 void nrtdsm_trace(NrtdsmObject& o, hipStream_t stream, int mode, const void* dRayOrgTmin, const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters) {

@@ -9,6 +9,7 @@
 #pragma once
 #include "../internal.h"
 #include "tfdm_build.h"
+#include "tfdm_update.h"
 
 namespace gfx {
 
@@ -29,12 +30,22 @@ struct DisplacedObject {
 struct HeightMapObject : DisplacedObject {
     uint32_t size = 0;
     DevBuf heights, pyramid;            // all levels behind one another (tfdm::level_offset)
+    bool ownMips = false;               // created with every level supplied: the coarser levels are not means of the finer ones
+    const char* lastChange = nullptr;   // the call that made this generation, when it is not set_params: a stale member's message names it
+    // what *_update_heights needs (tfdm_update.hip.h), allocated at the first update: an object that is never updated owns none of it
+    DevBuf updateFlags, levelOrder;     // eight flag words; the tree's node indices sorted by depth (tfdm_update.h LevelTable)
+    void* updateHost = nullptr;         // pinned: the flag words and the root node as they come back
+    tfdm::LevelTable levelTable;        // offsets of `levelOrder`; made from the tree at the first update of a generation
+    bool levelTableValid = false;       // false again whenever `nodes` becomes a new tree (create, set_params)
+    uint32_t numNonEmpty = 0;           // primitives whose box is not empty, counted when the table was made
     using DisplacedObject::DisplacedObject;
 };
 
 inline void displaced_release(DisplacedObject& o) { o.records.release(); o.aabbs.release(); o.nodes.release(); }
 inline void displaced_release(HeightMapObject& o) {
-    o.heights.release(); o.pyramid.release();
+    o.heights.release(); o.pyramid.release(); o.updateFlags.release(); o.levelOrder.release();
+    if (o.updateHost) (void)hipHostFree(o.updateHost);
+    o.updateHost = nullptr;
     displaced_release(static_cast<DisplacedObject&>(o));
 }
 
@@ -131,7 +142,7 @@ inline size_t displaced_size(const DisplacedObject& o, int what) {
 inline size_t displaced_size(const HeightMapObject& o, int what, uint32_t level) {
     const DisplacedObject& base = o;
     switch (what) {
-    case -1: return o.heights.bytes + o.pyramid.bytes + displaced_size(base, -1);
+    case -1: return o.heights.bytes + o.pyramid.bytes + o.updateFlags.bytes + o.levelOrder.bytes + displaced_size(base, -1);
     case GFX_TFDM_READ_PYRAMID:
     case GFX_TFDM_READ_HEIGHTS: {
         if (level > static_cast<uint32_t>(o.params.maxDepth)) throw HipError(std::string(o.name) + "_read: no such level");

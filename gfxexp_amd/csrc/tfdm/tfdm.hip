@@ -36,6 +36,7 @@ namespace {
 constexpr int kTraceBlock = GFX_TFDM_TRACE_BLOCK;
 
 #include "tfdm_pyramid.hip.h"       // k_tfdm_minmax_first, k_tfdm_minmax_level
+#include "tfdm_update.hip.h"        // k_tfdm_update_*, k_tfdm_refit_*, update_heights
 
 __global__ void __launch_bounds__(64) k_tfdm_prim_aabbs(const TriRecord* __restrict__ records, const F2* __restrict__ pyramid, Params p, uint32_t numTriangles,
                                                         Box* __restrict__ aabbs) {
@@ -110,6 +111,8 @@ void build_geometry(TfdmObject& o, hipStream_t stream, const gfx_tfdm_params& g)
         k_tfdm_prim_aabbs<<<(o.numTriangles + 63u) / 64u, 64, 0, stream>>>(records.as<TriRecord>(), o.pyramid.as<F2>(), p, o.numTriangles, aabbs.as<Box>());
     });
     ++o.generation;
+    o.levelTableValid = false;
+    o.lastChange = nullptr;
 }
 
 } // namespace
@@ -129,6 +132,7 @@ void tfdm_init(TfdmObject& o, hipStream_t stream, const void* vertices, uint32_t
     check_params(g, size);
     fill_mirror(o, vertices, stride, numVertices, triangles, numTriangles);
     o.size = size;
+    o.ownMips = numLevels > 1u;
     upload_height_map(o, stream, make_levels(heightLevels, numLevels, size));
     build_geometry(o, stream, g);
 }
@@ -136,6 +140,18 @@ void tfdm_init(TfdmObject& o, hipStream_t stream, const void* vertices, uint32_t
 void tfdm_set_params(TfdmObject& o, hipStream_t stream, const gfx_tfdm_params& g) {
     check_params(g, o.size);
     build_geometry(o, stream, g);
+}
+
+// The map changed in place: heights and pyramid over the dirty regions, every box again, the tree refitted (tfdm_update.hip.h).
+// prim_aabb leaves a box empty by the record alone (no roots, or a footprint no texel centre test lets in) unless the map holds
+// NaNs, so the tree's shape stays a fresh build's; where update_heights finds that it did not, the tree is made again.
+void tfdm_update_heights(Context& ctx, TfdmObject& o, hipStream_t stream, const float* dSrc, uint32_t srcPitch, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
+    const bool refitted = update_heights(ctx, o, stream, dSrc, srcPitch, x0, y0, w, h, false, true, [&]() {
+        k_tfdm_prim_aabbs<<<(o.numTriangles + 63u) / 64u, 64, 0, stream>>>(o.records.as<TriRecord>(), o.pyramid.as<F2>(), o.params, o.numTriangles, o.aabbs.as<Box>());
+    }, o.root);
+    if (refitted) ++o.generation;
+    else build_geometry(o, stream, o.pub);
+    o.lastChange = "gfx_tfdm_update_heights";
 }
 
 void tfdm_trace(TfdmObject& o, hipStream_t stream, int mode, const void* dRayOrgTmin, const void* dRayDirTmax, uint32_t numRays, void* dOut, void* dCounters) {

@@ -607,9 +607,18 @@ struct TraceStats { uint32_t aabbTests, leafTests, primTests; };
 
 GFX_TFDM_FN Box node_box(const Node& n) { Box b; b.lo = v3(n.lo[0], n.lo[1], n.lo[2]); b.hi = v3(n.hi[0], n.hi[1], n.hi[2]); return b; }
 
-// One ray, closest hit (kAny: any hit).  `Stack` has push(uint32 node, float entry), pop(uint32&, float&), empty(): the device
-// keeps it in an LDS column per lane, the host in an array.  A triangle is tested when the ray enters its box no later than the
-// current hit distance; equal distances go to the lower primitive index, so the result does not depend on the order of the walk.
+// One ray, closest hit (kAny: any hit).  `Stack` has push(uint32 node, float key), pop(uint32&, float&), empty(): the device
+// keeps it in an LDS column per lane, the host in an array.  Equal distances go to the lower primitive index.
+//
+// Every node has a key: where the ray enters its box, less a slack that is one number per ray (2^-17 of the magnitudes of the
+// root box's entry and exit: the roundings of the slab test and of intersect()'s distance are some 2^-20 of them).  A node is
+// walked while its key is no larger than the current hit distance, and a triangle's hit counts only from its leaf's key on.
+// intersect() works in the base triangle's tangent frame and can report a point well in front of the box prim_aabb puts around
+// P + h N / |N| (small triangles with strongly differing vertex normals).  Such a hit used to win or to be lost by whether its leaf
+// was reached before a nearer leaf's hit had put the leaf's box behind the current distance.  With the rule, a hit that counts lies
+// at or behind its leaf's key, an inner box is the union of its children's (its key is no larger than theirs: the same slack, and
+// rounding is monotone), and the current distance only shrinks: a node that is skipped holds no hit that could have won.  So the
+// result depends neither on the order of the walk nor on the tree's shape.
 template <bool kAny, bool kWithBilinear, class Stack>
 GFX_TFDM_FN bool trace_ray_local(const Node* nodes, const TriRecord* records, const Map& map, const Params& p, V3 org, V3 dir, float tmin, float tmax,
                            Stack& stack, TraceHit& best, TraceStats& ts) {
@@ -618,7 +627,10 @@ GFX_TFDM_FN bool trace_ray_local(const Node* nodes, const TriRecord* records, co
     float t0, t1;
     V3 nearT, farT;
     if (!box_hit(node_box(nodes[0]), org, inv, tmin, tmax, t0, t1, nearT, farT)) return false;
+    float slack = (fabsf(t0) + fabsf(t1)) * pow2i(-17);
+    if (!(slack >= 0.0f)) slack = inf();         // a NaN: nothing is skipped and every hit counts
     uint32_t cur = 0u;
+    float curKey = t0 - slack;
     while (true) {
         const Node n = nodes[cur];
         bool popNext = true;
@@ -632,29 +644,33 @@ GFX_TFDM_FN bool trace_ray_local(const Node* nodes, const TriRecord* records, co
             ++ts.primTests;
             const bool got = intersect<kWithBilinear>(records[prim], map, p, org, dir, tmin, bound, h, s);
             ts.aabbTests += s.aabbTests; ts.leafTests += s.leafTests;
-            if (got) {
+            if (got && h.t >= curKey) {
                 best.t = h.t; best.bcB = h.bcB; best.bcC = h.bcC; best.prim = prim; best.normal = h.normal; best.frontFace = h.frontFace;
                 if (kAny) return true;
             }
         }
         else {
             float a0, a1, b0, b1;
-            const bool hitA = box_hit(node_box(nodes[n.first]), org, inv, tmin, best.t, a0, a1, nearT, farT);
-            const bool hitB = box_hit(node_box(nodes[n.first + 1u]), org, inv, tmin, best.t, b0, b1, nearT, farT);
+            // (the far clip is the ray's own: what the current distance skips is decided by the key)
+            bool hitA = box_hit(node_box(nodes[n.first]), org, inv, tmin, tmax, a0, a1, nearT, farT);
+            bool hitB = box_hit(node_box(nodes[n.first + 1u]), org, inv, tmin, tmax, b0, b1, nearT, farT);
+            const float keyA = a0 - slack, keyB = b0 - slack;
+            hitA = hitA && keyA <= best.t;
+            hitB = hitB && keyB <= best.t;
             if (hitA && hitB) {
                 const bool aFirst = a0 <= b0;
-                stack.push(aFirst ? n.first + 1u : n.first, aFirst ? b0 : a0);
+                stack.push(aFirst ? n.first + 1u : n.first, aFirst ? keyB : keyA);
                 cur = aFirst ? n.first : n.first + 1u;
+                curKey = aFirst ? keyA : keyB;
                 popNext = false;
             }
-            else if (hitA || hitB) { cur = hitA ? n.first : n.first + 1u; popNext = false; }
+            else if (hitA || hitB) { cur = hitA ? n.first : n.first + 1u; curKey = hitA ? keyA : keyB; popNext = false; }
         }
         if (popNext) {
             bool have = false;
             while (!stack.empty()) {
-                float entry;
-                stack.pop(cur, entry);
-                if (entry <= best.t) { have = true; break; }     // entered behind the current hit: skipped
+                stack.pop(cur, curKey);
+                if (curKey <= best.t) { have = true; break; }     // entered behind the current hit: skipped
             }
             if (!have) break;
         }

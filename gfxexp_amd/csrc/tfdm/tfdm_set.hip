@@ -339,6 +339,7 @@ const Node& root_of(const TfdmSet::Member& m) {
 // the call after which a member's object has buffers the committed record does not know
 const char* stale_call_of(const TfdmSet::Member& m) {
     if (is_shell(m)) return static_cast<const ShellObject*>(m.obj)->lastChange;
+    if (const char* call = static_cast<const HeightMapObject*>(m.obj)->lastChange) return call;
     return is_nrtdsm(m) ? "gfx_nrtdsm_set_params" : "gfx_tfdm_set_params";
 }
 bool has_nrtdsm(const TfdmSet& s) {

@@ -827,10 +827,28 @@ int gfx_tfdm_create(gfx_ctx* ctx, void* stream, const void* vertices, uint32_t s
  * pyramid is kept.  localIntersection may change between all three modes (records, boxes and the tree do not depend on it).  A
  * refused call leaves the object as it was. */
 int gfx_tfdm_set_params(gfx_ctx* ctx, void* stream, gfx_tfdm* obj, const gfx_tfdm_params* params);
+/* New heights for the level-0 rectangle (x0, y0) .. (x0 + w, y0 + h) of an object's map, in place.  dSrc is
+ * DEVICE memory on the object's device, 4-byte aligned: dSrc[j * srcPitch + i] is the new fp32 height of texel (x0 + i, y0 + j),
+ * 0 <= i < w, 0 <= j < h.  The rectangle lies inside the map and does not wrap.  Afterwards every level of HEIGHTS and PYRAMID, AABBS
+ * and RECORDS are, bit for bit, what gfx_tfdm_create with the whole new map and the same parameters makes; NODES keeps its shape
+ * (node count, every first / count) with a leaf's box its primitive's new box and an inner node's box the exact union of its two
+ * children's.  No micro-geometry exists to be rebuilt: only the texels above the rectangle, the per-triangle boxes and the boxes
+ * of the tree are computed again, all of it on the device.  Everything runs on `stream` and the call returns after the work is
+ * done (it ends with a read-back of the new root node); the order against traces of the same object on OTHER streams is the
+ * caller's business.  A member of an instance set whose object was updated is stale as after gfx_tfdm_set_params: commit the set
+ * again (the instance's world box comes from the new root).  A displaced pixel's motion vector stays the instance's curToPrev: a
+ * change of height carries no motion.  Refused with a message, before anything of the object is written, so that the object
+ * answers as before: a null or misaligned dSrc; w or h of 0; srcPitch < w; a rectangle that leaves the map; an object created
+ * with its own mip levels (numLevels > 1: its coarser levels are not means, a regenerated region would mix two definitions); a
+ * source value that is not finite. */
+int gfx_tfdm_update_heights(gfx_ctx* ctx, void* stream, gfx_tfdm* obj, const float* dSrc, uint32_t srcPitch,
+                            uint32_t x0, uint32_t y0, uint32_t w, uint32_t h);
 int gfx_tfdm_destroy(gfx_tfdm* obj);
 /* One ray per entry, optixTrace against the custom-primitive GAS of the reference (tfdm_intersection_kernels.h:16-35 for the
  * per-triangle boxes, :39-562 for the surface).  mode GFX_TRACE_CLOSEST: dOut = gfx_tfdm_hit[numRays]; GFX_TRACE_ANY: dOut =
- * uint32_t[numRays] (1 = occluded).  Closest-hit ties on the distance go to the lower primitive index.  dCounters (optional,
+ * uint32_t[numRays] (1 = occluded).  Closest-hit ties on the distance go to the lower primitive index, and a hit
+ * counts only from where the ray enters its base triangle's box (less a rounding slack) on, so the answer does not depend on the tree
+ * (DESIGN.md section 25).  dCounters (optional,
  * device u64[4], added to): texel AABB tests, leaf (local intersection) tests, rays, base triangles tested -- the reference's
  * TraversalStats (tfdm_shared.h) and one more.  dRayOrgTmin, dRayDirTmax and a closest-hit dOut must be 16-byte aligned (they
  * are read and written as float4), an any-hit dOut 4-byte, dCounters 8-byte; a misaligned pointer is refused. */
@@ -862,6 +880,10 @@ int gfx_nrtdsm_create(gfx_ctx* ctx, void* stream, const void* vertices, uint32_t
                       const float* const* heightLevels, uint32_t numLevels, uint32_t size,
                       const gfx_tfdm_params* params, gfx_nrtdsm** out);
 int gfx_nrtdsm_set_params(gfx_ctx* ctx, void* stream, gfx_nrtdsm* obj, const gfx_tfdm_params* params);
+/* As gfx_tfdm_update_heights, with the same stream behaviour (synchronous on `stream`; ordering against traces on other streams
+ * is the caller's), the same staleness of set members and no motion; also refuses a source value outside [0, 1], as create does. */
+int gfx_nrtdsm_update_heights(gfx_ctx* ctx, void* stream, gfx_nrtdsm* obj, const float* dSrc, uint32_t srcPitch,
+                              uint32_t x0, uint32_t y0, uint32_t w, uint32_t h);
 int gfx_nrtdsm_destroy(gfx_nrtdsm* obj);
 int gfx_nrtdsm_trace(gfx_ctx* ctx, void* stream, gfx_nrtdsm* obj, int mode, const void* dRayOrgTmin, const void* dRayDirTmax,
                      uint32_t numRays, void* dOut, void* dCounters);

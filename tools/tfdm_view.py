@@ -56,7 +56,15 @@ spatial passes, shading; the shadow rays are the scene's any-hit query), --frame
 
 --move N: N frames of the --restir scene with the wall translating by --step along x per frame (gfx_tfdm_set_move + commit before each
 frame after the first) and the ground fixed; temporal reuse is on and nothing is accumulated.  Writes the last frame as
-<out>_move.png and its motion vectors as <out>_motion.png (red / green = 0.5 + mv / 16 pixels: grey stands still)."""
+<out>_move.png and its motion vectors as <out>_motion.png (red / green = 0.5 + mv / 16 pixels: grey stands still).
+
+    python tools/tfdm_view.py --ripple N [--nrtdsm] [--scene [--render | --restir]] [--size 256] [--out tfdm_view]
+
+--ripple N: N frames of a travelling ripple written into the middle quarter of the height map by a torch expression on the device;
+each frame is one gfx_tfdm_update_heights (gfx_nrtdsm_update_heights) of that sub-rectangle, with --scene one gfx_tfdm_set_commit,
+and the frame's trace or render.  No micro-geometry is rebuilt: the pyramid above the rectangle, the per-triangle boxes and a refit
+of the tree.  With --scene the map of the wall's object moves (without --nrtdsm the ground shares that object).  The images are those
+of the last frame; with --restir nothing is accumulated (with --render the frames accumulate, so the ripple blurs)."""
 import argparse
 import json
 import ctypes as C
@@ -74,6 +82,24 @@ import tfdm_common as K  # noqa: E402
 
 def _local(a):
     return api.TFDM_BOX if a.box else api.TFDM_BILINEAR if a.bilinear else api.TFDM_TWO_TRIANGLE
+
+
+class Ripple:
+    """The middle quarter of a map, rippling: frame k is the map's own values plus a damped ring wave of phase k, clipped to [0, 1]."""
+
+    def __init__(self, heights):
+        size = heights.shape[0]
+        self.rect = (size // 4, size // 4, max(size // 2, 1), max(size // 2, 1))
+        x0, y0, w, h = self.rect
+        self.base = torch.from_numpy(np.ascontiguousarray(heights[y0:y0 + h, x0:x0 + w], np.float32)).cuda()
+        yy, xx = torch.meshgrid(torch.arange(h, device="cuda", dtype=torch.float32), torch.arange(w, device="cuda", dtype=torch.float32), indexing="ij")
+        self.r = torch.sqrt((xx - 0.5 * w) ** 2 + (yy - 0.5 * h) ** 2)
+        self.damp = torch.exp(-self.r / (0.35 * w))
+
+    def apply(self, obj, k, stream):
+        x0, y0, w, h = self.rect
+        src = torch.clamp(self.base + 0.15 * torch.sin(0.35 * self.r - 0.6 * k) * self.damp, 0.0, 1.0).contiguous()
+        obj.update_heights(src.data_ptr(), x0, y0, w, h, stream=stream)      # returns when the update is done: `src` may go
 
 
 def _depth_image(dist, hit, n):
@@ -117,14 +143,18 @@ def scene_render(a):
     stream = torch.cuda.current_stream().cuda_stream
     if a.move:
         return scene_move(a, ctx, tset, instances, frames, cam, stream)
-    for k in range(a.frames):
-        frames.frame(k, cam, stream=stream)
+    ripple = Ripple(heights) if a.ripple else None
+    for k in range(a.ripple or a.frames):
+        if ripple:
+            ripple.apply(wall if wall is not None else tf, k, stream)
+            tset.commit(stream)
+        frames.frame(k, cam, stream=stream, **({"accumulate": False} if ripple and a.restir else {}))
     beauty = frames.beauty()
     ctx.bind_displaced_kinds(None)
     image = a.out + ("_restir.png" if a.restir else "_render.png")
     api.save_image_sdr(image, beauty, w, h, api.sdr_config(brightness=1.0, tone_map=True, gamma=True))
-    g0 = frames.t["gb0_%d" % ((a.frames - 1) % 2)].cpu().numpy().view(np.uint32).reshape(-1, 4)[:, 0]
-    print(json.dumps({"scene": "teapot on displaced ground, displaced wall, emissive rectangle", "size": int(heights.shape[0]), "frames": a.frames,
+    g0 = frames.t["gb0_%d" % (((a.ripple or a.frames) - 1) % 2)].cpu().numpy().view(np.uint32).reshape(-1, 4)[:, 0]
+    print(json.dumps({"scene": "teapot on displaced ground, displaced wall, emissive rectangle", "size": int(heights.shape[0]), "frames": a.ripple or a.frames, "ripple": bool(a.ripple),
                       "displaced_pixel_share": round(float(((g0 != api.GFX_INVALID_SLOT) & (g0 >= api.GBUFFER_DISPLACED)).mean()), 4),
                       "renderer": "restir_di" if a.restir else "path_tracer", "wall": "nrtdsm" if a.nrtdsm else "shell" if a.shell else "tfdm", "mean_radiance": round(float(beauty[:, :3].mean()), 5), "images": [image]}))
     return 0
@@ -184,8 +214,15 @@ def scene_view(a):
     d_out = torch.zeros(n * 8, dtype=torch.int32, device="cuda")
     d_cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
     d_part = torch.zeros(n * 4, dtype=torch.int32, device="cuda") if a.shell else None
-    api.trace_scene(ctx, accel, tset, api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), d_cnt.data_ptr(), stream=torch.cuda.current_stream().cuda_stream,
-                    d_shell_part=d_part.data_ptr() if a.shell else 0)
+    stream = torch.cuda.current_stream().cuda_stream
+    ripple = Ripple(heights) if a.ripple else None
+    for k in range(max(a.ripple, 1)):
+        if ripple:
+            ripple.apply(wall if wall is not None else tf, k, stream)
+            tset.commit(stream)
+            d_cnt.zero_()
+        api.trace_scene(ctx, accel, tset, api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), n, d_out.data_ptr(), d_cnt.data_ptr(), stream=stream,
+                        d_shell_part=d_part.data_ptr() if a.shell else 0)
     torch.cuda.synchronize()
     hits = d_out.cpu().numpy().view(api.SCENE_HIT_DTYPE)
     cnt = d_cnt.cpu().numpy()
@@ -286,11 +323,14 @@ def main():
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--move", type=int, default=0)
     ap.add_argument("--step", type=float, default=0.02)
+    ap.add_argument("--ripple", type=int, default=0)
     a = ap.parse_args()
     if a.mesh is None:
         a.mesh = "teapot" if a.nrtdsm and not a.scene else "quad"
     if a.move and not (a.scene and a.restir):
         ap.error("--move goes with --scene --restir")
+    if a.ripple and (a.shell or a.move or a.height):
+        ap.error("--ripple writes into the procedural height map of a TFDM or an NRTDSM object; it goes with neither --shell, --move nor --height")
     if a.render or a.restir:
         if a.shell and a.nrtdsm:
             ap.error("--scene takes the wall as --nrtdsm or as --shell, not both")
@@ -319,7 +359,13 @@ def main():
     d_org, d_dir = torch.from_numpy(org).cuda(), torch.from_numpy(dirs).cuda()
     d_out = torch.zeros(w * h * 8, dtype=torch.int32, device="cuda")
     d_cnt = torch.zeros(4, dtype=torch.int64, device="cuda")
-    tf.trace(api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), w * h, d_out.data_ptr(), d_cnt.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    stream = torch.cuda.current_stream().cuda_stream
+    ripple = Ripple(heights) if a.ripple else None
+    for k in range(max(a.ripple, 1)):
+        if ripple:
+            ripple.apply(tf, k, stream)
+            d_cnt.zero_()
+        tf.trace(api.TRACE_CLOSEST, d_org.data_ptr(), d_dir.data_ptr(), w * h, d_out.data_ptr(), d_cnt.data_ptr(), stream=stream)
     torch.cuda.synchronize()
     hits = d_out.cpu().numpy().view(api.TFDM_HIT_DTYPE)
     cnt = d_cnt.cpu().numpy()
