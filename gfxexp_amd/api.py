@@ -342,7 +342,7 @@ C_ABI_SYMBOLS = [
     "gfx_tfdm_set_create", "gfx_tfdm_set_add", "gfx_tfdm_set_transform", "gfx_tfdm_set_commit", "gfx_tfdm_set_read", "gfx_tfdm_set_destroy", "gfx_trace_scene",
     "gfx_scene_bind_displaced", "gfx_restir_primary_rays", "gfx_scene_bind_displaced_passes", "gfx_restir_last_rays",
     "gfx_tfdm_set_move", "gfx_tfdm_set_read_motion", "gfx_tfdm_set_add_nrtdsm", "gfx_tfdm_set_add_shell", "gfx_trace_scene_ex",
-    "gfx_scene_bind_displaced_kinds",
+    "gfx_scene_bind_displaced_kinds", "gfx_pt_last_nee_rays", "gfx_tfdm_set_bounds",
     "gfx_nrtdsm_create", "gfx_nrtdsm_set_params", "gfx_nrtdsm_destroy", "gfx_nrtdsm_trace", "gfx_nrtdsm_read", "gfx_nrtdsm_size",
     "gfx_shell_create", "gfx_shell_set_params", "gfx_shell_set_geometry", "gfx_shell_destroy", "gfx_shell_trace", "gfx_shell_read", "gfx_shell_size",
     "gfx_tfdm_update_heights", "gfx_nrtdsm_update_heights",
@@ -946,33 +946,35 @@ class Context:
         reads rngBuffer when jittering is on and leaves it as it is."""
         self._check(self.L.gfx_restir_primary_rays(self.h, C.c_void_p(stream), C.c_uint32(width), C.c_uint32(height), C.c_void_p(d_ray_org), C.c_void_p(d_ray_dir)))
 
-    def bind_displaced(self, tfdm_set, geom_slots=(), restir=False, pass_mask=None):
+    def bind_displaced(self, tfdm_set, geom_slots=(), restir=False, pass_mask=None, regir=False):
         """gfx_scene_bind_displaced: the G-buffer pass and the baseline path tracer render the displaced instances of `tfdm_set`
         (None: unbind); geom_slots[k] is the ungrouped geometry instance k is shaded with.  restir=True binds through
         gfx_scene_bind_displaced_passes with DISPLACED_RESTIR, so the ReSTIR passes run over the set too (their shadow rays become the
-        scene query); every pass the binding does not carry is refused while a set is bound.  pass_mask: the mask as given."""
+        scene query); regir=True adds DISPLACED_REGIR, so the ReGIR passes of pt_launch run over it (size the grid from the scene's
+        bounds joined with tfdm_set.bounds()); every pass the binding does not carry is refused while a set is bound.  pass_mask: the
+        mask as given."""
         if tfdm_set is None:
             self._check(self.L.gfx_scene_bind_displaced(self.h, None, None, C.c_uint32(0)))
             self._displaced = None
             return
         slots = np.ascontiguousarray(geom_slots, np.uint32).reshape(-1)
-        if restir or pass_mask is not None:
-            mask = pass_mask if pass_mask is not None else DISPLACED_GBUFFER_PT | DISPLACED_RESTIR
+        if restir or regir or pass_mask is not None:
+            mask = pass_mask if pass_mask is not None else DISPLACED_GBUFFER_PT | (DISPLACED_RESTIR if restir else 0) | (DISPLACED_REGIR if regir else 0)
             self._check(self.L.gfx_scene_bind_displaced_passes(self.h, tfdm_set.h, _p(slots), C.c_uint32(len(slots)), C.c_uint32(mask)))
         else:
             self._check(self.L.gfx_scene_bind_displaced(self.h, tfdm_set.h, _p(slots), C.c_uint32(len(slots))))
         self._displaced = tfdm_set          # the binding does not own the set: keep it alive
 
-    def bind_displaced_kinds(self, tfdm_set, members=(), restir=False, pass_mask=None):
+    def bind_displaced_kinds(self, tfdm_set, members=(), restir=False, pass_mask=None, regir=False):
         """gfx_scene_bind_displaced_kinds: bind_displaced for a set with members of any kind (None: unbind).  members[k] describes member
         k: a geometry slot (a TFDM or an NRTDSM member), or (geometry slot, [material slot of shell geometry 0, 1, ...]) for a shell
-        member, or a DISPLACED_MEMBER_DTYPE array of all of them.  restir / pass_mask as bind_displaced."""
+        member, or a DISPLACED_MEMBER_DTYPE array of all of them.  restir / regir / pass_mask as bind_displaced."""
         if tfdm_set is None:
             self._check(self.L.gfx_scene_bind_displaced_kinds(self.h, None, None, C.c_uint32(0), C.c_uint32(0)))
             self._displaced = None
             return
         m = displaced_members(members)
-        mask = pass_mask if pass_mask is not None else DISPLACED_GBUFFER_PT | (DISPLACED_RESTIR if restir else 0)
+        mask = pass_mask if pass_mask is not None else DISPLACED_GBUFFER_PT | (DISPLACED_RESTIR if restir else 0) | (DISPLACED_REGIR if regir else 0)
         self._check(self.L.gfx_scene_bind_displaced_kinds(self.h, tfdm_set.h, _p(m), C.c_uint32(len(m)), C.c_uint32(mask)))
         self._displaced = tfdm_set
 
@@ -983,6 +985,15 @@ class Context:
         n = C.c_uint32(0)
         self._check(self.L.gfx_restir_last_rays(self.h, C.c_void_p(stream), C.c_void_p(d_ray_org), C.c_void_p(d_ray_dir), C.c_void_p(d_occluded),
                                                 C.c_uint32(capacity), C.byref(n)))
+        return n.value
+
+    def pt_last_nee_rays(self, d_ray_org, d_ray_dir, d_occluded, d_owner_pixel, capacity, stream=0):
+        """gfx_pt_last_nee_rays: the compacted NEE queue (float4 pairs, gfx_trace's layout), the occlusion words (uint32) and the owning
+        pixel of each entry (uint32; d_owner_pixel may be 0) of the most recent any-hit pass pt_launch traced in its wavefront form,
+        copied into device buffers of `capacity` entries; returns the number of entries."""
+        n = C.c_uint32(0)
+        self._check(self.L.gfx_pt_last_nee_rays(self.h, C.c_void_p(stream), C.c_void_p(d_ray_org), C.c_void_p(d_ray_dir), C.c_void_p(d_occluded),
+                                                C.c_void_p(d_owner_pixel), C.c_uint32(capacity), C.byref(n)))
         return n.value
 
     def nrc_inference_image(self, net, which):
@@ -1449,6 +1460,7 @@ class Nrtdsm(_HeightMapObject):
 
 SCENE_PLAIN = 0x80000000
 DISPLACED_GBUFFER_PT, DISPLACED_RESTIR = 1, 2      # GFX_DISPLACED_*: the pass mask of gfx_scene_bind_displaced_passes
+DISPLACED_REGIR = 8                                # (4 is not assigned and is refused as an unknown bit)
 GBUFFER_DISPLACED = 0x80000000       # GFX_GBUFFER_DISPLACED: gbuffer0.instSlot of a displaced pixel = GBUFFER_DISPLACED | set index
 SCENE_HIT_DTYPE = np.dtype([("dist", "<f4"), ("bcB", "<f4"), ("bcC", "<f4"), ("index", "<u4"), ("normal", "<f4", 3), ("where", "<u4")])
 TFDM_INSTANCE_DTYPE = np.dtype([("objToWorld", "<f4", 12), ("worldToObj", "<f4", 12), ("boxLo", "<f4", 3), ("userId", "<u4"), ("boxHi", "<f4", 3), ("pad0", "<u4"),
@@ -1549,6 +1561,12 @@ class TfdmSet:
         out = np.zeros(len(self.objects), TFDM_INSTANCE_DTYPE)
         self.ctx._check(self.L.gfx_tfdm_set_read(self.ctx.h, self.h, _p(out), C.c_size_t(out.nbytes)))
         return out
+
+    def bounds(self):
+        """gfx_tfdm_set_bounds: (lo, hi), float32[3] each, the union of the committed records' world boxes; lo > hi for an empty set."""
+        lo, hi = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        self.ctx._check(self.L.gfx_tfdm_set_bounds(self.h, _p(lo), _p(hi)))
+        return lo, hi
 
     def read_motion(self):
         """The committed motion table (TFDM_MOTION_DTYPE): curToPrev per instance, the exact identity where it did not move."""

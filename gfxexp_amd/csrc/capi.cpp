@@ -963,6 +963,12 @@ int gfx_tfdm_set_read_motion(gfx_ctx* ctx, gfx_tfdm_set* set, void* hostOut, siz
     tfdm_set_read_motion(set->s, hostOut, bytes);
     GFX_CATCH(ctx)
 }
+int gfx_tfdm_set_bounds(gfx_tfdm_set* set, float lo[3], float hi[3]) {
+    if (!set) return 1;
+    GFX_TRY(set->ctx)
+    tfdm_set_bounds(set->s, lo, hi);
+    GFX_CATCH(set->ctx)
+}
 int gfx_tfdm_set_destroy(gfx_tfdm_set* set) {
     if (!set) return 1;
     int prev = -1;
@@ -1006,6 +1012,12 @@ int gfx_scene_bind_displaced_kinds(gfx_ctx* ctx, gfx_tfdm_set* set, const gfx_di
 int gfx_restir_last_rays(gfx_ctx* ctx, void* stream, void* dRayOrgTmin, void* dRayDirTmax, void* dOccluded, uint32_t capacity, uint32_t* count) {
     GFX_TRY(ctx)
     restir_last_rays(ctx->c, static_cast<hipStream_t>(stream), dRayOrgTmin, dRayDirTmax, dOccluded, capacity, count);
+    GFX_CATCH(ctx)
+}
+int gfx_pt_last_nee_rays(gfx_ctx* ctx, void* stream, void* dRayOrgTmin, void* dRayDirTmax, void* dOccluded, void* dOwnerPixel, uint32_t capacity,
+                         uint32_t* count) {
+    GFX_TRY(ctx)
+    pt_last_nee_rays(ctx->c, static_cast<hipStream_t>(stream), dRayOrgTmin, dRayDirTmax, dOccluded, dOwnerPixel, capacity, count);
     GFX_CATCH(ctx)
 }
 int gfx_restir_primary_rays(gfx_ctx* ctx, void* stream, uint32_t width, uint32_t height, void* dRayOrgTmin, void* dRayDirTmax) {

@@ -202,6 +202,9 @@ struct Context {
     DisplacedBinding displaced;
     // the queue of the last ReSTIR ray pass (gfx_restir_last_rays): state 0 none yet, 1 three-kernel form, 2 fused (no queue)
     struct LastRays { int state = 0; const void* org = nullptr; const void* dir = nullptr; const void* out = nullptr; uint32_t fixedCount = 0; const uint32_t* countPtr = nullptr; } lastRays;
+    // the NEE queue of the last any-hit pass a path tracer's wavefront form traced (gfx_pt_last_nee_rays): state as above; countPtr is
+    // the one of the two alternating queue heads that pass read (the extension trace behind it zeroes the other)
+    struct LastNee { int state = 0; const void* org = nullptr; const void* dir = nullptr; const void* out = nullptr; const void* pending = nullptr; const uint32_t* countPtr = nullptr; } lastNee;
     DevBuf nrcState, neeTrainIdx;
     DevBuf nrcQueryCount;            // u32: inference batch size of the NRC frame (GFX_PT_NRC_COUNT_QUERIES)
     // build scratch

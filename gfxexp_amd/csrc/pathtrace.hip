@@ -619,7 +619,9 @@ GFX_DEV void pt_first_setup_displaced(const PtArgs& a, const DisplacedArgs& d, s
     su.bsdf.setup(a.scene, mat, tu, tv);
     su.shade = true;
 }
-template <bool SHELL>
+// REGIR (a binding that carries GFX_DISPLACED_REGIR): the vertex's NEE comes from its grid cell, on a plain and on
+// a displaced pixel alike (the cell of the offset shading position); every lane reaches shade_vertex, as the cell-access count wants.
+template <bool SHELL, bool REGIR>
 GFX_DEV void pt_first_scene(const PtArgs& a, const DisplacedArgs& d) {
     const PixelId px = pixel_of_thread(a.px);
     const size_t p = px.p;
@@ -629,10 +631,10 @@ GFX_DEV void pt_first_scene(const PtArgs& a, const DisplacedArgs& d) {
     if (px.valid) g0 = static_cast<const uint4*>(a.s.gbuffer0[a.f.bufferIndex])[p];
     bool surface;
     if (g0.x != 0xFFFFFFFFu && (g0.x & GFX_GBUFFER_DISPLACED)) { pt_first_setup_displaced<SHELL>(a, d, p, g0, path, su); surface = true; }
-    else surface = pt_first_setup<false>(a, px, path, su);
+    else surface = pt_first_setup<REGIR>(a, px, path, su);
     const EnvMap env = load_env(a.s);
     const bool envEnabled = env.present() && a.f.enableEnvLight;
-    shade_vertex<false>(a, su.shade, env, envEnabled, path.pos, su.vOutLocal, su.frame, su.bsdf, path.rng, path.alpha, path.contribution, path.dirPDensity, path.o);
+    shade_vertex<REGIR>(a, su.shade, env, envEnabled, path.pos, su.vOutLocal, su.frame, su.bsdf, path.rng, path.alpha, path.contribution, path.dirPDensity, path.o);
     if (surface) static_cast<uint64_t*>(a.s.rngBuffer)[p] = path.rng.state;
     if (px.valid) {
         a.state[2 * p] = make_float4(path.alpha.x, path.alpha.y, path.alpha.z, path.dirPDensity);
@@ -640,8 +642,10 @@ GFX_DEV void pt_first_scene(const PtArgs& a, const DisplacedArgs& d) {
     }
     push_vertex(a, static_cast<uint32_t>(p), path.pos, path.o);
 }
-__global__ __launch_bounds__(kPtBlock) void k_pt_first_scene(PtArgs a, DisplacedArgs d) { pt_first_scene<false>(a, d); }
-__global__ __launch_bounds__(kPtBlock) void k_pt_first_scene_shell(PtArgs a, DisplacedArgs d) { pt_first_scene<true>(a, d); }
+__global__ __launch_bounds__(kPtBlock) void k_pt_first_scene(PtArgs a, DisplacedArgs d) { pt_first_scene<false, false>(a, d); }
+__global__ __launch_bounds__(kPtBlock) void k_pt_first_scene_shell(PtArgs a, DisplacedArgs d) { pt_first_scene<true, false>(a, d); }
+__global__ __launch_bounds__(kPtBlock) void k_pt_regir_first_scene(PtArgs a, DisplacedArgs d) { pt_first_scene<false, true>(a, d); }
+__global__ __launch_bounds__(kPtBlock) void k_pt_regir_first_scene_shell(PtArgs a, DisplacedArgs d) { pt_first_scene<true, true>(a, d); }
 // A later vertex on a displaced surface: everything from the hit (optix_pathtracing_kernels.cu:289-301).
 // materialSlot: the material the hit is shaded with, where it is not the bound geometry's (a shell member's, by shell geometry);
 // GFX_INVALID_SLOT: the bound geometry's.
@@ -669,7 +673,9 @@ GFX_DEV uint32_t pt_next_setup_displaced(const PtArgs& a, const DisplacedArgs& d
     }
     return kPtHitSurface;
 }
-template <bool SHELL>
+// REGIR: a plain hit as pt_next_setup<true> takes it (no environment term at a miss, hypothetical light density 0); a displaced hit adds
+// neither, so its branch is the baseline's; the Russian roulette of the ReGIR loop head is shade_vertex<true>'s.
+template <bool SHELL, bool REGIR>
 GFX_DEV void pt_bounce_scene(const PtArgs& a, const DisplacedArgs& d, const DisplacedShellArgs& e) {
     const uint32_t i = blockIdx.x * kPtBlock + threadIdx.x;
     const uint32_t count = *a.extCountIn;
@@ -706,10 +712,10 @@ GFX_DEV void pt_bounce_scene(const PtArgs& a, const DisplacedArgs& d, const Disp
         }
         else what = pt_next_setup_displaced(a, d, sh, rayOrg, rayDir, rngBuf, path, su);
     }
-    else what = pt_next_setup<false>(a, active, h, rayOrg, rayDir, rngBuf, path, su);
+    else what = pt_next_setup<REGIR>(a, active, h, rayOrg, rayDir, rngBuf, path, su);
     const EnvMap env = load_env(a.s);
     const bool envEnabled = env.present() && a.f.enableEnvLight;
-    shade_vertex<false>(a, su.shade, env, envEnabled, path.pos, su.vOutLocal, su.frame, su.bsdf, path.rng, path.alpha, path.contribution, path.dirPDensity, path.o);
+    shade_vertex<REGIR>(a, su.shade, env, envEnabled, path.pos, su.vOutLocal, su.frame, su.bsdf, path.rng, path.alpha, path.contribution, path.dirPDensity, path.o);
     if (what & kPtHitSurface) {
         static_cast<uint64_t*>(a.s.rngBuffer)[pixel] = path.rng.state;
         a.state[2ull * pixel] = make_float4(path.alpha.x, path.alpha.y, path.alpha.z, path.dirPDensity);
@@ -720,9 +726,15 @@ GFX_DEV void pt_bounce_scene(const PtArgs& a, const DisplacedArgs& d, const Disp
 __global__ __launch_bounds__(kPtBlock) void k_pt_bounce_scene(PtArgs a, DisplacedArgs d) {
     DisplacedShellArgs none;
     none.shellPart = nullptr; none.shellMats = nullptr;
-    pt_bounce_scene<false>(a, d, none);
+    pt_bounce_scene<false, false>(a, d, none);
 }
-__global__ __launch_bounds__(kPtBlock) void k_pt_bounce_scene_shell(PtArgs a, DisplacedArgs d, DisplacedShellArgs e) { pt_bounce_scene<true>(a, d, e); }
+__global__ __launch_bounds__(kPtBlock) void k_pt_bounce_scene_shell(PtArgs a, DisplacedArgs d, DisplacedShellArgs e) { pt_bounce_scene<true, false>(a, d, e); }
+__global__ __launch_bounds__(kPtBlock) void k_pt_regir_bounce_scene(PtArgs a, DisplacedArgs d) {
+    DisplacedShellArgs none;
+    none.shellPart = nullptr; none.shellMats = nullptr;
+    pt_bounce_scene<false, true>(a, d, none);
+}
+__global__ __launch_bounds__(kPtBlock) void k_pt_regir_bounce_scene_shell(PtArgs a, DisplacedArgs d, DisplacedShellArgs e) { pt_bounce_scene<true, true>(a, d, e); }
 
 // ---------------------------------------------------------------- ReGIR grid maintenance
 // sampleIntensity, regir/gpu_kernels/build_cell_reservoirs.cu:6-68 (the half-space tests compare lpCos,
@@ -1599,6 +1611,37 @@ __global__ __launch_bounds__(kPtBlock) void k_nrc_visualize(PtArgs a) {
     static_cast<float4*>(a.nrc.inferenceTerminalInfoBuffer)[p] = make_float4(1.0f, 1.0f, 1.0f, bits2f(nrc_terminal_bits(surface, 1, false, false)));
 }
 
+// ---------------------------------------------------------------- gfx_pt_last_nee_rays
+// the owner pixel of every NEE queue entry: the w word of its pending record
+__global__ __launch_bounds__(kPtBlock) void k_pt_nee_owners(const float4* __restrict__ pending, uint32_t n, uint32_t* __restrict__ owners) {
+    const uint32_t i = blockIdx.x * kPtBlock + threadIdx.x;
+    if (i < n) owners[i] = f2bits(pending[i].w);
+}
+void pt_last_nee_rays(Context& ctx, hipStream_t stream, void* dRayOrgTmin, void* dRayDirTmax, void* dOccluded, void* dOwnerPixel, uint32_t capacity, uint32_t* count) {
+    const Context::LastNee& last = ctx.lastNee;
+    if (!count) throw HipError("gfx_pt_last_nee_rays: null count");
+    if (last.state == 0) throw HipError("gfx_pt_last_nee_rays: no NEE pass has run yet");
+    if (last.state == 2) throw HipError("gfx_pt_last_nee_rays: the last path-tracing launch ran fused (one kernel, no ray queue); \"fuse_passes\" 1 keeps the wavefront form");
+    if ((reinterpret_cast<uintptr_t>(dRayOrgTmin) | reinterpret_cast<uintptr_t>(dRayDirTmax)) & 15u) throw HipError("gfx_pt_last_nee_rays: the ray outputs must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(dOccluded) | reinterpret_cast<uintptr_t>(dOwnerPixel)) & 3u) throw HipError("gfx_pt_last_nee_rays: the occlusion and owner outputs must be 4-byte aligned");
+    if (last.org != ctx.rayOrg.p || last.dir != ctx.rayDir.p || last.out != ctx.rayOut.p || last.pending != ctx.ptPending.p)
+        throw HipError("gfx_pt_last_nee_rays: the NEE queue was reallocated for a larger launch since the last NEE pass");
+    uint32_t n = 0;                              // the device count, once the launch is through (its streams are joined on `stream`)
+    GFX_HIP(hipMemcpyAsync(&n, last.countPtr, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GFX_HIP(hipStreamSynchronize(stream));
+    *count = n;
+    if (n > capacity) throw HipError("gfx_pt_last_nee_rays: the pass traced " + std::to_string(n) + " queue entries, capacity is " + std::to_string(capacity));
+    if (n == 0) return;
+    if (!dRayOrgTmin || !dRayDirTmax || !dOccluded) throw HipError("gfx_pt_last_nee_rays: null output");
+    GFX_HIP(hipMemcpyAsync(dRayOrgTmin, last.org, 16 * static_cast<size_t>(n), hipMemcpyDeviceToDevice, stream));
+    GFX_HIP(hipMemcpyAsync(dRayDirTmax, last.dir, 16 * static_cast<size_t>(n), hipMemcpyDeviceToDevice, stream));
+    GFX_HIP(hipMemcpyAsync(dOccluded, last.out, 4 * static_cast<size_t>(n), hipMemcpyDeviceToDevice, stream));
+    if (dOwnerPixel) {
+        hipLaunchKernelGGL(k_pt_nee_owners, dim3((n + kPtBlock - 1) / kPtBlock), dim3(kPtBlock), 0, stream, static_cast<const float4*>(last.pending), n, static_cast<uint32_t*>(dOwnerPixel));
+        GFX_HIP(hipGetLastError());
+    }
+}
+
 // ---------------------------------------------------------------- host sequencing
 void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, uint32_t height,
                       uint32_t maxPathLength, uint32_t rowBegin, uint32_t rowEnd) {
@@ -1612,9 +1655,16 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
     if (!rp.valid) throw HipError("gfx_pt_launch: gfx_restir_set_params has not been called");
     const bool displaced = ctx.displaced.set != nullptr;
     if (displaced) {
-        if (pass != GFX_PT_PATH_TRACE_BASELINE)
+        // a binding that carries GFX_DISPLACED_REGIR runs the four ReGIR passes; NRC stays refused under every binding
+        const bool regirBound = (ctx.displaced.passMask & GFX_DISPLACED_REGIR) != 0;
+        const bool regirOwn = pass >= GFX_PT_REGIR_BUILD_CELL_RESERVOIRS && pass <= GFX_PT_REGIR_UPDATE_LAST_ACCESS;
+        if (pass != GFX_PT_PATH_TRACE_BASELINE && !(regirBound && regirOwn)) {
+            if (regirBound)
+                throw HipError("gfx_pt_launch: a displaced instance set is bound (gfx_scene_bind_displaced_passes with GFX_DISPLACED_REGIR): the G-buffer pass, "
+                               "the baseline path tracer and the ReGIR passes render displaced instances; NRC pass " + std::to_string(pass) + " is refused");
             throw HipError("gfx_pt_launch: a displaced instance set is bound (gfx_scene_bind_displaced): only the G-buffer pass and the baseline path tracer "
                            "render displaced instances; ReGIR / NRC pass " + std::to_string(pass) + " is refused");
+        }
         displaced_check(ctx, "gfx_pt_launch");
     }
     const bool nrcRegir = pass == GFX_PT_PATH_TRACE_NRC_REGIR, nrcRestir = pass == GFX_PT_PATH_TRACE_NRC_RESTIR;
@@ -1782,6 +1832,7 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
         const size_t spillBytes = sizeof(uint2) * static_cast<size_t>(a.px.launchBlocks) * kPtBlock * spillCap;
         const bool small = launchWaves <= waveSlots + waveSlots / 2;
         if (!displaced && !nrc && !ctx.countersEnabled && spillBytes <= (size_t(1) << 30) && (ctx.tune.fusePasses == 2 || (ctx.tune.fusePasses == 0 && small))) {
+            ctx.lastNee.state = 2;
             ctx.spill.reserve(spillBytes);
             unsigned long long* ptDiag = nullptr;             // "pt_diag": wave iterations / lanes with a ray / traversal steps / waves / refills (gfx_pt_diag_read)
             if (ctx.tune.ptDiag) {
@@ -1816,8 +1867,10 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
     }
     void* const extHits = displaced ? ctx.displaced.ptHits.p : ctx.rayHits.p;
     if (displaced) {
-        ScopedKernelTimer timer(ctx, stream, shellRender ? "pt_first_scene_shell" : "pt_first_scene");
-        hipLaunchKernelGGL(shellRender ? k_pt_first_scene_shell : k_pt_first_scene, dim3(a.px.launchBlocks), dim3(kPtBlock), 0, stream, a, displaced_args(ctx, extHits));
+        void (*const first[2][2])(PtArgs, DisplacedArgs) = { { k_pt_first_scene, k_pt_first_scene_shell }, { k_pt_regir_first_scene, k_pt_regir_first_scene_shell } };
+        const char* const names[2][2] = { { "pt_first_scene", "pt_first_scene_shell" }, { "pt_regir_first_scene", "pt_regir_first_scene_shell" } };
+        ScopedKernelTimer timer(ctx, stream, names[regir][shellRender]);
+        hipLaunchKernelGGL(first[regir][shellRender], dim3(a.px.launchBlocks), dim3(kPtBlock), 0, stream, a, displaced_args(ctx, extHits));
         GFX_HIP(hipGetLastError());
     }
     else if (nrc) launch_pixels("nrc_pt_first", nrcRegir ? k_nrc_pt_first<1> : nrcRestir ? k_nrc_pt_first<2> : k_nrc_pt_first<0>);
@@ -1832,6 +1885,7 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
         if (overlap) { GFX_HIP(hipEventRecord(ctx.auxFork, stream)); GFX_HIP(hipStreamWaitEvent(neeStream, ctx.auxFork, 0)); }
         a.neeCount = neeCounts[nee];
         trace(neeStream, overlap, GFX_TRACE_ANY, a.neeOrg, a.neeDir, a.neeCount, ctx.rayOut.p);
+        ctx.lastNee = { 1, a.neeOrg, a.neeDir, ctx.rayOut.p, a.neePending, a.neeCount };
         launch(neeStream, "pt_apply_nee", k_pt_apply_nee);
         if (overlap) GFX_HIP(hipEventRecord(ctx.auxJoin, neeStream));
         if (regir && pathLength >= maxPathLength) { join(); break; }
@@ -1856,11 +1910,12 @@ void pathtrace_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width
         a.maxLengthTerminate = (pathLength >= maxPathLength && (!nrc || maxPathLength > 0)) ? 1u : 0u;
         a.nextMaxLengthTerminate = pathLength + 1 >= maxPathLength ? 1u : 0u;
         if (displaced) {
-            ScopedKernelTimer timer(ctx, stream, shellRender ? "pt_bounce_scene_shell" : "pt_bounce_scene");
+            const char* const names[2][2] = { { "pt_bounce_scene", "pt_bounce_scene_shell" }, { "pt_regir_bounce_scene", "pt_regir_bounce_scene_shell" } };
+            ScopedKernelTimer timer(ctx, stream, names[regir][shellRender]);
             if (shellRender)
-                hipLaunchKernelGGL(k_pt_bounce_scene_shell, dim3(grid), dim3(kPtBlock), 0, stream, a, displaced_args(ctx, extHits),
+                hipLaunchKernelGGL(regir ? k_pt_regir_bounce_scene_shell : k_pt_bounce_scene_shell, dim3(grid), dim3(kPtBlock), 0, stream, a, displaced_args(ctx, extHits),
                                    displaced_shell_args(ctx, ctx.displaced.ptShellPart.p));
-            else hipLaunchKernelGGL(k_pt_bounce_scene, dim3(grid), dim3(kPtBlock), 0, stream, a, displaced_args(ctx, extHits));
+            else hipLaunchKernelGGL(regir ? k_pt_regir_bounce_scene : k_pt_bounce_scene, dim3(grid), dim3(kPtBlock), 0, stream, a, displaced_args(ctx, extHits));
             GFX_HIP(hipGetLastError());
         }
         else if (nrc) launch(stream, "nrc_pt_bounce", nrcRegir ? k_nrc_pt_bounce<1> : nrcRestir ? k_nrc_pt_bounce<2> : k_nrc_pt_bounce<0>);

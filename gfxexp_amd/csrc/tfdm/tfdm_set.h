@@ -38,6 +38,7 @@ void tfdm_set_move(TfdmSet& s, uint32_t index, const float objToWorld[12]);     
 void tfdm_set_commit(TfdmSet& s, hipStream_t stream);
 void tfdm_set_read(TfdmSet& s, void* hostOut, size_t bytes);
 void tfdm_set_read_motion(TfdmSet& s, void* hostOut, size_t bytes);
+void tfdm_set_bounds(const TfdmSet& s, float lo[3], float hi[3]);   // union of the committed records' world boxes (host table)
 void tfdm_set_release(TfdmSet& s);
 // The scene query as the passes launch it (restir.hip, pathtrace.hip).  The ray count may be a device word (numRaysPtr; numRays is
 // then the queue capacity: k_scene_instances launches over it and the waves beyond the count leave at once), as TraceLaunch's is for
@@ -83,6 +84,8 @@ DisplacedShellArgs displaced_shell_args(const Context& ctx, const void* shellPar
 void restir_primary_rays(Context& ctx, hipStream_t stream, uint32_t width, uint32_t height, void* dRayOrgTmin, void* dRayDirTmax);   // restir.hip
 // gfx_restir_last_rays: the queue and the occlusion words of the last ray pass that ran in its three-kernel form (restir.hip)
 void restir_last_rays(Context& ctx, hipStream_t stream, void* dRayOrgTmin, void* dRayDirTmax, void* dOccluded, uint32_t capacity, uint32_t* count);
+// gfx_pt_last_nee_rays: the same for the last any-hit pass of a path tracer's wavefront form, with the owning pixels (pathtrace.hip)
+void pt_last_nee_rays(Context& ctx, hipStream_t stream, void* dRayOrgTmin, void* dRayDirTmax, void* dOccluded, void* dOwnerPixel, uint32_t capacity, uint32_t* count);
 
 // set == nullptr: no displaced instances; accel == nullptr: no plain geometry.  `fallbackPlain`: the plain-phase buffer of a
 // closest-hit query without a set (the context's).

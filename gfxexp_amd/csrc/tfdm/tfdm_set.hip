@@ -28,6 +28,7 @@
 // Register count, scratch and occupancy: DESIGN.md sections 15, 18, 22 and 23.
 #include <algorithm>
 #include <cstring>
+#include <limits>
 #include "tfdm_set.h"
 #include "tfdm_lds_stack.hip.h"
 #include "../nrtdsm/displaced_kinds.hip.h"
@@ -474,6 +475,14 @@ void tfdm_set_read(TfdmSet& s, void* hostOut, size_t bytes) {
     GFX_HIP(hipMemcpy(hostOut, s.table.p, need, hipMemcpyDeviceToHost));
 }
 
+void tfdm_set_bounds(const TfdmSet& s, float lo[3], float hi[3]) {
+    if (s.dirty) throw HipError("gfx_tfdm_set_bounds: the set has an add, a transform or a move that is not committed");
+    if (!lo || !hi) throw HipError("gfx_tfdm_set_bounds: null output");
+    for (int k = 0; k < 3; ++k) { lo[k] = std::numeric_limits<float>::infinity(); hi[k] = -std::numeric_limits<float>::infinity(); }
+    for (const InstanceRecord& r : s.host)
+        for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], r.boxLo[k]); hi[k] = std::max(hi[k], r.boxHi[k]); }
+}
+
 void tfdm_set_read_motion(TfdmSet& s, void* hostOut, size_t bytes) {
     if (s.dirty) throw HipError("gfx_tfdm_set_read_motion: the set has an add, a transform or a move that is not committed");
     const size_t need = sizeof(float) * s.hostMotion.size();
@@ -548,7 +557,7 @@ void trace_scene_launch(Context& ctx, hipStream_t stream, const SceneTrace& s) {
 
 void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint32_t n, uint32_t passMask) {
     DisplacedBinding& b = ctx.displaced;
-    if (passMask & ~(GFX_DISPLACED_GBUFFER_PT | GFX_DISPLACED_RESTIR))
+    if (passMask & ~(GFX_DISPLACED_GBUFFER_PT | GFX_DISPLACED_RESTIR | GFX_DISPLACED_REGIR))
         throw HipError("gfx_scene_bind_displaced_passes: unknown bit in the pass mask " + std::to_string(passMask));
     if (!set) { unbind(b); return; }
     if (set->device != ctx.device) throw HipError("gfx_scene_bind_displaced: the instance set belongs to another device");
@@ -575,7 +584,7 @@ void displaced_bind(Context& ctx, TfdmSet* set, const uint32_t* geomSlots, uint3
 void displaced_bind_kinds(Context& ctx, TfdmSet* set, const gfx_displaced_member* members, uint32_t n, uint32_t passMask) {
     DisplacedBinding& b = ctx.displaced;
     const std::string me = "gfx_scene_bind_displaced_kinds: ";
-    if (passMask & ~(GFX_DISPLACED_GBUFFER_PT | GFX_DISPLACED_RESTIR)) throw HipError(me + "unknown bit in the pass mask " + std::to_string(passMask));
+    if (passMask & ~(GFX_DISPLACED_GBUFFER_PT | GFX_DISPLACED_RESTIR | GFX_DISPLACED_REGIR)) throw HipError(me + "unknown bit in the pass mask " + std::to_string(passMask));
     if (!set) { unbind(b); return; }
     if (set->device != ctx.device) throw HipError(me + "the instance set belongs to another device");
     if (n != set->members.size())

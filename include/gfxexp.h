@@ -974,6 +974,10 @@ int gfx_tfdm_set_commit(gfx_ctx* ctx, void* stream, gfx_tfdm_set* set);
 int gfx_tfdm_set_read(gfx_ctx* ctx, gfx_tfdm_set* set, void* hostOut, size_t bytes);
 /* The committed motion table, 48 bytes per instance (`bytes` must be exactly that), for tests; refuses what gfx_tfdm_set_read refuses. */
 int gfx_tfdm_set_read_motion(gfx_ctx* ctx, gfx_tfdm_set* set, void* hostOut, size_t bytes);
+/* The union of the committed records' world boxes (boxLo / boxHi, padded as the scene query tests them), from the committed table on
+ * the host: what a ReGIR grid or a camera fit needs of members that are not in the BVH8.  An empty set gives the empty box lo = +inf,
+ * hi = -inf; a set with an uncommitted change is refused. */
+int gfx_tfdm_set_bounds(gfx_tfdm_set* set, float lo[3], float hi[3]);
 int gfx_tfdm_set_destroy(gfx_tfdm_set* set);
 
 /* closest-hit record of gfx_trace_scene, 32 B (what a renderer needs from a displaced hit: tfdm/tfdm_shared.h:570-577).
@@ -1009,8 +1013,13 @@ int gfx_trace_scene_ex(gfx_ctx* ctx, void* stream, uint64_t accel, gfx_tfdm_set*
  * GFX_PT_SETUP_GBUFFERS and GFX_PT_PATH_TRACE_BASELINE trace plain and displaced geometry together (the scene query above, in their
  * wavefront form whatever "fuse_passes" says).  A binding made with GFX_DISPLACED_RESTIR in its pass mask (gfx_scene_bind_displaced_passes)
  * also runs the ReSTIR passes and the rearchitected set over it: their shadow rays become the scene's any-hit query, and they too run in
- * their three-kernel form whatever "fuse_passes" says.  Every pass the binding does not carry (ReSTIR without that bit; ReGIR and NRC
- * with any binding) is refused with a message.  Without a binding every pass does what it always did.
+ * their three-kernel form whatever "fuse_passes" says.  A binding made with GFX_DISPLACED_REGIR runs the ReGIR passes of gfx_pt_launch
+ * (DESIGN.md section 26): the two cell-reservoir builds and GFX_PT_REGIR_UPDATE_LAST_ACCESS as they always ran (the grid never looks at
+ * geometry), GFX_PT_PATH_TRACE_REGIR in its wavefront form whatever "fuse_passes" says, its shadow and extension rays through the scene
+ * query.  The grid is the caller's (gfx_regir_set_params): the displaced members are not in the BVH8, so size it from the scene's bounds
+ * joined with gfx_tfdm_set_bounds (a vertex outside the grid clamps to a border cell).  The two bits may be set together.  Every pass
+ * the binding does not carry (ReSTIR and ReGIR without their bit; NRC, GFX_PT_PATH_TRACE_NRC_REGIR included, with any binding) is refused
+ * with a message.  Without a binding every pass does what it always did.
  *   geomInstSlots[k]  the geometry instance k of the set is shaded with: a gfx_geom_create of the vertex and triangle arrays the
  *                     instance's gfx_tfdm was created from, put in NO group (so it is not in the BVH8).  Material, texture
  *                     coordinates and texCoord0Dir come from it, transform and normal matrix from the instance's record.
@@ -1036,6 +1045,8 @@ int gfx_scene_bind_displaced(gfx_ctx* ctx, gfx_tfdm_set* set, const uint32_t* ge
  * binding carries.  Checks and refusals are those above; an unknown bit in passMask is refused.  Displaced emitters stay refused. */
 #define GFX_DISPLACED_GBUFFER_PT 1u   /* the G-buffer passes and the baseline path tracer */
 #define GFX_DISPLACED_RESTIR 2u       /* ... and the ReSTIR passes, the rearchitected set included */
+/* (bit 4 is not assigned: a mask that carries it is refused as an unknown bit, which callers may rely on) */
+#define GFX_DISPLACED_REGIR 8u        /* ... and the ReGIR passes: both cell builds, GFX_PT_PATH_TRACE_REGIR, the last-access update */
 int gfx_scene_bind_displaced_passes(gfx_ctx* ctx, gfx_tfdm_set* set, const uint32_t* geomInstSlots, uint32_t n, uint32_t passMask);
 /* The binding for a set with members of any kind: the two calls above refuse a set that has an NRTDSM or a
  * shell member, this one renders it.  members[k] describes member k of the set; passMask as above; set == NULL unbinds.  An NRTDSM
@@ -1063,6 +1074,15 @@ int gfx_restir_primary_rays(gfx_ctx* ctx, void* stream, uint32_t width, uint32_t
  * a message: no ray pass yet, the last one ran fused (no queue exists), capacity < *count (which is still set), rays not 16-byte or
  * words not 4-byte aligned.  `stream` is a hipStream_t passed as void*, as everywhere in this header. */
 int gfx_restir_last_rays(gfx_ctx* ctx, void* stream, void* dRayOrgTmin, void* dRayDirTmax, void* dOccluded, uint32_t capacity, uint32_t* count);
+/* The same for gfx_pt_launch: the compacted NEE (shadow ray) queue of the most recent any-hit pass a path tracer traced in its
+ * wavefront form (the last one of that launch: the baseline's terminal vertex emits none, ReGIR ends on one), its occlusion words and,
+ * if dOwnerPixel is not NULL, the pixel that owns each entry (uint32, row-major index); *count = the device count of that pass (this
+ * waits for `stream`).  With or without a binding; under one the words are the scene query's.  The buffers are the context's ray
+ * scratch: call before the next launch that traces rays.  Refused with a message: no such pass yet, the last path-tracing launch ran
+ * fused (one kernel, no queue), the queue reallocated for a larger launch since, capacity < *count (which is still set), rays not
+ * 16-byte or words / owners not 4-byte aligned. */
+int gfx_pt_last_nee_rays(gfx_ctx* ctx, void* stream, void* dRayOrgTmin, void* dRayDirTmax, void* dOccluded, void* dOwnerPixel, uint32_t capacity,
+                         uint32_t* count);
 
 #ifdef __cplusplus
 }

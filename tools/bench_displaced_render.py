@@ -1,6 +1,6 @@
 """Rendering displaced instances against rendering their tessellation, for an MI355X.
 
-    python tools/bench_displaced_render.py [--nrtdsm | --shell] [--size 1024] [--frames 20] [--width 1920] [--height 1080] [--max-len 5] [--step-timeout 300]
+    python tools/bench_displaced_render.py [--regir] [--nrtdsm | --shell] [--size 1024] [--frames 20] [--width 1920] [--height 1080] [--max-len 5] [--step-timeout 300]
 
 The scene of tfdm_common.lit_mixed_scene (a plain teapot on a displaced ground quad, a displaced wall behind it, an emissive
 rectangle above, one size x size height map), G-buffer pass + baseline path tracer per frame:
@@ -16,6 +16,11 @@ With --nrtdsm / --shell one more row, the scene of tools/bench_scene_trace.py --
                      shell-aware renderer kernels and k_scene_instances_shell in every trace
 
 and the result has "<row>_over_displaced_ms".
+
+With --regir every row renders a ReGIR frame instead (build cells, temporal after frame 0; GFX_PT_PATH_TRACE_REGIR; update last access:
+tfdm_common.RegirFrames) over a grid of 16 x 8 x 16 cells on the scene's bounds joined with the set's (gfx_tfdm_set_bounds), the
+displaced rows through a binding that carries GFX_DISPLACED_REGIR; the metric is "displaced_render_regir".  Timing, kernel shares
+and bytes as without it.
 
 Per side: milliseconds per frame (HIP events around --frames frames after 3 warm-up frames), the per-kernel times of one more frame
 from the context's timers, and the device bytes of the geometry (displaced: the object and the instance table; tessellated: BVH8
@@ -41,7 +46,7 @@ def _arg(argv, name, default):
     return type(default)(argv[argv.index(name) + 1]) if name in argv else default
 
 
-def step(name, size, frames, w, h, max_len):
+def step(name, size, frames, w, h, max_len, regir=False):
     import torch
     from gfxexp_amd import api
     import tfdm_common as K
@@ -70,11 +75,11 @@ def step(name, size, frames, w, h, max_len):
             tset.add(wall if wall is not None and k == len(instances) - 1 else tf, m, uid)
         tset.commit()
         if wall is None:
-            ctx.bind_displaced(tset, [slot] * len(instances))
+            ctx.bind_displaced(tset, [slot] * len(instances), regir=regir)
         else:
-            ctx.bind_displaced_kinds(tset, [slot] * (len(instances) - 1) + [(slot, [shell_mat]) if name == "displaced_shell" else slot])
+            ctx.bind_displaced_kinds(tset, [slot] * (len(instances) - 1) + [(slot, [shell_mat]) if name == "displaced_shell" else slot], regir=regir)
         out["device_bytes"] = tf.device_bytes() + (wall.device_bytes() if wall is not None else 0) + api.TFDM_RECORD_BYTES * len(instances)
-    fr = K.PathTraceFrames(ctx, accel, w, h)
+    fr = K.RegirFrames(ctx, accel, w, h, K.joined_bounds(hs.bounds(), None if tess else tset)) if regir else K.PathTraceFrames(ctx, accel, w, h)
     cam = K.look_at_camera(w, h, pos, target)
     stream = torch.cuda.current_stream().cuda_stream
     for k in range(3):
@@ -101,14 +106,14 @@ def main(argv):
     size, frames, max_len = _arg(argv, "--size", 1024), _arg(argv, "--frames", 20), _arg(argv, "--max-len", 5)
     w, h = _arg(argv, "--width", 1920), _arg(argv, "--height", 1080)
     if "--step" in argv:
-        print("STEP_RESULT " + json.dumps(step(argv[argv.index("--step") + 1], size, frames, w, h, max_len)))
+        print("STEP_RESULT " + json.dumps(step(argv[argv.index("--step") + 1], size, frames, w, h, max_len, "--regir" in argv)))
         return 0
     limit = _arg(argv, "--step-timeout", 300)
-    result = {"metric": "displaced_render", "size": size, "frames": frames, "width": w, "height": h, "max_len": max_len}
+    result = {"metric": "displaced_render_regir" if "--regir" in argv else "displaced_render", "size": size, "frames": frames, "width": w, "height": h, "max_len": max_len}
     steps = STEPS + [KIND_STEPS[f] for f in KIND_STEPS if f in argv]
     for name in steps:
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name, "--size", str(size), "--frames", str(frames),
-               "--width", str(w), "--height", str(h), "--max-len", str(max_len)]
+               "--width", str(w), "--height", str(h), "--max-len", str(max_len)] + (["--regir"] if "--regir" in argv else [])
         r = subprocess.run(cmd, capture_output=True, text=True)
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("STEP_RESULT ")]
         if r.returncode != 0 or not line:

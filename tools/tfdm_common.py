@@ -212,6 +212,59 @@ class PathTraceFrames:
         return self.t["beauty"].cpu().numpy().view(np.float32).reshape(-1, 4)
 
 
+class RegirFrames(PathTraceFrames):
+    """... and a ReGIR grid over `bounds` (lo + hi, six floats: the scene's bounds joined with the bound set's, whose members are not in
+    the BVH8), with one frame of the ReGIR loop: G-buffer, build cells (temporal after frame 0), PATH_TRACE_REGIR, update last access
+    (regir_main.cpp:2021-2066)."""
+    SLOTS_PER_CELL = 512
+
+    def __init__(self, ctx, accel, width, height, bounds, dims=(16, 8, 16), seed=591842031321323413):
+        import torch
+        super().__init__(ctx, accel, width, height, seed)
+        cells = int(dims[0]) * int(dims[1]) * int(dims[2])
+        slots = cells * self.SLOTS_PER_CELL
+        z = lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        self.t["regir_rngs"] = torch.from_numpy(api.seed_rng_states(slots, seed).view(np.uint8)).cuda()
+        self.t["regir_accesses"] = z(4 * cells)
+        self.t["regir_last_access"] = torch.full((4 * cells,), 0xFF, dtype=torch.uint8, device="cuda")
+        g = api.GfxRegirParams()
+        for i in range(2):
+            self.t.update({"regir_res_%d" % i: z(48 * slots), "regir_info_%d" % i: z(8 * slots), "regir_active_%d" % i: z(4)})
+            g.reservoirs[i], g.reservoirInfos[i] = self.t["regir_res_%d" % i].data_ptr(), self.t["regir_info_%d" % i].data_ptr()
+            g.numActiveCells[i] = self.t["regir_active_%d" % i].data_ptr()
+        g.lightSlotRngs, g.perCellNumAccesses = self.t["regir_rngs"].data_ptr(), self.t["regir_accesses"].data_ptr()
+        g.lastAccessFrameIndices = self.t["regir_last_access"].data_ptr()
+        lo, hi = np.asarray(bounds[:3], np.float32), np.asarray(bounds[3:], np.float32)
+        size = ((hi - lo) / np.asarray(dims, np.float32)).astype(np.float32)
+        for k in range(3):
+            g.gridOrigin[k], g.gridCellSize[k], g.gridDimension[k] = float(lo[k]), float(size[k]), int(dims[k])
+        g.log2NumCandidatesPerLightSlot, g.log2NumCandidatesPerCell, g.enableCellRandomization = 3, 2, 1
+        self.g = g
+
+    def frame(self, index, cam, max_len=5, stream=0):
+        f = api.GfxRestirFrameParams()
+        C.memmove(C.byref(f.camera), C.byref(cam), C.sizeof(cam))
+        C.memmove(C.byref(f.prevCamera), C.byref(cam), C.sizeof(cam))
+        f.travHandle, f.numAccumFrames, f.frameIndex, f.bufferIndex = self.accel, index, index, index % 2
+        f.resetFlowBuffer, f.enableJittering, f.envLightPowerCoeff = int(index == 0), 1, 1.0
+        ctx = self.ctx
+        ctx.lights_build_instances(stream)
+        ctx.restir_set_params(self.s, f, 0, 0, stream)
+        ctx.regir_set_params(self.g)
+        build = api.PT_REGIR_BUILD_CELLS_TEMPORAL if index else api.PT_REGIR_BUILD_CELLS
+        for pass_id in (api.PT_SETUP_GBUFFERS, build, api.PT_PATH_TRACE_REGIR, api.PT_REGIR_UPDATE_LAST_ACCESS):
+            ctx.pt_launch(pass_id, self.w, self.h, max_len, 0, 0, stream)
+
+
+def joined_bounds(scene_bounds, tset=None):
+    """lo + hi (six floats) of the scene's bounds joined with a displaced-instance set's (TfdmSet.bounds), for a ReGIR grid."""
+    b = np.asarray(scene_bounds, np.float32)
+    if tset is None:
+        return b
+    lo, hi = tset.bounds()
+    return np.concatenate([np.minimum(b[:3], lo), np.maximum(b[3:], hi)]).astype(np.float32)
+
+
 class RestirFrames(PathTraceFrames):
     """... and the buffers of the ReSTIR DI passes (reservoirs, reservoir info, sample visibility, neighbour deltas) with one frame of
     G-buffer, initial + temporal (biased), `spatial` biased spatial passes and shading, sequenced as restir_di_main.cpp does."""

@@ -52,6 +52,12 @@ G-buffer pass and the baseline path tracer), --frames accumulated frames, writte
 spatial passes, shading; the shadow rays are the scene's any-hit query), --frames accumulated frames, written tone-mapped as
 <out>_restir.png.
 
+    python tools/tfdm_view.py --scene --regir [--nrtdsm | --shell] [--frames 64] [--size 256] [--width 960] [--height-px 540] [--out tfdm_view]
+
+--regir: the scene of --render through the ReGIR frame loop under a binding that carries GFX_DISPLACED_REGIR (G-buffer, build cells --
+temporal after frame 0 --, GFX_PT_PATH_TRACE_REGIR, update last access), the grid over the scene's bounds joined with the set's
+(gfx_tfdm_set_bounds: the displaced members are not in the BVH8), --frames accumulated frames, written tone-mapped as <out>_regir.png.
+
     python tools/tfdm_view.py --scene --restir --move N [--step 0.02] [--size 256] [--width 960] [--height-px 540] [--out tfdm_view]
 
 --move N: N frames of the --restir scene with the wall translating by --step along x per frame (gfx_tfdm_set_move + commit before each
@@ -133,12 +139,15 @@ def scene_render(a):
         tset.add(wall if wall is not None and k == len(instances) - 1 else tf, m, uid)
     tset.commit()
     if wall is None:
-        ctx.bind_displaced(tset, [slot] * len(instances), restir=a.restir)
+        ctx.bind_displaced(tset, [slot] * len(instances), restir=a.restir, regir=a.regir)
     else:
         members = [slot] * (len(instances) - 1) + [(slot, [shell_mat]) if a.shell else slot]
-        ctx.bind_displaced_kinds(tset, members, restir=a.restir)
+        ctx.bind_displaced_kinds(tset, members, restir=a.restir, regir=a.regir)
     w, h = a.width, a.height_px
-    frames = K.RestirFrames(ctx, accel, w, h) if a.restir else K.PathTraceFrames(ctx, accel, w, h)
+    if a.regir:
+        frames = K.RegirFrames(ctx, accel, w, h, K.joined_bounds(hs.bounds(), tset))
+    else:
+        frames = K.RestirFrames(ctx, accel, w, h) if a.restir else K.PathTraceFrames(ctx, accel, w, h)
     cam = K.look_at_camera(w, h, pos, target)
     stream = torch.cuda.current_stream().cuda_stream
     if a.move:
@@ -151,12 +160,12 @@ def scene_render(a):
         frames.frame(k, cam, stream=stream, **({"accumulate": False} if ripple and a.restir else {}))
     beauty = frames.beauty()
     ctx.bind_displaced_kinds(None)
-    image = a.out + ("_restir.png" if a.restir else "_render.png")
+    image = a.out + ("_restir.png" if a.restir else "_regir.png" if a.regir else "_render.png")
     api.save_image_sdr(image, beauty, w, h, api.sdr_config(brightness=1.0, tone_map=True, gamma=True))
     g0 = frames.t["gb0_%d" % (((a.ripple or a.frames) - 1) % 2)].cpu().numpy().view(np.uint32).reshape(-1, 4)[:, 0]
     print(json.dumps({"scene": "teapot on displaced ground, displaced wall, emissive rectangle", "size": int(heights.shape[0]), "frames": a.ripple or a.frames, "ripple": bool(a.ripple),
                       "displaced_pixel_share": round(float(((g0 != api.GFX_INVALID_SLOT) & (g0 >= api.GBUFFER_DISPLACED)).mean()), 4),
-                      "renderer": "restir_di" if a.restir else "path_tracer", "wall": "nrtdsm" if a.nrtdsm else "shell" if a.shell else "tfdm", "mean_radiance": round(float(beauty[:, :3].mean()), 5), "images": [image]}))
+                      "renderer": "restir_di" if a.restir else "regir" if a.regir else "path_tracer", "wall": "nrtdsm" if a.nrtdsm else "shell" if a.shell else "tfdm", "mean_radiance": round(float(beauty[:, :3].mean()), 5), "images": [image]}))
     return 0
 
 
@@ -320,6 +329,7 @@ def main():
     ap.add_argument("--scene", action="store_true")
     ap.add_argument("--render", action="store_true")
     ap.add_argument("--restir", action="store_true")
+    ap.add_argument("--regir", action="store_true")
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--move", type=int, default=0)
     ap.add_argument("--step", type=float, default=0.02)
@@ -331,7 +341,9 @@ def main():
         ap.error("--move goes with --scene --restir")
     if a.ripple and (a.shell or a.move or a.height):
         ap.error("--ripple writes into the procedural height map of a TFDM or an NRTDSM object; it goes with neither --shell, --move nor --height")
-    if a.render or a.restir:
+    if a.regir and (not a.scene or a.restir or a.move or a.ripple):
+        ap.error("--regir goes with --scene, and with neither --restir, --move nor --ripple")
+    if a.render or a.restir or a.regir:
         if a.shell and a.nrtdsm:
             ap.error("--scene takes the wall as --nrtdsm or as --shell, not both")
         return scene_render(a)
