@@ -21,6 +21,7 @@
 #include "coop_fetch.hip.h"
 #include "trace_local.hip.h"
 #include "restir_rearch.hip.h"
+#include "pass_launch.hip.h"
 #include "tfdm/tfdm_set.h"
 #include "tfdm/displaced_surface.hip.h"
 #include "nrtdsm/displaced_kinds.hip.h"
@@ -1216,9 +1217,7 @@ static RestirArgs make_args(Context& ctx, uint32_t width, uint32_t height, uint3
 template <typename K>
 static void launch_pixels(Context& ctx, hipStream_t stream, const char* name, K kernel, const RestirArgs& a) {
     if (a.px.rowEnd == a.px.rowBegin) return;
-    ScopedKernelTimer timer(ctx, stream, name);
-    hipLaunchKernelGGL(kernel, dim3(a.px.launchBlocks), dim3(kBlock), 0, stream, a);
-    GFX_HIP(hipGetLastError());
+    launch_timed(ctx, stream, name, kernel, dim3(a.px.launchBlocks), dim3(kBlock), a);
 }
 
 // The shadow rays of a ray pass.  fixedCount: one entry per launch slot; useCounter: the device count a.rayCount, of at most `capacity`
@@ -1228,22 +1227,11 @@ static void trace_queue(Context& ctx, hipStream_t stream, const RestirArgs& a, i
     Context::LastRays& last = ctx.lastRays;
     last.state = 1; last.org = a.rayOrg; last.dir = a.rayDir; last.out = out;
     last.fixedCount = fixedCount; last.countPtr = useCounter ? a.rayCount : nullptr;
-    if (ctx.displaced.set && (ctx.displaced.passMask & GFX_DISPLACED_RESTIR)) {
-        const DevAccel accel = ctx.accels[ctx.restir.f.travHandle - 1]->dev();
-        SceneTrace t;
-        t.accel = &accel; t.set = ctx.displaced.set; t.mode = mode;
-        t.rayOrgTmin = a.rayOrg; t.rayDirTmax = a.rayDir;
-        t.numRays = useCounter ? capacity : fixedCount; t.numRaysPtr = useCounter ? a.rayCount : nullptr;
-        t.out = out;
-        trace_scene_launch(ctx, stream, t);
-        return;
-    }
-    TraceLaunch t;
-    t.accel = ctx.accels[ctx.restir.f.travHandle - 1]->dev();
-    t.rayOrgTmin = a.rayOrg; t.rayDirTmax = a.rayDir;
-    t.numRays = fixedCount; t.numRaysPtr = useCounter ? a.rayCount : nullptr;
-    t.out = out; t.mode = mode;
-    trace_launch(ctx, stream, t);
+    SceneTrace q;
+    q.rayOrgTmin = a.rayOrg; q.rayDirTmax = a.rayDir; q.mode = mode; q.out = out;
+    q.numRays = useCounter ? capacity : fixedCount; q.numRaysPtr = useCounter ? a.rayCount : nullptr;
+    // the set is in play for the ray passes only under a binding that carries GFX_DISPLACED_RESTIR
+    trace_ray_queue(ctx, stream, ctx.accels[ctx.restir.f.travHandle - 1]->dev(), ctx.displaced.set && (ctx.displaced.passMask & GFX_DISPLACED_RESTIR), q);
 }
 
 // ---------------------------------------------------------------- output chain (copy_buffers.cu:6-80)
@@ -1289,17 +1277,15 @@ void restir_copy_to_linear(Context& ctx, hipStream_t stream, void* color, void* 
     const gfx_restir_static_params& s = ctx.restir.s;
     const size_t n = static_cast<size_t>(s.imageSizeX) * s.imageSizeY;
     if (!n) return;
-    hipLaunchKernelGGL(k_copy_to_linear, dim3(static_cast<uint32_t>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, s, ctx.restir.f.bufferIndex, n,
-                       static_cast<float4*>(color), static_cast<float4*>(albedo), static_cast<float4*>(normal), static_cast<float2*>(motion));
-    GFX_HIP(hipGetLastError());
+    launch_checked(stream, k_copy_to_linear, dim3(static_cast<uint32_t>((n + kBlock - 1) / kBlock)), dim3(kBlock), s, ctx.restir.f.bufferIndex, n,
+                   static_cast<float4*>(color), static_cast<float4*>(albedo), static_cast<float4*>(normal), static_cast<float2*>(motion));
 }
 void restir_visualize(Context& ctx, hipStream_t stream, const void* linearBuffer, int bufferType, float mvOffset, float mvScale, uint32_t width, uint32_t height, void* out) {
     (void)ctx;
     const size_t n = static_cast<size_t>(width) * height;
     if (!n) return;
-    hipLaunchKernelGGL(k_visualize, dim3(static_cast<uint32_t>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, linearBuffer, bufferType, mvOffset, mvScale, n,
-                       static_cast<float4*>(out));
-    GFX_HIP(hipGetLastError());
+    launch_checked(stream, k_visualize, dim3(static_cast<uint32_t>((n + kBlock - 1) / kBlock)), dim3(kBlock), linearBuffer, bufferType, mvOffset, mvScale, n,
+                   static_cast<float4*>(out));
 }
 
 void restir_primary_rays(Context& ctx, hipStream_t stream, uint32_t width, uint32_t height, void* dRayOrgTmin, void* dRayDirTmax) {
@@ -1307,8 +1293,7 @@ void restir_primary_rays(Context& ctx, hipStream_t stream, uint32_t width, uint3
     if ((reinterpret_cast<uintptr_t>(dRayOrgTmin) | reinterpret_cast<uintptr_t>(dRayDirTmax)) & 15u) throw HipError("gfx_restir_primary_rays: the outputs must be 16-byte aligned");
     const RestirArgs a = make_args(ctx, width, height, 0, height, false);
     if (a.px.launchBlocks == 0) return;
-    hipLaunchKernelGGL(k_primary_rays_inspect, dim3(a.px.launchBlocks), dim3(kBlock), 0, stream, a, static_cast<float4*>(dRayOrgTmin), static_cast<float4*>(dRayDirTmax));
-    GFX_HIP(hipGetLastError());
+    launch_checked(stream, k_primary_rays_inspect, dim3(a.px.launchBlocks), dim3(kBlock), a, static_cast<float4*>(dRayOrgTmin), static_cast<float4*>(dRayDirTmax));
 }
 
 void restir_last_rays(Context& ctx, hipStream_t stream, void* dRayOrgTmin, void* dRayDirTmax, void* dOccluded, uint32_t capacity, uint32_t* count) {
@@ -1364,14 +1349,12 @@ void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, u
     const size_t fusedSpillBytes = sizeof(uint2) * static_cast<size_t>(a.px.launchBlocks) * kBlock * spillCap;
     // (a bound set: the three-kernel form whatever "fuse_passes" says -- the fused kernels trace through trace_local and cannot see it)
     const bool fused = !displaced && !ctx.countersEnabled && fusedSpillBytes <= (size_t(1) << 30) && (ctx.tune.fusePasses == 2 || (ctx.tune.fusePasses == 0 && fusableLaunch));
-    // Cost-ordered block start (block_order_begin / _end below) for the kernels whose launch is several rounds of blocks.
+    // Cost-ordered block start (launch_cost_ordered, pass_launch.hip.h) for the kernels whose launch is several rounds of blocks.
     const uint64_t orderKey = (static_cast<uint64_t>(rowBegin) << 44) ^ (static_cast<uint64_t>(rowEnd) << 24) ^ (static_cast<uint64_t>(width) << 4);
     const uint32_t orderMinBlocks = 8u * static_cast<uint32_t>(ctx.numCUs);     // up to about one round: they all start together
-    auto block_order_begin = [&](int which, uint32_t blocks, uint32_t variant, const uint32_t*& order, uint32_t*& cost) {
-        gfx::block_order_begin(ctx, stream, which, blocks, orderKey ^ variant, orderMinBlocks, order, cost);
-        a.px.order = order;
+    auto cost_ordered = [&](int which, uint32_t blocks, uint32_t variant, auto launch) {
+        launch_cost_ordered(ctx, stream, which, blocks, orderKey ^ variant, orderMinBlocks, a.px, launch);
     };
-    auto block_order_end = [&](int which, uint32_t blocks, uint32_t* cost) { gfx::block_order_end(ctx, stream, which, blocks, cost); };
     // (Not for the kernels that gather from neighbouring pixels: started in the candidate kernel's cost order k_spatial took 0.47 ms per
     // frame instead of 0.37 -- blocks of equal cost are scattered over the image, and the XCD-supertile block order is what keeps a tile's
     // neighbours in its XCD's L2.  profiles/r04_experiments.txt 19.)
@@ -1393,55 +1376,39 @@ void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, u
         // primary rays are coherent (neighbouring lanes walk nearly the same nodes, the temporal hint ends most of them early): the
         // wave-local traversal loses little to the missing refill and saves the ray queue and two launches at every size (rearchitected
         // ReSTIR at 1920x1080: 2.250 -> 2.115 ms per frame, NRC 3.65 -> 3.53) -- fused unless "fuse_passes" says never
+        const DevAccel accel = ctx.accels[ctx.restir.f.travHandle - 1]->dev();
+        SceneTrace q;                      // the primary rays of the wavefront forms: one per launch slot, own scratch
+        q.rayOrgTmin = a.rayOrg; q.rayDirTmax = a.rayDir; q.numRays = numSlots; q.mode = GFX_TRACE_CLOSEST;
+        q.spill = &ctx.gbSpill; q.counters = &ctx.gbCounters;
+        q.hintFromOut = true;            // gbRayHits keeps the previous frame's (plain) hit of every ray slot
         if (displaced) {
-            // the wavefront form whatever "fuse_passes" says: the trace is the scene query.  Its plain phase writes gbRayHits, which so
-            // stays the temporal hint store; the instance phase widens into a buffer of the binding's own.
+            // the wavefront form whatever "fuse_passes" says: the trace is the scene query (under any binding).  Its plain phase writes
+            // gbRayHits, which so stays the temporal hint store; the instance phase widens into a buffer of the binding's own.
             ctx.displaced.gbHits.reserve(sizeof(gfx_scene_hit) * frameSlots);
             launch_pixels(ctx, stream, "primary_rays", k_primary_rays, a);
-            const DevAccel accel = ctx.accels[ctx.restir.f.travHandle - 1]->dev();
-            SceneTrace t;
-            t.accel = &accel; t.set = ctx.displaced.set; t.mode = GFX_TRACE_CLOSEST;
-            t.rayOrgTmin = a.rayOrg; t.rayDirTmax = a.rayDir;
-            t.numRays = numSlots;
-            t.out = ctx.displaced.gbHits.p; t.plainHits = ctx.gbRayHits.p;
-            t.spill = &ctx.gbSpill; t.counters = &ctx.gbCounters;
-            t.hintFromOut = true;
+            q.out = ctx.displaced.gbHits.p; q.plainHits = ctx.gbRayHits.p;
             // a kinds binding over a set with a shell member: the instance phase writes the shell part of every slot it traces
             const bool shell = displaced_shell_render(ctx);
-            if (shell) { ctx.displaced.gbShellPart.reserve(sizeof(gfx_scene_shell_part) * frameSlots); t.shellPart = ctx.displaced.gbShellPart.p; }
-            trace_scene_launch(ctx, stream, t);
-            ScopedKernelTimer timer(ctx, stream, shell ? "gbuffer_resolve_scene_shell" : "gbuffer_resolve_scene");
+            if (shell) { ctx.displaced.gbShellPart.reserve(sizeof(gfx_scene_shell_part) * frameSlots); q.shellPart = ctx.displaced.gbShellPart.p; }
+            trace_ray_queue(ctx, stream, accel, true, q);
+            const dim3 grid(a.px.launchBlocks), block(kBlock);
             if (shell)
-                hipLaunchKernelGGL(k_gbuffer_resolve_scene_shell, dim3(a.px.launchBlocks), dim3(kBlock), 0, stream, a, displaced_args(ctx, ctx.displaced.gbHits.p),
-                                   displaced_shell_args(ctx, ctx.displaced.gbShellPart.p));
-            else
-                hipLaunchKernelGGL(k_gbuffer_resolve_scene, dim3(a.px.launchBlocks), dim3(kBlock), 0, stream, a, displaced_args(ctx, ctx.displaced.gbHits.p));
-            GFX_HIP(hipGetLastError());
+                launch_timed(ctx, stream, "gbuffer_resolve_scene_shell", k_gbuffer_resolve_scene_shell, grid, block, a, displaced_args(ctx, ctx.displaced.gbHits.p),
+                             displaced_shell_args(ctx, ctx.displaced.gbShellPart.p));
+            else launch_timed(ctx, stream, "gbuffer_resolve_scene", k_gbuffer_resolve_scene, grid, block, a, displaced_args(ctx, ctx.displaced.gbHits.p));
             break;
         }
         if (!ctx.countersEnabled && fusedSpillBytes <= (size_t(1) << 30) && ctx.tune.fusePasses != 1) {
             ctx.gbSpill.reserve(fusedSpillBytes);
-            const uint32_t* order = nullptr;
-            uint32_t* cost = nullptr;
-            block_order_begin(2, a.px.launchBlocks, 0u, order, cost);
-            {
-                ScopedKernelTimer timer(ctx, stream, "gbuffer_fused");
-                hipLaunchKernelGGL(k_gbuffer_fused, dim3(a.px.launchBlocks), dim3(kBlock), 0, stream, a, ctx.accels[ctx.restir.f.travHandle - 1]->dev(),
-                                   ctx.gbRayHits.as<gfx_hit>(), ctx.gbSpill.as<uint2>(), spillCap, ctx.tune.temporalHints ? 1 : 0, cost);
-                GFX_HIP(hipGetLastError());
-            }
-            block_order_end(2, a.px.launchBlocks, cost);
+            cost_ordered(2, a.px.launchBlocks, 0u, [&](uint32_t* cost) {
+                launch_timed(ctx, stream, "gbuffer_fused", k_gbuffer_fused, dim3(a.px.launchBlocks), dim3(kBlock), a, accel,
+                             ctx.gbRayHits.as<gfx_hit>(), ctx.gbSpill.as<uint2>(), spillCap, ctx.tune.temporalHints ? 1 : 0, cost);
+            });
             break;
         }
         launch_pixels(ctx, stream, "primary_rays", k_primary_rays, a);
-        TraceLaunch t;
-        t.accel = ctx.accels[ctx.restir.f.travHandle - 1]->dev();
-        t.rayOrgTmin = a.rayOrg; t.rayDirTmax = a.rayDir;
-        t.numRays = numSlots; t.numRaysPtr = nullptr;
-        t.out = ctx.gbRayHits.p; t.mode = GFX_TRACE_CLOSEST;
-        t.spill = &ctx.gbSpill; t.counters = &ctx.gbCounters;
-        t.hintFromOut = true;   // gbRayHits keeps the previous frame's hit of every ray slot
-        trace_launch(ctx, stream, t);
+        q.out = ctx.gbRayHits.p;
+        trace_ray_queue(ctx, stream, accel, false, q);
         launch_pixels(ctx, stream, "gbuffer_resolve", k_gbuffer_resolve, a);
         break;
     }
@@ -1468,16 +1435,10 @@ void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, u
                 if (tex) kernel = split == 4 ? GFX_PICK(true, 4) : GFX_PICK(true, 1);
                 else kernel = split == 4 ? GFX_PICK(false, 4) : GFX_PICK(false, 1);
 #undef GFX_PICK
-                const uint32_t* order = nullptr;
-                uint32_t* cost = nullptr;
-                block_order_begin(0, grid, split, order, cost);
-                {
-                    ctx.lastRays.state = 2;
-                    ScopedKernelTimer timer(ctx, stream, "initial_fused");
-                    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, a, accel, ctx.spill.as<uint2>(), spillCap, cost);
-                    GFX_HIP(hipGetLastError());
-                }
-                block_order_end(0, grid, cost);
+                ctx.lastRays.state = 2;
+                cost_ordered(0, grid, split, [&](uint32_t* cost) {
+                    launch_timed(ctx, stream, "initial_fused", kernel, dim3(grid), dim3(kBlock), a, accel, ctx.spill.as<uint2>(), spillCap, cost);
+                });
                 break;
             }
             // one lane per pixel: the two-phase loop that skips provably zero-weight candidates ("candidate_prefilter", emitter_cull.h)
@@ -1487,15 +1448,9 @@ void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, u
                    : prefilter ? k_initial_candidates<true, 1, true> : k_initial_candidates<true, 1, false>)
                 : (split == 4 ? k_initial_candidates<false, 4, false> : split == 2 ? k_initial_candidates<false, 2, false>
                    : prefilter ? k_initial_candidates<false, 1, true> : k_initial_candidates<false, 1, false>);
-            const uint32_t* order = nullptr;
-            uint32_t* cost = nullptr;
-            block_order_begin(3, grid, split, order, cost);
-            {
-                ScopedKernelTimer timer(ctx, stream, "initial_candidates");
-                hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, a, cost);
-                GFX_HIP(hipGetLastError());
-            }
-            block_order_end(3, grid, cost);
+            cost_ordered(3, grid, split, [&](uint32_t* cost) {
+                launch_timed(ctx, stream, "initial_candidates", kernel, dim3(grid), dim3(kBlock), a, cost);
+            });
             a.px.order = nullptr;                      // the trace and the temporal kernel below run in index order
         }
         trace_queue(ctx, stream, a, GFX_TRACE_ANY, a.px.launchBlocks * kBlock, false, ctx.rayOut.p);   // one entry per launch slot (emit_ray_at_slot)
@@ -1520,16 +1475,10 @@ void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, u
             ctx.lastRays.state = 2;
             ctx.spill.reserve(fusedSpillBytes);
             const bool both = pass == GFX_RESTIR_SPATIAL_BIASED_AND_SHADING;
-            const uint32_t* order = nullptr;
-            uint32_t* cost = nullptr;
-            block_order_begin(1, a.px.launchBlocks, both ? 1u : 0u, order, cost);
-            {
-                ScopedKernelTimer timer(ctx, stream, both ? "spatial_shading_fused" : "shading_fused");
-                hipLaunchKernelGGL(both ? k_shading_fused<true> : k_shading_fused<false>, dim3(a.px.launchBlocks), dim3(kBlock), 0, stream, a,
-                                   ctx.accels[ctx.restir.f.travHandle - 1]->dev(), ctx.spill.as<uint2>(), spillCap, cost);
-                GFX_HIP(hipGetLastError());
-            }
-            block_order_end(1, a.px.launchBlocks, cost);
+            cost_ordered(1, a.px.launchBlocks, both ? 1u : 0u, [&](uint32_t* cost) {
+                launch_timed(ctx, stream, both ? "spatial_shading_fused" : "shading_fused", both ? k_shading_fused<true> : k_shading_fused<false>,
+                             dim3(a.px.launchBlocks), dim3(kBlock), a, ctx.accels[ctx.restir.f.travHandle - 1]->dev(), ctx.spill.as<uint2>(), spillCap, cost);
+            });
             break;
         }
         if (pass == GFX_RESTIR_SPATIAL_BIASED_AND_SHADING) launch_pixels(ctx, stream, "spatial_shade_prepare", k_spatial_shade_prepare, a);
@@ -1539,18 +1488,14 @@ void restir_launch(Context& ctx, hipStream_t stream, int pass, uint32_t width, u
         break;
     case GFX_RESTIR_LIGHT_PRESAMPLING: {
         if (!a.s.lightPreSamplingRngs || !a.s.preSampledLights) throw HipError("gfx_restir_launch: light pre-sampling buffers are not set");
-        ScopedKernelTimer timer(ctx, stream, "light_presample");
-        hipLaunchKernelGGL(k_light_presample, dim3(kNumPreSampledLights / kBlock), dim3(kBlock), 0, stream, a);
-        GFX_HIP(hipGetLastError());
+        launch_timed(ctx, stream, "light_presample", k_light_presample, dim3(kNumPreSampledLights / kBlock), dim3(kBlock), a);
         break;
     }
     case GFX_RESTIR_PER_PIXEL_RIS: {
         if (rowBegin % 8 != 0) throw HipError("gfx_restir_launch_rows: per-pixel RIS bands must start on an 8-row tile boundary");
         const uint32_t tilesX = (width + 7) / 8, tileRows = (rowEnd + 7) / 8 - rowBegin / 8;
         const uint32_t numTiles = tilesX * tileRows;
-        ScopedKernelTimer timer(ctx, stream, "per_pixel_ris");
-        hipLaunchKernelGGL(k_per_pixel_ris, dim3((numTiles + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, stream, a);
-        GFX_HIP(hipGetLastError());
+        launch_timed(ctx, stream, "per_pixel_ris", k_per_pixel_ris, dim3((numTiles + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), a);
         break;
     }
     case GFX_RESTIR_TRACE_SHADOW_RAYS:
